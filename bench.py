@@ -14,7 +14,14 @@ RCCL and assembled into the full frame on every rank ("strong" scaling: the imag
 exchange of frame f runs on a communication stream while the renderer's stream traces frame f + 1;
 the timed region ends only when the last frame is assembled on every rank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene sponza|cornell] [--no-cpu-baseline]
+A plain run sets up, warms up, times the K steps once, writes the outputs of the timed path when
+--dump-outputs is given, and prints the result line.  --full adds everything else the benchmark
+measures or checks: the repeated timed regions (median), frame latency, per-kernel times, the
+roofline, path regeneration beside the serial loop, the CPU baseline, the film hash and the
+unsharded re-render with N > 1, and on the default workload the atrium companion and the two
+other trees.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene sponza|cornell] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -38,6 +45,23 @@ def algorithmic_bytes(nodes, tris, rays):
 
 
 L2_PEAK_GBS = 34500.0      # aggregate L2 bandwidth, MI355X_MICROARCH.md (L2 section)
+OUTPUT_BUDGET_BYTES = 60_000_000       # --dump-outputs: all files together stay below 64 MB
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float32.  An [H, W, C] array larger than its share of the budget is stored
+    as a fixed, seeded sample of its pixels (<name>.npy: [k, C], pixel order) with their flat indices in <name>_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    share = OUTPUT_BUDGET_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        if a.nbytes > share:
+            px = a.reshape(a.shape[0] * a.shape[1], -1)
+            k = share // (px.shape[1] * 4 + 8)
+            idx = np.sort(np.random.default_rng(0).choice(len(px), k, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = px[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def profile_counters(scene, w, h, spp, depth, svgf, brk_multi=False):
@@ -165,8 +189,12 @@ def main_mgpu(args):
     m.synchronize()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    if args.dump:
-        np.save(args.dump, m.download_film())
+    if args.dump or args.dump_outputs:
+        film = m.download_film()
+        if args.dump:
+            np.save(args.dump, film)
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, {"film": film})
     print(json.dumps({
         "metric": "Mrays/sec (W*H*spp/1e6/s, reference definition)", "value": round(W * H * spp / 1e6 / (elapsed / args.steps), 3),
         "unit": "Mrays/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
@@ -179,10 +207,11 @@ def main_mgpu(args):
 
 
 def run_workload(args, cfg, ctx):
-    """One benchmark workload end to end: W warm-up frames, the timed K frames, the same frames with HIP events, the same
-    frames with ONE frame in flight (latency), a counting pass, an isolated-kernel pass, the CPU baseline.  Returns the
-    result dict on rank 0 (None elsewhere).  cfg: scene, width, height, spp, depth, svgf, all_samples, frames_in_flight,
-    experiment, cpu_baseline; ctx: torch, dist, rank, local_rank, world, use_dist."""
+    """One benchmark workload end to end: W warm-up frames and the timed K frames; with cfg["full"] also the repeated timed
+    regions, path regeneration beside them, the same frames with ONE frame in flight (latency), the same frames with HIP events,
+    a counting pass, an isolated-kernel pass, the CPU baseline.  Returns the result dict on rank 0 (None elsewhere).  cfg:
+    scene, width, height, spp, depth, svgf, all_samples, frames_in_flight, experiment, cpu_baseline, full, dump, dump_outputs;
+    ctx: torch, dist, rank, local_rank, world, use_dist."""
     torch, dist = ctx["torch"], ctx["dist"]
     rank, local_rank, world, use_dist = ctx["rank"], ctx["local_rank"], ctx["world"], ctx["use_dist"]
     from aten_amd.interop import tensor_from_ptr
@@ -311,15 +340,16 @@ def run_workload(args, cfg, ctx):
 
     for i in range(warmup):
         step(i, False)
-    # The timed region is EXACTLY K steps between barriers + synchronisations; it is timed `repeats` times over (each from a
-    # reset film) and `value` is the MEDIAN: one 20-step region is 84 ms, box noise +-1-2 %, the same size as a round's gain
+    # The timed region is EXACTLY K steps between barriers + synchronisations.  A plain run times it once; with --full it is
+    # timed `repeats` times over (each from a reset film) and `value` is the MEDIAN: one 20-step region is 84 ms, noise
+    # +-1-2 %, the same size as a round's gain
     repeats = max(1, args.repeats)
     region_s = []
     for _ in range(repeats):
         r.reset()
         region_s.append(timed(steps))
     # --repeats 0 ... no: a SHORT region (the driver's 20 steps are 70 ms) is repeated until the timed regions add up to
-    # `--min-timed-seconds` of GPU work (default 2 s, at most 64 repeats): a steadier median, and a GPU that an outside
+    # `--min-timed-seconds` of GPU work (--full: default 2 s, at most 64 repeats): a steadier median, and a GPU that an outside
     # sampler can see busy.  Every rank takes the same decision (the first region's duration is the max over ranks).
     if args.min_timed_seconds > 0 and region_s[0] > 0:
         want = int(min(64, np.ceil(args.min_timed_seconds / max(region_s[0], 1e-6))))
@@ -333,16 +363,63 @@ def run_workload(args, cfg, ctx):
         repeats = len(region_s)
     elapsed = float(np.median(region_s))
     host_enqueue_ms = 1e3 * host_enqueue[0] / steps
-    # the film the timed frames produced (K progressive frames from a reset film): its hash goes into the line, so that the
-    # N = 1, 2, 4, 8 records of a scaling run can be held against each other (the image does not depend on the sharding)
+    ms_per_step = 1e3 * elapsed / steps
+    mrays = W * H * spp / 1e6 / (elapsed / steps)
+    # what the timed path computed in its last step, as its caller receives it: the film (K progressive frames from a reset film;
+    # with N > 1 the frame assembled on rank 0) or, with SVGF, the filtered frame
+    is_full = cfg.get("full", False)
+    final_img = None
+    if rank == 0 and not svgf and (is_full or cfg.get("dump") or cfg.get("dump_outputs")):
+        final_img = full[0].cpu().numpy() if use_dist else r.download_film()
+    if rank == 0 and cfg.get("dump_outputs"):
+        write_outputs(cfg["dump_outputs"], {"svgf_output": r.svgf_buffer("output")} if svgf else {"film": final_img})
+    # the film's hash goes into the line, so that the N = 1, 2, 4, 8 records of a scaling run can be held against each other
+    # (the image does not depend on the sharding)
     import hashlib
     film_sha256 = None
-    final_img = None
-    if rank == 0 and not svgf:
-        final_img = full[0].cpu().numpy() if use_dist else r.download_film()
+    if is_full and final_img is not None:
         film_sha256 = hashlib.sha256(np.ascontiguousarray(final_img).tobytes()).hexdigest()
-        if not cfg.get("dump"):
-            final_img = None
+    if final_img is not None and cfg.get("dump"):
+        np.save(cfg["dump"], final_img)
+    final_img = None
+
+    # what the collective layer saw: backend, world, and the device every rank drove (PCI bus id: distinct GPUs, not one GPU
+    # N times) -- gathered while all ranks are still in step
+    def gather_dist_info():
+        if not use_dist:
+            return None
+        p = torch.cuda.get_device_properties(local_rank)
+        mine = {"rank": rank, "local_rank": local_rank, "device_index": torch.cuda.current_device(), "name": p.name,
+                "pci_bus_id": ("%04x:%02x:%02x" % (getattr(p, "pci_domain_id", 0), p.pci_bus_id, getattr(p, "pci_device_id", 0))) if hasattr(p, "pci_bus_id") else None,
+                "uuid": str(getattr(p, "uuid", "")) or None, "tile_slots": int(r.tile_slots())}
+        devices = [None] * world
+        dist.all_gather_object(devices, mine)
+        info = {"backend": dist.get_backend(), "world": dist.get_world_size(), "devices": devices,
+                "distinct_devices": len(set((d["pci_bus_id"], d["uuid"]) for d in devices))}
+        if info["backend"] == "nccl" and info["distinct_devices"] != world:
+            # one rank per GPU is the contract: RCCL ranks sharing a device would make every number below meaningless
+            raise SystemExit("bench.py: %d ranks drive %d distinct GPUs (%s)" % (world, info["distinct_devices"], devices))
+        return info
+
+    metric = ("Mrays/sec (W*H*spp/1e6/s, reference definition), Sponza 1080p 1spp 5-bounce" if (scene == "sponza" and (W, H, spp, depth) == (1920, 1080, 1, 5) and not svgf)
+              else "Mrays/sec (W*H*spp/1e6/s, reference definition)")
+    config = {"workload": workload, "width": W, "height": H, "spp": spp, "max_depth": depth, "rr_depth": rr,
+              "sharding": "8x8 screen tiles, tile %% %d, RCCL all_gather of tile buffers" % world if world > 1 else "none",
+              "frames_in_flight": in_flight, "shade_math": cfg.get("shade_math", "strict"),
+              "regeneration": {"enabled_in_timed_region": True, "burst_frames": regen_timed} if regen_timed else None,
+              "triangles": int(len(fs.arrays["triangles"])), "bvh_nodes": int(sum(len(n) for n in fs.arrays["bvh_lists"])),
+              "anyhit_twins": n_twins, "planar_area_lights": n_planar}
+    if not is_full:
+        # a plain run: the headline figure of the K timed steps and nothing else (--full measures and checks the rest)
+        dist_info = gather_dist_info()
+        out = None
+        if rank == 0:
+            out = {"metric": metric, "value": round(mrays, 3), "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+                   "ms_per_step": round(ms_per_step, 4), "repeats": repeats, "ms_per_step_repeats": [round(1e3 * t / steps, 4) for t in region_s],
+                   "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                   "dist": dist_info, "config": config}
+        r.close()
+        return out
 
     # Path regeneration (atn_set_regeneration / atn_render_burst) beside the serial loop: the same K frames from
     # a reset film as bursts of `regen_burst` frames in one pool of path slots, same frames in flight.  OFF in the timed region above
@@ -397,9 +474,6 @@ def run_workload(args, cfg, ctx):
     sync_all()
     elapsed_events = time.perf_counter() - t1
     ktimes = r.kernel_times()
-
-    ms_per_step = 1e3 * elapsed / steps
-    mrays = W * H * spp / 1e6 / (elapsed / steps)
 
     # work counters of the same frames (untimed pass) for the roofline model
     r.reset()
@@ -642,24 +716,7 @@ def run_workload(args, cfg, ctx):
             cpu_baseline["value_8_threads"] = round(cw * ch * spp / 1e6 / med8, 4)
             cpu_baseline["frames_8_threads"] = nfr8
 
-    if final_img is not None:
-        np.save(cfg["dump"], final_img)
-
-    # what the collective layer saw: backend, world, and the device every rank drove (PCI bus id: distinct GPUs, not one GPU
-    # N times) -- gathered while all ranks are still in step
-    dist_info = None
-    if use_dist:
-        p = torch.cuda.get_device_properties(local_rank)
-        mine = {"rank": rank, "local_rank": local_rank, "device_index": torch.cuda.current_device(), "name": p.name,
-                "pci_bus_id": ("%04x:%02x:%02x" % (getattr(p, "pci_domain_id", 0), p.pci_bus_id, getattr(p, "pci_device_id", 0))) if hasattr(p, "pci_bus_id") else None,
-                "uuid": str(getattr(p, "uuid", "")) or None, "tile_slots": int(r.tile_slots())}
-        devices = [None] * world
-        dist.all_gather_object(devices, mine)
-        dist_info = {"backend": dist.get_backend(), "world": dist.get_world_size(), "devices": devices,
-                     "distinct_devices": len(set((d["pci_bus_id"], d["uuid"]) for d in devices))}
-        if dist_info["backend"] == "nccl" and dist_info["distinct_devices"] != world:
-            # one rank per GPU is the contract: RCCL ranks sharing a device would make every number below meaningless
-            raise SystemExit("bench.py: %d ranks drive %d distinct GPUs (%s)" % (world, dist_info["distinct_devices"], devices))
+    dist_info = gather_dist_info()
 
     # --verify-film: rank 0 renders the same K frames UNSHARDED once more and compares the film with the one the N ranks
     # assembled (byte for byte; the other ranks go on to the closing barrier)
@@ -676,8 +733,7 @@ def run_workload(args, cfg, ctx):
     out = None
     if rank == 0:
         out = {
-            "metric": "Mrays/sec (W*H*spp/1e6/s, reference definition), Sponza 1080p 1spp 5-bounce" if (scene == "sponza" and (W, H, spp, depth) == (1920, 1080, 1, 5) and not svgf)
-            else "Mrays/sec (W*H*spp/1e6/s, reference definition)",
+            "metric": metric,
             "value": round(mrays, 3), "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
             "ms_per_step": round(ms_per_step, 4),
             "repeats": repeats, "spread": round(max(region_s) / min(region_s), 4),
@@ -692,12 +748,7 @@ def run_workload(args, cfg, ctx):
             "host_enqueue_ms_per_step": round(host_enqueue_ms, 4),
             "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload, "width": W, "height": H, "spp": spp, "max_depth": depth, "rr_depth": rr,
-                       "sharding": "8x8 screen tiles, tile %% %d, RCCL all_gather of tile buffers" % world if world > 1 else "none",
-                       "frames_in_flight": in_flight, "shade_math": cfg.get("shade_math", "strict"),
-                       "regeneration": ({"enabled_in_timed_region": True, "burst_frames": regen_timed} if regen_timed else regen_info),
-                       "triangles": int(len(fs.arrays["triangles"])), "bvh_nodes": int(sum(len(n) for n in fs.arrays["bvh_lists"])),
-                       "anyhit_twins": n_twins, "planar_area_lights": n_planar},
+            "config": dict(config, regeneration=config["regeneration"] or regen_info),
             "ray_segments_per_frame": round(ray_segments), "Mray_segments_per_s": round(ray_segments / 1e6 / (elapsed / steps), 2),
             "work_per_frame": {k: round(v) for k, v in per_frame.items()},
             "kernel_ms_per_frame": kernel_ms_per_frame,
@@ -728,13 +779,22 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=1)
     ap.add_argument("--depth", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline figure: repeated timed regions (median), frame latency, "
+                         "per-kernel times, roofline, path regeneration beside the serial loop, CPU baseline, film hash, the unsharded "
+                         "re-render with N > 1, and on the default workload the companion and the two other trees; a plain run times "
+                         "the K steps once and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the timed path computed in its last step as DIR/<name>.npy (float32): "
+                         "film.npy, the accumulated film [H, W, 4] (svgf_output.npy with --svgf); an output over the 64 MB budget "
+                         "is a fixed, seeded sample of its pixels, with their indices in <name>_index.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=0.0, help="seconds of CPU-baseline sampling (default 16, + 8 for the 8-thread sample; below 12 the 8-thread sample is skipped)")
     ap.add_argument("--no-companion", action="store_true",
-                    help="the default run (Sponza stand-in, 1 GPU) also times the 250 K-triangle procedural atrium at the same 1080p 1 spp "
+                    help="with --full the default run (Sponza stand-in, 1 GPU) also times the 250 K-triangle procedural atrium at the same 1080p 1 spp "
                          "5-bounce protocol and reports it under `companion` (SURVEY 8(d): the stand-in AND a synthetic scale-up); this skips it")
     ap.add_argument("--no-own-tree", action="store_true",
-                    help="the default run also times the headline frames through the tree of the repo's own BVH builder (`own_tree`); this skips it")
+                    help="with --full the default run also times the headline frames through the tree of the repo's own BVH builder (`own_tree`); this skips it")
     ap.add_argument("--experiment", default="", help="traffic experiments on the sponza scene, not a benchmark configuration: "
                     "'notex' (no textures), 'noibl' (white background instead of the environment map), 'notex,noibl'")
     ap.add_argument("--dump", default=None, help="write the final frame (npy) here")
@@ -746,7 +806,7 @@ def main():
                          "the line says so in config.shade_math")
     ap.add_argument("--regen", type=int, default=0,
                     help="K > 0: the timed steps are path-regenerated bursts of K progressive frames (atn_render_burst; --steps a multiple of K, one GPU); "
-                         "default 0: the serial loop is timed and an 8-frame regenerated burst is measured beside it (config.regeneration)")
+                         "default 0: the serial loop is timed (and with --full an 8-frame regenerated burst is measured beside it, config.regeneration)")
     ap.add_argument("--mgpu", action="store_true",
                     help="one process, every GPU behind the C-ABI (atn_mgpu_*: worker thread per GPU, peer-copy gather into "
                          "GPU 0) instead of one process per GPU + RCCL all_gather")
@@ -754,16 +814,22 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the one-rank-per-GPU mode; nccl (= RCCL) is what is measured, gloo lets "
                          "several ranks SHARE a GPU (RCCL refuses that), which is how the tests run a world of two on a 1-GPU box")
-    ap.add_argument("--repeats", type=int, default=5, help="the K-step timed region is measured (at least) this many times; value = the median")
-    ap.add_argument("--min-timed-seconds", type=float, default=2.0,
-                    help="repeat the K-step region until the regions add up to this much time (0 = exactly --repeats); at most 64 repeats")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K-step timed region is measured (at least) this many times; value = the median (default 1, 5 with --full)")
+    ap.add_argument("--min-timed-seconds", type=float, default=None,
+                    help="repeat the K-step region until the regions add up to this much time (0 = exactly --repeats); at most 64 repeats "
+                         "(default 0, 2 with --full)")
     ap.add_argument("--verify-film", action="store_true",
-                    help="after the timed region rank 0 renders the same K frames unsharded and reports film_equals_single_gpu "
+                    help="with --full: after the timed region rank 0 renders the same K frames unsharded and reports film_equals_single_gpu "
                          "(on by default with more than one rank)")
     ap.add_argument("--no-verify-film", action="store_true", help="skip that check with more than one rank")
     ap.add_argument("--force-gather", action="store_true",
                     help="run the RCCL tile gather even with one rank (exercises the N>1 step on a 1-GPU box)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.min_timed_seconds is None:
+        args.min_timed_seconds = 2.0 if args.full else 0.0
     if args.config == "c2":
         args.scene = "cornell"
     elif args.config == "c4":
@@ -807,9 +873,9 @@ def main():
     ctx = {"torch": torch, "dist": dist, "rank": rank, "local_rank": local_rank, "world": world, "use_dist": use_dist}
     cfg = {"scene": args.scene, "width": args.width, "height": args.height, "spp": args.spp, "depth": args.depth, "svgf": args.svgf,
            "all_samples": args.all_samples, "frames_in_flight": args.frames_in_flight, "experiment": args.experiment,
-           "cpu_baseline": not args.no_cpu_baseline, "dump": args.dump, "regen_timed": args.regen, "shade_math": args.shade_math,
+           "cpu_baseline": not args.no_cpu_baseline, "dump": args.dump, "dump_outputs": args.dump_outputs, "full": args.full, "regen_timed": args.regen, "shade_math": args.shade_math,
            **({"cpu_budget_s": args.cpu_budget, "cpu_8_threads": args.cpu_budget >= 12} if args.cpu_budget > 0 else {}),
-           "verify_film": args.verify_film or (world > 1 and not args.no_verify_film)}
+           "verify_film": args.full and (args.verify_film or (world > 1 and not args.no_verify_film))}
     out = run_workload(args, cfg, ctx)
 
     # "sponza_lod for oracle-checked runs AND a synthetic scale-up for perf -- say which one every time".  The
@@ -817,8 +883,8 @@ def main():
     # an XCD's L2 and has real L2 / HBM traffic.  Same protocol, own roofline and CPU baseline, under `companion`.
     default_line = (args.scene == "sponza" and (args.width, args.height, args.spp, args.depth) == (1920, 1080, 1, 5) and not args.svgf
                     and not args.experiment and world == 1 and not use_dist)
-    if default_line and not args.no_companion:
-        ccfg = dict(cfg, scene="atrium", dump=None, cpu_budget_s=9.0, cpu_8_threads=False)
+    if args.full and default_line and not args.no_companion:
+        ccfg = dict(cfg, scene="atrium", dump=None, dump_outputs=None, cpu_budget_s=9.0, cpu_8_threads=False)
         comp = run_workload(args, ccfg, dict(ctx, use_dist=False))
         if rank == 0 and comp is not None:
             keep = ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "ms_per_frame_latency", "config", "ray_segments_per_frame",
@@ -832,13 +898,13 @@ def main():
                                           "ms_per_frame_latency": comp["ms_per_frame_latency"],
                                           "roofline_bound": comp["roofline"]["bound"], "roofline_frac": comp["roofline"]["frac"],
                                           "cpu_baseline_value": (comp["cpu_baseline"] or {}).get("value")}
-    if default_line and not args.no_own_tree:
+    if args.full and default_line and not args.no_own_tree:
         # the same headline frames through (a) the tree of the repo's OWN builder (csrc/host/bvh_builder.cpp) instead of the
         # reference-built sponza_lod.sbvh -- what a caller who ingests the OBJ through atns_* gets -- and (b) the reference-built
         # tree after the builder's post passes (atns_optimize_nodes: same boxes and leaves, re-arranged and re-threaded)
         ref_visits = max(out["work_per_frame"]["closest_nodes"] + out["work_per_frame"]["shadow_nodes"], 1) if rank == 0 else 1
         for key, sc in (("own_tree", "sponza_own_tree"), ("reference_tree_optimized", "sponza_ref_tree_opt")):
-            ocfg = dict(cfg, scene=sc, dump=None, cpu_baseline=False)
+            ocfg = dict(cfg, scene=sc, dump=None, dump_outputs=None, cpu_baseline=False)
             own = run_workload(args, ocfg, dict(ctx, use_dist=False))
             if rank == 0 and own is not None:
                 out[key] = {k: own[k] for k in ("value", "unit", "ms_per_step", "ms_per_frame_latency", "work_per_frame", "kernel_ms_per_frame_isolated", "film_sha256")}
@@ -846,7 +912,7 @@ def main():
                 out[key]["bvh_nodes"] = own["config"]["bvh_nodes"]
                 out["config"][key] = {"value": own["value"], "ms_per_step": own["ms_per_step"],
                                       "node_visits_vs_reference_tree": round((own["work_per_frame"]["closest_nodes"] + own["work_per_frame"]["shadow_nodes"]) / ref_visits, 4)}
-    if rank == 0 and out is not None:
+    if args.full and rank == 0 and out is not None:
         parts = ["%s: %.1f Mrays/s, %.3f ms/frame, roofline %s %s" % (out["config"]["workload"][:40], out["value"], out["ms_per_step"], out["roofline"]["bound"], out["roofline"]["frac"])]
         if "companion" in out:
             c = out["companion"]

@@ -1,6 +1,7 @@
-"""bench.py as the driver runs it, on one GPU: the JSON contract, the companion workload, and -- with --force-gather --
-the N > 1 exchange step (RCCL all_gather_into_tensor of the tile buffers + atn_assemble_tiles_on) with a world of one,
-so that the multi-GPU bench path runs every round even when no 8-GPU node is available."""
+"""bench.py as the driver runs it, on one GPU: the plain line and its outputs, the JSON contract of --full, the companion
+workload, and -- with --force-gather -- the N > 1 exchange step (RCCL all_gather_into_tensor of the tile buffers +
+atn_assemble_tiles_on) with a world of one, so that the multi-GPU bench path runs every round even when no 8-GPU node is
+available."""
 import json
 import os
 import subprocess
@@ -15,12 +16,41 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run_bench(extra, tmp_path, name):
     dump = str(tmp_path / (name + ".npy"))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29571", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--no-companion", "--no-own-tree", "--min-timed-seconds", "0", "--dump", dump] + extra,
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
     return json.loads(lines[-1]), np.load(dump)      # the JSON line is the LAST line of stdout, whatever RCCL printed before
+
+
+@pytest.mark.gpu
+def test_plain_line_times_k_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run (no --full) times exactly --steps steps once and prints the headline line only; --dump-outputs writes the film
+    of the last timed step, the same film --full's --dump writes, and the same inputs give the same outputs from run to run."""
+    env = dict(os.environ)
+    lines, films = [], []
+    for i in range(2):
+        out = tmp_path / ("out%d" % i)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines.append(json.loads([l for l in p.stdout.decode().splitlines() if l.strip()][-1]))
+        assert sorted(os.listdir(out)) == ["film.npy"]
+        films.append(np.load(out / "film.npy"))
+    for d in lines:
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["repeats"] == 1 and len(d["ms_per_step_repeats"]) == 1
+        assert d["ms_per_step"] == d["ms_per_step_repeats"][0] > 0
+        assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] - 1920 * 1080 / 1e6 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+        assert "Sponza 1080p 1spp 5-bounce" in d["metric"] and "sponza_lod" in d["config"]["workload"]
+        for k in ("roofline", "cpu_baseline", "companion", "own_tree", "ms_per_frame_latency", "film_sha256", "summary"):
+            assert k not in d, k
+    assert films[0].dtype == np.float32 and films[0].shape == (1080, 1920, 4)
+    assert (films[0][..., 3] == 3).all()
+    assert films[0].tobytes() == films[1].tobytes()
+    _, film_full = run_bench([], tmp_path, "full")
+    assert film_full.tobytes() == films[0].tobytes()
 
 
 @pytest.mark.gpu
@@ -51,7 +81,7 @@ def test_force_gather_film_equals_plain_film(tmp_path):
 @pytest.mark.gpu
 def test_default_line_carries_roofline_companion_and_cpu_baseline():
     env = dict(os.environ)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1"], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "1"], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     d = json.loads([l for l in p.stdout.decode().splitlines() if l.strip()][-1])
@@ -100,7 +130,7 @@ def test_ranks_sharing_the_gpu_render_the_single_rank_film(tmp_path, world):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(29573 + world), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-backend", "gloo", "--steps", "3",
+           "--master-port", str(29573 + world), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--dist-backend", "gloo", "--steps", "3",
            "--warmup", "1", "--repeats", "2", "--min-timed-seconds", "0", "--dump", dump] + (["--no-cpu-baseline"] if world != 2 else [])
     # (no --verify-film: with more than one rank it is on by default; the world of two also carries the CPU baseline, which
     #  rank 0 measures while the others wait -- the plain `bench.py --gpus N` line of the driver must be complete)

@@ -9,6 +9,7 @@ import pytest
 
 from aten_amd import layout as L
 from aten_amd.scene.builder import SceneBuilder
+from conftest import GOLDEN
 
 OBJ = """# every ObjLoader rule in one file
 mtllib t.mtl
@@ -215,8 +216,7 @@ def test_material_xml(tmp_path):
         native_obj.load_material_xml(str(tmp_path / "noroot.xml"))
     with pytest.raises(IOError):
         native_obj.load_material_xml(str(tmp_path / "missing.xml"))
-    ref = "/root/reference/asset/converted_unitychan/unitychan_mtrl.xml"
-    if os.path.exists(ref):                                             # the one XML the reference ships (build container only)
-        mats = native_obj.load_material_xml(ref)
-        assert len(mats) == 9 and mats[0][0] == "face" and mats[0][1] == "diffuse"
-        assert all(k in (0, 1, 2) for m in mats for _, k, _, _ in m[2])
+    # the one XML the reference ships (asset/converted_unitychan/unitychan_mtrl.xml), kept as a fixture
+    mats = native_obj.load_material_xml(os.path.join(GOLDEN, "unitychan_mtrl.xml"))
+    assert len(mats) == 9 and mats[0][0] == "face" and mats[0][1] == "diffuse"
+    assert all(k in (0, 1, 2) for m in mats for _, k, _, _ in m[2])

@@ -7,14 +7,14 @@ for name in "$@"; do
   so=$PWD/aten_amd/_variants/libaten_amd_$name.so
   [ -f "$so" ] || { echo "$name: no library"; continue; }
   for scene in $SCENES; do
-    ATEN_AMD_LIB=$so timeout 300 python bench.py --scene $scene --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    ATEN_AMD_LIB=$so timeout 300 python bench.py --full --scene $scene --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_frame_isolated']
 print('%-24s %-8s %8.3f ms/frame  isolated: fused %.3f shade %.3f' % ('$name','$scene',d['ms_per_step'],k['trace_fused'],k['shade']))"
     if [ "${PMC:-0}" = "1" ]; then
       for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" "TCP_TOTAL_ACCESSES_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum GRBM_GUI_ACTIVE" "SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM_RD GRBM_GUI_ACTIVE"; do
         tag=$(echo $set | cut -c1-6 | tr -d ' ')
-        (cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" && rm -rf /tmp/pmc_${name}_$tag && ATEN_AMD_LIB=$so timeout 300 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc_${name}_$tag -o pmc -- python bench.py --scene $scene --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1)
+        (export TMPDIR=/tmp && rm -rf /tmp/pmc_${name}_$tag && ATEN_AMD_LIB=$so timeout 300 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc_${name}_$tag -o pmc -- python bench.py --full --scene $scene --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1)
       done
       python - <<PY
 import csv,glob,collections

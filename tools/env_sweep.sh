@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 run() {  # label, env...
   label=$1; shift
   for cfg in "--scene sponza --no-companion" "--scene atrium" "--config c2"; do
-    env "$@" timeout 300 python bench.py $cfg --steps 100 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    env "$@" timeout 300 python bench.py --full $cfg --steps 100 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_frame_isolated']
 print('%-28s %-32s %8.3f ms/frame (spread %.3f) latency %.3f  isolated: %s' % ('$label','$cfg',d['ms_per_step'],d.get('spread',0),d.get('ms_per_frame_latency',0),' '.join('%s %.3f'%(n,v) for n,v in k.items() if n in ('trace_closest','shade','trace_fused'))))"

@@ -2,7 +2,7 @@
 # Instruction-cache counters per kernel (counters only: rocprofv3 --pmc, dispatches serialised).  usage: tools/icache_exp.sh [bench args]
 cd "$GRAFT_REPO_ROOT"
 OUT=/tmp/icache_pmc; rm -rf $OUT
-(cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" && timeout 600 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $OUT -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-companion "$@" > /tmp/icache.log 2>&1)
+(export TMPDIR=/tmp && timeout 600 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $OUT -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-companion "$@" > /tmp/icache.log 2>&1)
 python - <<PY
 import csv,glob,collections
 acc=collections.defaultdict(lambda: collections.defaultdict(list))

@@ -18,6 +18,6 @@ SETS[6]="FETCH_SIZE"
 SETS[7]="WRITE_SIZE"
 for i in $PASSES; do
   PMC=${SETS[$i]}
-  timeout 300 rocprofv3 --pmc $PMC --output-format csv -d "$OUT/pass$i" -o pmc -- python bench.py $ARGS > "$OUT/pass$i.log" 2>&1
+  timeout 300 rocprofv3 --pmc $PMC --output-format csv -d "$OUT/pass$i" -o pmc -- python bench.py --full $ARGS > "$OUT/pass$i.log" 2>&1
   echo "pass $i rc=$? : $PMC"
 done

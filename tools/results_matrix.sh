@@ -9,17 +9,17 @@
 set -u
 TAG=${1:?tag}; ONLY=${2:-.}
 cd "$GRAFT_REPO_ROOT"
-OUT=gpurun_out/${TAG}_matrix
+OUT=${RESULTS_DIR:-results}/${TAG}_matrix
 mkdir -p "$OUT" profiles
 cell() {    # name  workload-tag  bench-args...
   local NAME=$1 WL=$2; shift 2
   echo "$NAME" | grep -Eq "$ONLY" || return 0
   bash tools/pmc_collect.sh "$OUT/$NAME/pmc" "1 2 3 4 5 6 7" "$@" --no-companion --no-own-tree > "$OUT/$NAME.pmc.log" 2>&1
   python tools/pmc_to_json.py "$OUT/$NAME/pmc" "$WL" > "profiles/${TAG}_counters_matrix_${NAME}.json"
-  cp "profiles/${TAG}_counters_matrix_${NAME}.json" "$OUT/"      # (gpurun brings back gpurun_out/ only: copy from there into profiles/)
+  cp "profiles/${TAG}_counters_matrix_${NAME}.json" "$OUT/"      # (a copy beside the cell's other outputs)
   rm -rf "$OUT/$NAME/pmc"
   [ "${MATRIX_PMC_ONLY:-0}" = "1" ] && return 0
-  timeout 900 python bench.py "$@" --no-companion --no-own-tree --cpu-budget 8 --repeats 3 --min-timed-seconds 1 > "$OUT/$NAME.json" 2> "$OUT/$NAME.err"
+  timeout 900 python bench.py --full "$@" --no-companion --no-own-tree --cpu-budget 8 --repeats 3 --min-timed-seconds 1 > "$OUT/$NAME.json" 2> "$OUT/$NAME.err"
   python - <<PY
 import json
 try:

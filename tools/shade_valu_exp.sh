@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"
 for ex in "" notex noibl "notex,noibl"; do
   OUT=/tmp/shade_pmc; rm -rf $OUT
-  (cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" && timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VALU_TRANS_F32 SQ_WAVES SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-companion ${ex:+--experiment $ex} > /tmp/shade_pmc.log 2>&1)
+  (export TMPDIR=/tmp && timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VALU_TRANS_F32 SQ_WAVES SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-companion ${ex:+--experiment $ex} > /tmp/shade_pmc.log 2>&1)
   python - <<PY
 import csv,glob,collections
 acc=collections.defaultdict(lambda: collections.defaultdict(list))

@@ -17,8 +17,7 @@
 
 #include "../../include/aten_amd.h"
 #include "device/kernels.hpp"
-#include "device/regen_launch.hpp"
-#include "device/relaxed_launch.hpp"
+#include "device/launch.hpp"
 #include "device/svgf.hpp"
 #include "device/lbvh.hpp"
 #include "host/scene_upload.hpp"
@@ -111,9 +110,8 @@ public:
     int env_anyhit_twin_dirs = 8;   // ATEN_AMD_ANYHIT_TWIN_DIRS: 8 = one twin per direction octant (default), 1 = the one direction-free twin
     bool opt_node_layout = true, opt_planar_lights = true;      // ATEN_AMD_NODE_LAYOUT / ATEN_AMD_PLANAR_LIGHTS at creation; atn_set_upload_options
     bool env_atrous4 = true;    // SVGF a-trous levels with four pixels per thread (k_svgf_atrous4); ATEN_AMD_SVGF_ATROUS4=0: one pixel per thread
-    uint32_t env_trace_blocks = 0;
-    int env_shade_waves = 0;    // ATEN_AMD_SHADE_WAVES=4|5 forces the k_shade_wn flavour (default: 5 when frames are in flight, else 4)
-    int env_shade_items = 0, env_flavour = -1;
+    int env_shade_waves = 0;    // ATEN_AMD_SHADE_WAVES=4|5 forces the k_shade_wn flavour (default: plan_pass)
+    int env_flavour = -1;       // ATEN_AMD_TRACE: 1 = the refill walk, 0 = the plain walk for every launch (default: refill_walk)
 
     // scene (HBM-resident after UpdateSceneData)
     DevBuf<float4> nodes, vtx_pos, vtx_nml, matrices, texels, carpaint, shade_tris;
@@ -599,10 +597,10 @@ public:
         if (upd == stream) bank_epoch = scene_epoch;       // this bank's stream is already behind the update
         return ATN_OK;
     }
-    // a frame's last read of the scene is behind it on its stream
+    // with frames in flight: this bank's frame has read the scene for the last time (its ev_gather, and the scene set's ev_read)
     int record_scene_read()
     {
-        if (frames_in_flight <= 1) return ATN_OK;
+        ATN_HIP(hipEventRecord(ev_gather, stream));
         hipEvent_t& e = ev_read[bank_scene_set];
         if (!e) ATN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ATN_HIP(hipEventRecord(e, stream));
@@ -650,9 +648,7 @@ public:
         // read once here, never inside a frame
         if (const char* e = std::getenv("ATEN_AMD_FUSE")) fuse_traces = e[0] != '0';
         if (const char* e = std::getenv("ATEN_AMD_SVGF_ATROUS4")) env_atrous4 = e[0] != '0';     // 0: the one-pixel-per-thread a-trous kernel
-        if (const char* e = std::getenv("ATEN_AMD_TRACE_BLOCKS")) env_trace_blocks = (uint32_t)std::atoi(e);
-        if (const char* e = std::getenv("ATEN_AMD_SHADE_WAVES")) { const int v = std::atoi(e); if (v == 4 || v == 5) env_shade_waves = v; }   // else: by frames in flight
-        if (const char* e = std::getenv("ATEN_AMD_SHADE_ITEMS")) { const int v = std::atoi(e); if (v >= 1 && v <= kChunkItems) env_shade_items = v; }
+        if (const char* e = std::getenv("ATEN_AMD_SHADE_WAVES")) { const int v = std::atoi(e); if (v == 4 || v == 5) env_shade_waves = v; }   // else: plan_pass
         if (const char* e = std::getenv("ATEN_AMD_LDS_NODES")) env_lds_nodes = std::atoi(e) != 0;
         if (const char* e = std::getenv("ATEN_AMD_ANYHIT_TWIN")) env_anyhit_twin = std::max(0, std::min(2, std::atoi(e)));
         if (const char* e = std::getenv("ATEN_AMD_ANYHIT_TWIN_DIRS")) env_anyhit_twin_dirs = std::atoi(e) == 1 ? 1 : 8;
@@ -660,7 +656,6 @@ public:
         if (const char* e = std::getenv("ATEN_AMD_PLANAR_LIGHTS")) opt_planar_lights = std::atoi(e) != 0; // 0: shadow rays towards area lights always walk to their closest hit
         if (const char* e = std::getenv("ATEN_AMD_PROBE_STREAMS")) env_probe_streams = std::atoi(e) != 0;
         if (const char* e = std::getenv("ATEN_AMD_TRACE")) { env_flavour = e[0] == 'r' ? 1 : 0; }   // 'r'efill / 's'imple
-        if (const char* e = std::getenv("ATEN_AMD_SIMPLE_BLOCK")) { const int v = std::atoi(e); if (v == 64 || v == 128 || v == 256) simple_block = (uint32_t)v; }
         if (const char* e = std::getenv("ATEN_AMD_BATCHES")) {
             n_batches = std::atoi(e);
             batches_forced = true;
@@ -769,9 +764,6 @@ public:
         n_host_matrices = s->n_matrices;
         host_matrices.assign(s->matrices, s->matrices + s->n_matrices);     // (update_tlas without matrices still recognises identity instances)
         tree_is_deep = img.n_nodes >= kRefillMinNodes;
-        use_refill = tree_is_deep;
-        flavour_forced = false;
-        if (env_flavour >= 0) { use_refill = env_flavour == 1; flavour_forced = true; }
         return ATN_OK;
     }
 
@@ -896,7 +888,6 @@ public:
         if (n_mtxs) scene.mtx_quads = (uint32_t)mv.size();
         point_scene_at_current_set();
         tree_is_deep = n_bottom_nodes + n_top >= kRefillMinNodes;
-        if (!flavour_forced) use_refill = tree_is_deep;
         return ATN_OK;
     }
 
@@ -1192,8 +1183,7 @@ public:
     // Since the trace launches are fused (r01-g) the refill walk only pays when a launch carries >= ~1.5 M paths as
     // well: on the 2-, 4- and 8-way shards of the 1080p frame the plain walk is 12-16 % faster (3.28 / 2.10 / 1.48 ms
     // against 3.71 / 2.39 / 1.77), so the flavour is picked per frame from tree size AND frame size.
-    bool use_refill = false, tree_is_deep = false, flavour_forced = false;
-    uint32_t simple_block = 64;     // threads per block of the plain walk's fused launches: one wave per block retires on its own (1-2 % over 256)
+    bool tree_is_deep = false;
     static constexpr size_t kRefillMinNodes = 2048;
     // Re-measured after the burst walk (r02_e, sponza_lod, 3 frames in flight, ms per frame of an N-way shard: refill 4.29 /
     // 2.31 / 1.29 / 0.71 vs plain 5.51 / 2.93 / 1.39 / 0.75 at 2.07 M / 1.04 M / 0.52 M / 0.26 M paths): the r01 crossover of
@@ -1205,6 +1195,12 @@ public:
     // walks tie on the 4-way shard (sponza_lod 1.075 / 1.076 ms, atrium 1.667 refill / 1.704 plain), the plain walk keeps the 8-way shard
     // (0.606 vs 0.627, atrium 1.036 vs 1.075): 800 K -> 400 K paths
     static constexpr uint32_t kRefillMinPaths = 400u * 1000u;
+    // the walk of a frame's passes (frame) or of the traversal probe (the tree alone); ATEN_AMD_TRACE forces one for every launch
+    bool refill_walk(bool frame) const
+    {
+        if (env_flavour >= 0) return env_flavour == 1;
+        return tree_is_deep && (!frame || n_slots >= kRefillMinPaths);
+    }
 
     // bytes of the LDS copy a small scene is walked from (node image + matrix rows), 0 = the scene is walked from global memory
     uint32_t lds_scene_bytes() const
@@ -1213,9 +1209,9 @@ public:
         return (env_lds_nodes && b <= kLdsNodesMaxBytes) ? (uint32_t)b : 0u;
     }
 
-    uint32_t trace_grid(uint32_t n_jobs) const
+    uint32_t trace_grid(uint32_t n_jobs, bool refill) const
     {
-        if (use_refill) {
+        if (refill) {
             // persistent waves pulling kFetchChunk-job chunks: about as many waves as fit on the chip
             const uint32_t waves_per_block = (uint32_t)kTraceBlock / 64u;
             uint32_t blocks = ((n_jobs + atn::kFetchChunk - 1u) / atn::kFetchChunk + waves_per_block - 1u) / waves_per_block;
@@ -1225,62 +1221,65 @@ public:
             // room beside this launch: 4.5 waves per SIMD's worth is slower alone (3.35 ms) and faster in the pipeline (r04 sweep,
             // profiles/r04_sweep_trace_grid.txt: sponza_lod 4.13 -> 4.04 ms per frame, atrium 5.84 -> 5.71 with 4 frames in flight;
             // 768 .. 1280 blocks within 1 %).
-            const uint32_t cap = env_trace_blocks ? env_trace_blocks
-                               : ((frames_in_flight > 1 ? 256u * 18u : 256u * 32u) / waves_per_block);
+            const uint32_t cap = (frames_in_flight > 1 ? 256u * 18u : 256u * 32u) / waves_per_block;
             return blocks < cap ? blocks : cap;
         }
         return grid_for(n_jobs);
     }
 
-    // the persistent kernels run kTraceBlock threads per block
-    template <bool SHADOW>
-    void launch_trace(const PathBuffers& pb, uint32_t grid, bool count, int32_t b, hipStream_t stream)
+    // What a pass over n paths launches (device/launch.hpp: PassPlan).  The frame's walk, the LDS copy and the shade flavour are
+    // properties of the context; the grids and chunk sizes follow n.
+    PassPlan plan_pass(PassKind kind, uint32_t n) const
     {
-        const dim3 g(grid), t(use_refill ? (uint32_t)kTraceBlock : 256u);
-        const uint32_t lds = 0u;
-        if (SHADOW) {
-            if (count) { if (use_refill) hipLaunchKernelGGL((k_trace_shadow<true, true>), g, t, lds, stream, pb, scene, b); else hipLaunchKernelGGL((k_trace_shadow<true, false>), g, t, lds, stream, pb, scene, b); }
-            else { if (use_refill) hipLaunchKernelGGL((k_trace_shadow<false, true>), g, t, lds, stream, pb, scene, b); else hipLaunchKernelGGL((k_trace_shadow<false, false>), g, t, lds, stream, pb, scene, b); }
-        }
-        else {
-            if (count) { if (use_refill) hipLaunchKernelGGL((k_trace_closest<true, true>), g, t, lds, stream, pb, scene, b); else hipLaunchKernelGGL((k_trace_closest<true, false>), g, t, lds, stream, pb, scene, b); }
-            else { if (use_refill) hipLaunchKernelGGL((k_trace_closest<false, true>), g, t, lds, stream, pb, scene, b); else hipLaunchKernelGGL((k_trace_closest<false, false>), g, t, lds, stream, pb, scene, b); }
-        }
+        PassPlan p{};
+        p.kind = kind;
+        p.refill = refill_walk(true);
+        p.lds_bytes = lds_scene_bytes();
+        // threads per block of the plain walk's fused launches: one wave per block retires on its own (1-2 % over 256); a node image
+        // of a few KB is walked from an LDS copy (trace_simple<., ., true>), above 8 KB per copy the blocks get four waves to share it
+        p.block = p.lds_bytes > 8192u ? 256u : 64u;
+        p.trace_grid = trace_grid(n, p.refill);
+        p.fused_grid = trace_grid(2u * n, p.refill);
+        // k_shade works on chunks of `items` x 256 queue entries per block (one queue atomic per chunk): 4 on full
+        // frames; below ~0.4 M paths a launch has too few such blocks to fill 256 CUs (measured on the 8-way
+        // shard: 2 -> 1.38 ms, 4 -> 1.46 ms, 1 -> 1.41 ms per frame)
+        p.shade_items = n >= 400u * 1000u ? kChunkItems : 2;
+        p.shade_grid = grid_for((n + (uint32_t)p.shade_items - 1u) / (uint32_t)p.shade_items);
+        // 5 waves per SIMD (96 registers, a few spilled) pays where shade shares the SIMDs with another frame's trace waves AND the launch is
+        // large enough not to be latency-bound itself: the Disney / analytic sets on every shard size measured, the core set on full frames
+        // only (profiles/r04_variants_shade_waves.txt, r04_shard_matrix.txt).  The SVGF flavour -- AOV writes, 25 registers spilled at 96 --
+        // stays at 4 (C5 4.66 vs 4.68 ms per frame), and so does the regenerated shade kernel, which needs all 128 registers of the 4-wave
+        // budget (held to 96 for 5 waves it spills 21-44 of them).
+        const bool big = n >= 1500u * 1000u;
+        p.shade_waves = env_shade_waves ? env_shade_waves
+                      : (kind == PassKind::Serial && frames_in_flight > 1 && (scene.material_set != kMsCore || big) ? 5 : 4);
+        return p;
+    }
+
+    // the unfused trace launches (ATEN_AMD_FUSE=0, and counted frames: the fused kernel does not count); the persistent kernels run
+    // kTraceBlock threads per block
+    template <bool SHADOW>
+    void launch_trace(const PassPlan& p, const PathBuffers& pb, bool count, int32_t b, hipStream_t st)
+    {
+        const dim3 g(p.trace_grid), t(p.refill ? (uint32_t)kTraceBlock : 256u);
+        with_flags([&](auto c, auto refill) {
+            if constexpr (SHADOW) hipLaunchKernelGGL((k_trace_shadow<decltype(c)::value, decltype(refill)::value>), g, t, 0, st, pb, scene, b);
+            else hipLaunchKernelGGL((k_trace_closest<decltype(c)::value, decltype(refill)::value>), g, t, 0, st, pb, scene, b);
+        }, count, p.refill);
     }
 
     template <bool SVGF>
-    void launch_shade(uint32_t g_shade, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, int32_t b, const SvgfShade& sv)
+    void launch_shade(const PassPlan& p, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, int32_t b, const SvgfShade& sv)
     {
-        const dim3 g(g_shade), t(256);
-        // 5 waves per SIMD (96 registers, a few spilled) pays where shade shares the SIMDs with another frame's trace waves AND the launch is
-        // large enough not to be latency-bound itself: the Disney / analytic sets on every shard size measured, the core set on full frames
-        // only (profiles/r04_variants_shade_waves.txt, r04_shard_matrix.txt)
-        const bool big = (uint32_t)(fp.slot_end - fp.slot_begin) >= 1500u * 1000u;
-        // (the SVGF flavour -- AOV writes, 25 registers spilled at 96 -- stays at 4: C5 4.66 vs 4.68 ms per frame)
-        const int shade_waves = env_shade_waves ? env_shade_waves
-                              : (!SVGF && frames_in_flight > 1 && (scene.material_set != kMsCore || big) ? 5 : 4);
         if (!SVGF && shade_math_relaxed) {      // atn_set_shade_math(1): the same kernel under --use_fast_math rules (shade_relaxed.hip); not the parity path
-            relaxed_launch_shade(scene.material_set, shade_waves, g_shade, st, pb, scene, fp, camera, b);
+            relaxed_launch_shade(scene.material_set, p.shade_waves, p.shade_grid, st, pb, scene, fp, camera, b);
             return;
         }
-        switch (scene.material_set) {       // BSDFs no uploaded material uses are compiled out of the instantiation launched
-        // (small sets: 5 waves per SIMD when frames overlap -- they share the SIMDs with another frame's trace waves --, 4 otherwise:
-        // kernels.hpp, k_shade_wn)
-        case kMsCore:
-            if (shade_waves == 5) hipLaunchKernelGGL((k_shade_wn<SVGF, kMsCore, 5>), g, t, 0, st, pb, scene, fp, camera, b, sv);
-            else hipLaunchKernelGGL((k_shade_wn<SVGF, kMsCore, 4>), g, t, 0, st, pb, scene, fp, camera, b, sv);
-            break;
-        case kMsDisney:
-            if (shade_waves == 5) hipLaunchKernelGGL((k_shade_wn<SVGF, kMsDisney, 5>), g, t, 0, st, pb, scene, fp, camera, b, sv);
-            else hipLaunchKernelGGL((k_shade_wn<SVGF, kMsDisney, 4>), g, t, 0, st, pb, scene, fp, camera, b, sv);
-            break;
-        case kMsAnalytic:
-            if (shade_waves == 5) hipLaunchKernelGGL((k_shade_wn<SVGF, kMsAnalytic, 5>), g, t, 0, st, pb, scene, fp, camera, b, sv);
-            else hipLaunchKernelGGL((k_shade_wn<SVGF, kMsAnalytic, 4>), g, t, 0, st, pb, scene, fp, camera, b, sv);
-            break;
-        case kMsCarPaint: hipLaunchKernelGGL((k_shade<SVGF, kMsCarPaint>), g, t, 0, st, pb, scene, fp, camera, b, sv); break;
-        default: hipLaunchKernelGGL((k_shade<SVGF, kMsToon>), g, t, 0, st, pb, scene, fp, camera, b, sv); break;
-        }
+        with_shade_flavour(scene.material_set, p.shade_waves, [&](auto k) {
+            using K = decltype(k);
+            if constexpr (K::waves == 0) hipLaunchKernelGGL((k_shade<SVGF, K::ms>), dim3(p.shade_grid), dim3(256), 0, st, pb, scene, fp, camera, b, sv);
+            else hipLaunchKernelGGL((k_shade_wn<SVGF, K::ms, K::waves>), dim3(p.shade_grid), dim3(256), 0, st, pb, scene, fp, camera, b, sv);
+        });
     }
 
     void prof_begin(bool on, int kind, hipStream_t st = nullptr)
@@ -1324,7 +1323,6 @@ public:
         // while launches are latency-bound (<= ~1 M paths in flight); on a full 1080p frame the concurrent shade kernel
         // streams path state through the L2 that the walk wants for its nodes and the deep-tree walk loses more than
         // the overlap wins (6.13 vs 6.59 ms), the shallow-tree walk still gains with two batches.
-        if (!flavour_forced) use_refill = tree_is_deep && n_slots >= kRefillMinPaths;
         int nb;
         if (batches_forced) {
             nb = n_batches;
@@ -1336,8 +1334,7 @@ public:
             // (with frames in flight the next frame fills the gaps a second batch was for: measured r02_e on Cornell, 3 in
             // flight, 1.04 M paths: 1 batch 0.82 ms, 2 batches 0.96; 2.07 M paths: 1.66 vs 1.63)
             // (r03, node image in LDS, 3 in flight, Cornell 2.07 M paths: 1 batch 1.52 ms, 2 batches 1.58 -- one batch whenever frames overlap)
-            const bool lds_nodes = lds_scene_bytes() != 0u;
-            nb = use_refill ? 1 : (lds_nodes && frames_in_flight > 1) ? 1 : (n_slots >= (frames_in_flight > 1 ? 1500u : 800u) * 1000u ? 2 : 1);
+            nb = refill_walk(true) ? 1 : (lds_scene_bytes() && frames_in_flight > 1) ? 1 : (n_slots >= (frames_in_flight > 1 ? 1500u : 800u) * 1000u ? 2 : 1);
             if (nb > n_batches) nb = n_batches;
         }
         // the streams a frame's batches run on must not share a hardware queue (see streams_run_side_by_side)
@@ -1355,14 +1352,9 @@ public:
             PathBuffers pb = buffers(count, k, begin);
             fp.slot_begin = (int32_t)begin; fp.slot_end = (int32_t)end;
             const uint32_t n = end - begin;
-            // k_shade works on chunks of `items` x 256 queue entries per block (one queue atomic per chunk): 4 on full
-            // frames; below ~0.4 M paths a launch has too few such blocks to fill 256 CUs (measured on the 8-way
-            // shard: 2 -> 1.38 ms, 4 -> 1.46 ms, 1 -> 1.41 ms per frame)
-            int items = n >= 400u * 1000u ? kChunkItems : 2;
-            if (env_shade_items) items = env_shade_items;
-            fp.chunk_items = items;
-            const uint32_t g_shade = grid_for((n + (uint32_t)items - 1u) / (uint32_t)items);
-            const uint32_t g_slots = grid_for(n), g_trace = trace_grid(n), g_all = (n + 255u) / 256u;
+            const PassPlan plan = plan_pass(SVGF ? PassKind::Svgf : PassKind::Serial, n);
+            fp.chunk_items = plan.shade_items;
+            const uint32_t g_slots = grid_for(n), g_all = (n + 255u) / 256u;
             for (int32_t s = 0; s < d->sample; s++) {
                 fp.sample = s;
                 if (s > 0) ATN_HIP(hipMemsetAsync(pb.q_count, 0, (size_t)4 * counters_depth * 4, st));
@@ -1372,60 +1364,26 @@ public:
                 if (count || !fuse_traces) {
                     for (int32_t b = 0; b < d->maxDepth; b++) {
                         prof_begin(prof, ATN_K_TRACE_CLOSEST, st);
-                        launch_trace<false>(pb, g_trace, count, b, st);
+                        launch_trace<false>(plan, pb, count, b, st);
                         prof_end(prof);
                         prof_begin(prof, ATN_K_SHADE, st);
-                        launch_shade<SVGF>(g_shade, st, pb, fp, b, sv);
+                        launch_shade<SVGF>(plan, st, pb, fp, b, sv);
                         prof_end(prof);
                         prof_begin(prof, ATN_K_TRACE_SHADOW, st);
-                        launch_trace<true>(pb, g_trace, count, b, st);
+                        launch_trace<true>(plan, pb, count, b, st);
                         prof_end(prof);
                     }
                 }
                 else {
                     // depth + 1 trace launches: [closest 0], [shadow b + closest b+1] ..., [shadow depth-1]
-                    const uint32_t g_fused = trace_grid(2u * n);
                     for (int32_t b = 0; b <= d->maxDepth; b++) {
-                        const int32_t bs = b - 1, bc = b < d->maxDepth ? b : -1;
-                        // the first launch holds only primary rays: coherent, they finish together, and the refill bookkeeping buys
-                        // nothing (sponza_lod 4.33 -> 4.30 ms, atrium 4K 221 -> 219 ms)
-                        const bool refill_now = use_refill && b != 0;     // (primary rays, coherent, take the plain walk: DESIGN.md section 7)
-                        // (timed under "trace_closest" when it is a different kernel from the other launches: the roofline of
-                        // k_trace_fused<true, .> is about those)
-                        prof_begin(prof, (use_refill && !refill_now && b == 0) ? ATN_K_TRACE_CLOSEST : ATN_K_TRACE_FUSED, st);
-                        // a node image of a few KB is walked from an LDS copy (trace_simple<., ., true>); above 8 KB per copy the blocks get
-                        // four waves to share it
-                        const bool lds_nodes = lds_scene_bytes() != 0u;
-                        const uint32_t sb = (lds_nodes && lds_scene_bytes() > 8192u) ? 256u : simple_block;
-                        const dim3 gr(refill_now ? g_fused : g_fused * (256u / sb)), tb(refill_now ? (uint32_t)kTraceBlock : sb);
-                        const uint32_t lds = lds_nodes ? lds_scene_bytes() : 0u;
-                        if (lds_nodes && refill_now) {
-                            if (scene.any_alpha) hipLaunchKernelGGL((k_trace_fused<true, true, true>), gr, tb, lds, st, pb, scene, bs, bc, b);
-                            else hipLaunchKernelGGL((k_trace_fused<true, false, true>), gr, tb, lds, st, pb, scene, bs, bc, b);
-                        }
-                        else if (lds_nodes) {
-                            if (scene.any_alpha) hipLaunchKernelGGL((k_trace_fused<false, true, true>), gr, tb, lds, st, pb, scene, bs, bc, b);
-                            else hipLaunchKernelGGL((k_trace_fused<false, false, true>), gr, tb, lds, st, pb, scene, bs, bc, b);
-                        }
-                        else if (refill_now) {
-                            if (scene.any_alpha) hipLaunchKernelGGL((k_trace_fused<true, true>), gr, tb, lds, st, pb, scene, bs, bc, b);
-                            else hipLaunchKernelGGL((k_trace_fused<true, false>), gr, tb, lds, st, pb, scene, bs, bc, b);
-                        }
-                        else if (b == 0) {
-                            // only closest-hit rays (there is no bounce -1 to cast shadows): the closest-hit kernel is the same walk
-                            // without the shadow job's code in it (every ray's stop_t is a constant there; the fused kernel's plain
-                            // flavour grew by the any-hit twins' root selection: primary rays 0.168 -> 0.203 ms per frame, back at
-                            // 0.168 through this launch)
-                            hipLaunchKernelGGL((k_trace_closest<false, false>), gr, tb, lds, st, pb, scene, 0);
-                        }
-                        else {
-                            if (scene.any_alpha) hipLaunchKernelGGL((k_trace_fused<false, true>), gr, tb, lds, st, pb, scene, bs, bc, b);
-                            else hipLaunchKernelGGL((k_trace_fused<false, false>), gr, tb, lds, st, pb, scene, bs, bc, b);
-                        }
+                        const TraceLaunch tl = trace_launch(plan, b);
+                        prof_begin(prof, tl.prof_kind, st);
+                        launch_trace_fused<false>(tl, st, pb, scene, b - 1, b < d->maxDepth ? b : -1, b);
                         prof_end(prof);
                         if (b < d->maxDepth) {
                             prof_begin(prof, ATN_K_SHADE, st);
-                            launch_shade<SVGF>(g_shade, st, pb, fp, b, sv);
+                            launch_shade<SVGF>(plan, st, pb, fp, b, sv);
                             prof_end(prof);
                         }
                     }
@@ -1445,30 +1403,55 @@ public:
         return ATN_OK;
     }
 
-    // ≙ idaten::PathTracing::render + OnRender (src/libidaten/kernel/pathtracing.cpp:49-153), loop
-    // structure of aten::PathTracing::OnRender/radiance (src/libaten/renderer/pathtracing/pathtracing.cpp:22-89,269-366)
-    int render(const atn_destination* d, atn_vec4* out_host)
+    // ---- what every frame does around its passes (render, render_regen, svgf_render) ----
+    int check_ready(const atn_destination* d)
     {
         if (!d) return fail(ATN_ERR_INVALID_ARG, "null destination");
         if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
         if (!has_camera) return fail(ATN_ERR_INVALID_ARG, "atn_update_camera has not been called");
         if (n_seeds == 0) return fail(ATN_ERR_INVALID_ARG, "atn_init_sampler / atn_set_random has not been called");
         if (d->width <= 0 || d->height <= 0 || d->maxDepth <= 0 || d->sample <= 0) return fail(ATN_ERR_INVALID_ARG, "bad destination");
+        return ATN_OK;
+    }
+    // rotate (the bank that has been idle longest becomes the current one), go behind the latest scene update, size the buffers
+    int begin_frame(const atn_destination& d, bool rotate)
+    {
+        if (rotate) swap_bank(spare[frame_seq % (uint64_t)(frames_in_flight - 1)]);
+        frame_seq++;
+        const int rc = wait_scene_epoch();
+        return rc ? rc : ensure_frame(d.width, d.height, d.maxDepth);
+    }
+    // the film is a running mean: its writers go in frame order, each behind the last one (ev_film)
+    int wait_film()
+    {
+        if (film_pending) ATN_HIP(hipStreamWaitEvent(stream, ev_film, 0));
+        return ATN_OK;
+    }
+    int record_film_writer()
+    {
+        if (frames_in_flight <= 1) return ATN_OK;
+        if (!ev_film) ATN_HIP(hipEventCreateWithFlags(&ev_film, hipEventDisableTiming));
+        ATN_HIP(hipEventRecord(ev_film, stream));
+        film_pending = true;
+        return ATN_OK;
+    }
+    int end_film_frame()
+    {
+        const int rc = frames_in_flight > 1 ? record_scene_read() : ATN_OK;
+        return rc ? rc : record_film_writer();
+    }
+
+    // ≙ idaten::PathTracing::render + OnRender (src/libidaten/kernel/pathtracing.cpp:49-153), loop
+    // structure of aten::PathTracing::OnRender/radiance (src/libaten/renderer/pathtracing/pathtracing.cpp:22-89,269-366)
+    int render(const atn_destination* d, atn_vec4* out_host)
+    {
+        int rc = check_ready(d);
+        if (rc) return rc;
         ATN_HIP(hipSetDevice(device));
         if (d->sample > 1 && regen_applies(*d, 1)) return render_regen(d, 1, out_host);
         const bool count = d->count_stats != 0, prof = d->profile != 0;
-        int rc;
-        if (frames_in_flight > 1) {
-            if (count) { rc = quiesce(); if (rc) return rc; }       // the counters are one set, read back synchronously
-            else {
-                // rotate: the bank that has been idle longest becomes the current one
-                swap_bank(spare[frame_seq % (uint64_t)(frames_in_flight - 1)]);
-            }
-        }
-        frame_seq++;
-        rc = wait_scene_epoch();
-        if (rc) return rc;
-        rc = ensure_frame(d->width, d->height, d->maxDepth);
+        if (frames_in_flight > 1 && count) { rc = quiesce(); if (rc) return rc; }      // the counters are one set, read back synchronously
+        rc = begin_frame(*d, frames_in_flight > 1 && !count);
         if (rc) return rc;
         FrameParams fp = frame_params(*d);
         if (count) {
@@ -1485,17 +1468,15 @@ public:
         rc = run_paths<false>(d, fp, count, prof, SvgfShade{}, SvgfFrame{});
         if (rc) return rc;
         fp.slot_begin = 0; fp.slot_end = (int32_t)n_slots;
-        if (film_pending) ATN_HIP(hipStreamWaitEvent(stream, ev_film, 0));     // the film is a running mean: frame order
+        rc = wait_film();
+        if (rc) return rc;
         prof_begin(prof, ATN_K_GATHER);
         if (d->sample == 1) hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
         else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
         prof_end(prof);
         ATN_HIP(hipGetLastError());
-        if (frames_in_flight > 1) {
-            ATN_HIP(hipEventRecord(ev_gather, stream)); rc = record_scene_read(); if (rc) return rc;
-            if (!ev_film) ATN_HIP(hipEventCreateWithFlags(&ev_film, hipEventDisableTiming));
-            ATN_HIP(hipEventRecord(ev_film, stream)); film_pending = true;
-        }
+        rc = end_film_frame();
+        if (rc) return rc;
 
         if (count) {
             hipLaunchKernelGGL(k_cost_to_pixels, dim3(g_all), dim3(256), 0, stream, fp, (const uint32_t*)cost.p, cost_film.p);
@@ -1555,10 +1536,7 @@ public:
         if (!d) return fail(ATN_ERR_INVALID_ARG, "null destination");
         if (n_frames <= 0) return fail(ATN_ERR_INVALID_ARG, "bad burst length");
         if (regen_applies(*d, n_frames)) {
-            if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
-            if (!has_camera) return fail(ATN_ERR_INVALID_ARG, "atn_update_camera has not been called");
-            if (n_seeds == 0) return fail(ATN_ERR_INVALID_ARG, "atn_init_sampler / atn_set_random has not been called");
-            if (d->width <= 0 || d->height <= 0 || d->maxDepth <= 0 || d->sample <= 0) return fail(ATN_ERR_INVALID_ARG, "bad destination");
+            { const int rc = check_ready(d); if (rc) return rc; }
             ATN_HIP(hipSetDevice(device));
             // pieces of at most kRegenStagingBytes of staging planes (1080p: 32 frames; a 4K frame is 133 MB)
             const uint64_t tiles = (uint64_t)((d->width + 7) / 8) * ((d->height + 7) / 8);
@@ -1586,12 +1564,7 @@ public:
     int render_regen(const atn_destination* d, int32_t n_frames, atn_vec4* out_host)
     {
         const bool prof = d->profile != 0;
-        int rc;
-        if (frames_in_flight > 1) swap_bank(spare[frame_seq % (uint64_t)(frames_in_flight - 1)]);
-        frame_seq++;
-        rc = wait_scene_epoch();
-        if (rc) return rc;
-        rc = ensure_frame(d->width, d->height, d->maxDepth);
+        int rc = begin_frame(*d, frames_in_flight > 1);
         if (rc) return rc;
         // Stages: while items are left every slot is busy, so the cursor passes the last item after at most (path-stages of all items) /
         // (slots) <= n_frames * spp * maxDepth stages; the items then in flight need at most spp * maxDepth more.
@@ -1613,66 +1586,50 @@ public:
         pb.fetch_shadow = nullptr;
         const RegenOut ro{ rg_frames.p, film.p, tile_out.p };
 
-        if (!flavour_forced) use_refill = tree_is_deep && n_slots >= kRefillMinPaths;
         const uint32_t n = rg_n_valid;      // the pool: one slot per pixel of the shard (n_frames >= 1: never more slots than items)
-        int items = n >= 400u * 1000u ? kChunkItems : 2;
-        if (env_shade_items) items = env_shade_items;
-        fp.chunk_items = items;
-        const uint32_t g_shade = grid_for((n + (uint32_t)items - 1u) / (uint32_t)items);
-        const uint32_t g_all = (n_slots + 255u) / 256u, g_fused = trace_grid(2u * n);
+        const PassPlan plan = plan_pass(PassKind::Regen, n);
+        fp.chunk_items = plan.shade_items;
+        const uint32_t g_all = (n_slots + 255u) / 256u;
         // the regions a shade launch writes for the compaction in front of the next stage (kernels.hpp, k_regen_compact)
-        const uint32_t chunk_size = 256u * (uint32_t)items, n_chunks = (n + chunk_size - 1u) / chunk_size, n_groups = (n_chunks + kRegenGroup - 1u) / kRegenGroup;
+        const uint32_t chunk_size = 256u * (uint32_t)plan.shade_items, n_chunks = (n + chunk_size - 1u) / chunk_size, n_groups = (n_chunks + kRegenGroup - 1u) / kRegenGroup;
         const size_t region_words = (size_t)n_chunks * chunk_size;
         const size_t rg_words = 2 * region_words + 2 * (size_t)n_chunks + 4 * (size_t)n_groups;
         if (rg_regions.n < rg_words) ATN_HIP(rg_regions.resize(rg_words));
         pb.q_regions = rg_regions.p; pb.sh_regions = rg_regions.p + region_words; pb.region_counts = rg_regions.p + 2 * region_words;
         uint32_t* const group_counts[2] = { pb.region_counts + 2 * (size_t)n_chunks, pb.region_counts + 2 * (size_t)n_chunks + 2 * (size_t)n_groups };
-        const bool big = n >= 1500u * 1000u;
-        const bool small_set = scene.material_set == kMsCore || scene.material_set == kMsDisney || scene.material_set == kMsAnalytic;
-        // (the regenerated shade kernel needs all 128 registers of the 4-wave budget: held to 96 for 5 waves it spills 21-44 of them)
-        const int shade_waves = !small_set ? 0 : env_shade_waves ? env_shade_waves : 4;
-        (void)big;
-        const bool lds_nodes = lds_scene_bytes() != 0u;
-        const uint32_t sb = (lds_nodes && lds_scene_bytes() > 8192u) ? 256u : simple_block;
 
         ATN_HIP(hipMemsetAsync(rg_counters.p, 0, (3 * cstride + 1) * sizeof(uint32_t), stream));
         ATN_HIP(hipMemsetAsync(group_counts[0], 0, 4 * (size_t)n_groups * sizeof(uint32_t), stream));
         prof_begin(prof, ATN_K_GEN);
         pb.group_counts = group_counts[0];
-        regen_launch_begin(g_shade, stream, pb, fp, camera);
+        regen_launch_begin(plan.shade_grid, stream, pb, fp, camera);
         regen_launch_compact(n_chunks, stream, pb, 0, chunk_size, group_counts[1], n_groups);
         prof_end(prof);
         for (int32_t i = 0; i <= stages; i++) {
             // trace(i): the shadow rays shade(i - 1) cast + the closest-hit rays of the paths (continued and regenerated) it queued
-            const bool refill_now = use_refill && i != 0;       // (stage 0 holds primary rays only: coherent, the plain walk)
-            RegenTraceLaunch tl{};
-            tl.refill = refill_now; tl.alpha = scene.any_alpha != 0; tl.lds_nodes = lds_nodes;
-            tl.grid = refill_now ? g_fused : g_fused * (256u / sb); tl.block = refill_now ? (uint32_t)kTraceBlock : sb;
-            tl.lds_bytes = lds_nodes ? lds_scene_bytes() : 0u;
-            prof_begin(prof, (use_refill && i == 0) ? ATN_K_TRACE_CLOSEST : ATN_K_TRACE_FUSED);
+            const TraceLaunch tl = trace_launch(plan, i);
+            prof_begin(prof, tl.prof_kind);
             regen_launch_trace(tl, stream, pb, scene, i - 1, i < stages ? i : -1, i);
             prof_end(prof);
             if (i < stages) {
                 prof_begin(prof, ATN_K_SHADE);
                 pb.group_counts = group_counts[(i + 1) & 1];
-                regen_launch_shade(scene.material_set, shade_waves, g_shade, stream, pb, scene, fp, camera, i, ro);
+                regen_launch_shade(scene.material_set, plan.shade_waves, plan.shade_grid, stream, pb, scene, fp, camera, i, ro);
                 prof_end(prof);
                 prof_begin(prof, ATN_K_ACCUM);      // (timed under the serial loop's per-sample epilogue kind)
                 regen_launch_compact(n_chunks, stream, pb, i + 1, chunk_size, group_counts[i & 1], n_groups);
                 prof_end(prof);
             }
         }
-        if (film_pending) ATN_HIP(hipStreamWaitEvent(stream, ev_film, 0));     // the film is a running mean: burst order
+        rc = wait_film();
+        if (rc) return rc;
         prof_begin(prof, ATN_K_GATHER);
         regen_launch_flush((n + 255u) / 256u, stream, pb, fp, ro);
         regen_launch_end(g_all, stream, pb, fp, ro);
         prof_end(prof);
         ATN_HIP(hipGetLastError());
-        if (frames_in_flight > 1) {
-            ATN_HIP(hipEventRecord(ev_gather, stream)); rc = record_scene_read(); if (rc) return rc;
-            if (!ev_film) ATN_HIP(hipEventCreateWithFlags(&ev_film, hipEventDisableTiming));
-            ATN_HIP(hipEventRecord(ev_film, stream)); film_pending = true;
-        }
+        rc = end_film_frame();
+        if (rc) return rc;
         if (out_host) {
             ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
             ATN_HIP(hipStreamSynchronize(stream));
@@ -1857,11 +1814,8 @@ public:
     // ≙ aten::SVGFRenderer::OnRender (svgf.cpp:452-637)
     int svgf_render(const atn_destination* d, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host, bool path_pass = true)
     {
-        if (!d) return fail(ATN_ERR_INVALID_ARG, "null destination");
-        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
-        if (!has_camera) return fail(ATN_ERR_INVALID_ARG, "atn_update_camera has not been called");
-        if (n_seeds == 0) return fail(ATN_ERR_INVALID_ARG, "atn_init_sampler / atn_set_random has not been called");
-        if (d->width <= 0 || d->height <= 0 || d->maxDepth <= 0 || d->sample <= 0) return fail(ATN_ERR_INVALID_ARG, "bad destination");
+        int rc = check_ready(d);
+        if (rc) return rc;
         if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "SVGF needs the whole frame on one GPU (filter footprints cross tiles)");
         ATN_HIP(hipSetDevice(device));
         // Frames in flight (atn_set_frames_in_flight > 1): the path pass of frame f + 1 runs on the next bank's stream while
@@ -1870,22 +1824,15 @@ public:
         // that consumed that slot two frames ago; the filter passes run on one filter stream, frame after frame, each
         // waiting for its own path pass.
         const bool pipelined = frames_in_flight > 1 && path_pass;
-        int rc;
         if (!pipelined && frames_in_flight > 1) { rc = quiesce(); if (rc) return rc; }
         else if (w_or_h_changed(d->width, d->height)) { rc = quiesce(); if (rc) return rc; }
-        if (pipelined) {
-            if (!sv_stream) {
-                ATN_HIP(hipStreamCreateWithFlags(&sv_stream, hipStreamNonBlocking));
-                for (auto& e : sv_ev_prepare) ATN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            }
-            swap_bank(spare[frame_seq % (uint64_t)(frames_in_flight - 1)]);
+        if (pipelined && !sv_stream) {
+            ATN_HIP(hipStreamCreateWithFlags(&sv_stream, hipStreamNonBlocking));
+            for (auto& e : sv_ev_prepare) ATN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        frame_seq++;
-        rc = wait_scene_epoch();
+        rc = begin_frame(*d, pipelined);
         if (rc) return rc;
         hipStream_t fs = pipelined ? sv_stream : stream;       // the stream the filter passes run on
-        rc = ensure_frame(d->width, d->height, d->maxDepth);
-        if (rc) return rc;
         rc = svgf_ensure(d->width, d->height, stages_host != nullptr);
         if (rc) return rc;
         if (!compute_motion && (!sv_motion_set || sv_motion_count < (size_t)d->width * d->height))
@@ -1922,8 +1869,7 @@ public:
             rc = run_paths<true>(d, fp, false, prof, sv, sf);
             if (rc) return rc;
             if (pipelined) {
-                ATN_HIP(hipEventRecord(ev_gather, stream));         // this bank's "path pass done"
-                rc = record_scene_read();
+                rc = record_scene_read();       // (this bank's "path pass done")
                 if (rc) return rc;
                 ATN_HIP(hipStreamWaitEvent(fs, ev_gather, 0));
             }
@@ -1987,10 +1933,7 @@ public:
             ATN_HIP(hipSetDevice(device));
             { int q = quiesce(); if (q) return q; }
             ATN_HIP(hipMemsetAsync(film.p, 0, film.n * sizeof(float4), stream));
-            if (frames_in_flight > 1) {     // the next frame runs on another bank's stream: its k_gather goes behind the clear
-                if (!ev_film) ATN_HIP(hipEventCreateWithFlags(&ev_film, hipEventDisableTiming));
-                ATN_HIP(hipEventRecord(ev_film, stream)); film_pending = true;
-            }
+            return record_film_writer();        // the next frame's k_gather goes behind the clear
         }
         return ATN_OK;
     }
@@ -2543,19 +2486,12 @@ int atn_trace_closest(atn_ctx* ctx, const atn_ray* rays_host, uint32_t n, float 
     C_HIP(r, hipMemsetAsync(st.p, 0, 64, r.stream));
     {
         // the probe exercises the walk the scene's tree calls for (or the forced one), whatever n is
-        const bool probe_refill = r.flavour_forced ? r.use_refill : r.tree_is_deep;
-        r.use_refill = probe_refill;        // trace_grid sizes the launch for it
-        const dim3 g(r.trace_grid(n)), t(probe_refill ? (uint32_t)atn::kTraceBlock : 256u);
-        const uint32_t lds = 0u;
+        const bool refill = r.refill_walk(false);
+        const dim3 g(r.trace_grid(n, refill)), t(refill ? (uint32_t)atn::kTraceBlock : 256u);
         const atn_ray* rp = rays.p;
-        if (stats_out) {
-            if (probe_refill) hipLaunchKernelGGL((atn::k_trace_batch<true, true>), g, t, lds, r.stream, r.scene, rp, n, t_min, t_max, out.p, st.p);
-            else hipLaunchKernelGGL((atn::k_trace_batch<true, false>), g, t, lds, r.stream, r.scene, rp, n, t_min, t_max, out.p, st.p);
-        }
-        else {
-            if (probe_refill) hipLaunchKernelGGL((atn::k_trace_batch<false, true>), g, t, lds, r.stream, r.scene, rp, n, t_min, t_max, out.p, st.p);
-            else hipLaunchKernelGGL((atn::k_trace_batch<false, false>), g, t, lds, r.stream, r.scene, rp, n, t_min, t_max, out.p, st.p);
-        }
+        atn::with_flags([&](auto c, auto rf) {
+            hipLaunchKernelGGL((atn::k_trace_batch<decltype(c)::value, decltype(rf)::value>), g, t, 0, r.stream, r.scene, rp, n, t_min, t_max, out.p, st.p);
+        }, stats_out != nullptr, refill);
     }
     C_HIP(r, hipGetLastError());
     C_HIP(r, hipMemcpyAsync(out_host, out.p, (size_t)n * sizeof(atn_intersection), hipMemcpyDeviceToHost, r.stream));

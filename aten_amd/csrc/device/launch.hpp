@@ -1,0 +1,102 @@
+// Launch policy shared by the translation units of libaten_amd.so (build.py: HIP_UNITS, compiled in parallel under their own flags):
+// what a pass launches (PassPlan: PathTracing::plan_pass), which kernel instantiation each launch gets, and the launchers regen.hip and
+// shade_relaxed.hip export to aten_amd.hip.
+#pragma once
+#include <type_traits>
+#include "kernels.hpp"
+
+namespace atn {
+
+// f(std::bool_constant<flags>{}...): runtime flags -> template arguments, one instantiation per combination
+template <class F>
+void with_flags(F&& f) { f(); }
+template <class F, class... B>
+void with_flags(F&& f, bool flag, B... rest)
+{
+    if (flag) with_flags([&](auto... x) { f(std::true_type{}, x...); }, rest...);
+    else with_flags([&](auto... x) { f(std::false_type{}, x...); }, rest...);
+}
+
+// f(ShadeFlavour<MS, WAVES>{}) launches the shade instantiation of a material set (BSDFs no uploaded material uses are compiled out):
+// the three smaller sets held to `waves` = 4 / 5 waves per SIMD (kernels.hpp, k_shade_wn), CarPaint and Toon unconstrained (WAVES = 0)
+template <int MS, int WAVES>
+struct ShadeFlavour { static constexpr int ms = MS, waves = WAVES; };
+template <class F>
+void with_shade_flavour(int material_set, int waves, F&& f)
+{
+    switch (material_set) {
+    case kMsCore: if (waves == 5) f(ShadeFlavour<kMsCore, 5>{}); else f(ShadeFlavour<kMsCore, 4>{}); break;
+    case kMsDisney: if (waves == 5) f(ShadeFlavour<kMsDisney, 5>{}); else f(ShadeFlavour<kMsDisney, 4>{}); break;
+    case kMsAnalytic: if (waves == 5) f(ShadeFlavour<kMsAnalytic, 5>{}); else f(ShadeFlavour<kMsAnalytic, 4>{}); break;
+    case kMsCarPaint: f(ShadeFlavour<kMsCarPaint, 0>{}); break;
+    default: f(ShadeFlavour<kMsToon, 0>{}); break;
+    }
+}
+
+enum class PassKind { Serial, Svgf, Regen };
+
+// What one pass over n paths launches: the serial sample loop of a batch, the SVGF path pass of a batch, or a regenerated burst.
+struct PassPlan {
+    PassKind kind;
+    bool refill;                // the persistent lane-refilling walk (deep trees) / the plain walk
+    uint32_t lds_bytes;         // the LDS copy of the node image the walk reads (0: the walk reads global memory)
+    uint32_t block;             // threads per block of the plain walk's fused launches
+    uint32_t trace_grid;        // blocks of an unfused trace launch (n jobs)
+    uint32_t fused_grid;        // blocks of a fused trace launch (2n jobs; in 256-thread blocks for the plain walk)
+    int shade_items;            // queue entries per thread and chunk of the shade launches (FrameParams::chunk_items)
+    uint32_t shade_grid;
+    int shade_waves;            // 4 / 5 (with_shade_flavour)
+};
+
+// One fused trace launch of a pass: shadow rays of stage - 1 + closest-hit rays of stage
+struct TraceLaunch {
+    bool closest;               // k_trace_closest<false, false> instead of k_trace_fused
+    bool refill, lds;
+    uint32_t grid, block, lds_bytes;
+    int prof_kind;              // ATN_K_*
+};
+
+inline TraceLaunch trace_launch(const PassPlan& p, int32_t stage)
+{
+    // the first launch holds only primary rays: coherent, they finish together, and the refill bookkeeping buys nothing (sponza_lod
+    // 4.33 -> 4.30 ms, atrium 4K 221 -> 219 ms)
+    const bool refill = p.refill && stage != 0;
+    // Only closest-hit rays in the first launch of a serial sample (there is no bounce -1 to cast shadows): the closest-hit kernel is
+    // the same walk without the shadow job's code in it (every ray's stop_t is a constant there; the fused kernel's plain flavour grew
+    // by the any-hit twins' root selection: primary rays 0.168 -> 0.203 ms per frame, back at 0.168 through this launch).  The
+    // regenerated pool's stage 0 keeps the fused kernel.
+    const bool closest = p.kind != PassKind::Regen && stage == 0 && p.lds_bytes == 0u;
+    // (timed under "trace_closest" when it is a different kernel from the other launches: the roofline of k_trace_fused<true, .> is
+    // about those)
+    return TraceLaunch{ closest, refill, p.lds_bytes != 0u, refill ? p.fused_grid : p.fused_grid * (256u / p.block),
+                        refill ? (uint32_t)kTraceBlock : p.block, p.lds_bytes, p.refill && stage == 0 ? ATN_K_TRACE_CLOSEST : ATN_K_TRACE_FUSED };
+}
+
+// aten_amd.hip instantiates REGEN = false (the serial loop), regen.hip REGEN = true (the regenerated pool)
+template <bool REGEN>
+void launch_trace_fused(const TraceLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, int32_t bs, int32_t bc, int32_t launch)
+{
+    const dim3 g(l.grid), t(l.block);
+    if constexpr (!REGEN) if (l.closest) { hipLaunchKernelGGL((k_trace_closest<false, false>), g, t, l.lds_bytes, st, pb, sc, bc); return; }
+    with_flags([&](auto refill, auto alpha, auto lds) {
+        hipLaunchKernelGGL((k_trace_fused<decltype(refill)::value, decltype(alpha)::value, decltype(lds)::value, REGEN>), g, t, l.lds_bytes, st, pb, sc, bs, bc, launch);
+    }, l.refill, sc.any_alpha != 0, l.lds);
+}
+
+// ---- regen.hip (PathTracing::render_regen) ----
+void regen_launch_begin(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const atn_camera_param& cam);
+// shadow rays of stage bs (< 0: none) + closest-hit rays of stage bc (< 0: none); `launch` indexes the job-fetch cursor
+void regen_launch_trace(const TraceLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, int32_t bs, int32_t bc, int32_t launch);
+void regen_launch_shade(int material_set, int waves, uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                        const atn_camera_param& cam, int32_t stage, const RegenOut& ro);
+// the stable compaction in front of trace(stage): regions written by shade(stage - 1) (by regen_launch_begin for stage 0) -> dense queues
+void regen_launch_compact(uint32_t grid, hipStream_t st, const PathBuffers& pb, int32_t stage, uint32_t chunk_size, uint32_t* group_counts_next, uint32_t n_groups);
+// the pending epilogues of retired slots (per slot), in front of regen_launch_end (per pixel)
+void regen_launch_flush(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const RegenOut& ro);
+void regen_launch_end(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const RegenOut& ro);
+
+// ---- shade_relaxed.hip ----
+void relaxed_launch_shade(int material_set, int waves, uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                          const atn_camera_param& cam, int32_t bounce);
+
+} // namespace atn

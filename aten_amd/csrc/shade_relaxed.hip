@@ -13,7 +13,7 @@
 #define logf __logf
 #define powf __powf
 #include "../../include/aten_amd.h"
-#include "device/relaxed_launch.hpp"
+#include "device/launch.hpp"
 
 namespace atn {
 
@@ -28,25 +28,14 @@ __global__ void __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) __launch_boun
     shade_body<false, MS>(pb, sc, fp, cam, bounce, SvgfShade{});
 }
 
-template <int MS>
-static void relaxed_waves(int waves, uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const atn_camera_param& cam, int32_t bounce)
-{
-    const dim3 g(grid), t(256);
-    if (waves == 5) hipLaunchKernelGGL((k_shade_relaxed_wn<MS, 5>), g, t, 0, st, pb, sc, fp, cam, bounce);
-    else hipLaunchKernelGGL((k_shade_relaxed_wn<MS, 4>), g, t, 0, st, pb, sc, fp, cam, bounce);
-}
-
 void relaxed_launch_shade(int material_set, int waves, uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
                           const atn_camera_param& cam, int32_t bounce)
 {
-    const dim3 g(grid), t(256);
-    switch (material_set) {
-    case kMsCore: relaxed_waves<kMsCore>(waves, grid, st, pb, sc, fp, cam, bounce); break;
-    case kMsDisney: relaxed_waves<kMsDisney>(waves, grid, st, pb, sc, fp, cam, bounce); break;
-    case kMsAnalytic: relaxed_waves<kMsAnalytic>(waves, grid, st, pb, sc, fp, cam, bounce); break;
-    case kMsCarPaint: hipLaunchKernelGGL((k_shade_relaxed<kMsCarPaint>), g, t, 0, st, pb, sc, fp, cam, bounce); break;
-    default: hipLaunchKernelGGL((k_shade_relaxed<kMsToon>), g, t, 0, st, pb, sc, fp, cam, bounce); break;
-    }
+    with_shade_flavour(material_set, waves, [&](auto k) {
+        using K = decltype(k);
+        if constexpr (K::waves == 0) hipLaunchKernelGGL((k_shade_relaxed<K::ms>), dim3(grid), dim3(256), 0, st, pb, sc, fp, cam, bounce);
+        else hipLaunchKernelGGL((k_shade_relaxed_wn<K::ms, K::waves>), dim3(grid), dim3(256), 0, st, pb, sc, fp, cam, bounce);
+    });
 }
 
 } // namespace atn

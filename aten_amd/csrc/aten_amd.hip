@@ -19,6 +19,7 @@
 #include "device/kernels.hpp"
 #include "device/launch.hpp"
 #include "device/svgf.hpp"
+#include "device/restir.hpp"
 #include "device/lbvh.hpp"
 #include "host/scene_upload.hpp"
 #include "host/ibl_precompute.hpp"
@@ -674,6 +675,7 @@ public:
             if (bstream[k]) (void)hipStreamDestroy(bstream[k]);
         }
         if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (rs_ev) (void)hipEventDestroy(rs_ev);
         if (ev_gather) (void)hipEventDestroy(ev_gather);
         for (auto& e : sv_ev_prepare) if (e) (void)hipEventDestroy(e);
         if (ev_film) (void)hipEventDestroy(ev_film);
@@ -1718,9 +1720,10 @@ public:
 
     // MatricesForRendering::Reset = Camera::ComputeCameraMatrices: mat4::lookat(origin, center, up) and
     // mat4::perspective(znear, zfar, vfov, aspect) written into the existing matrices (mat4.h:457-513)
-    void svgf_reset_matrices()
+    void svgf_reset_matrices() { camera_matrices(camera, sv_W2V, sv_V2C, sv_prevW2V); }
+    static void camera_matrices(const atn_camera_param& camera, float* W2V, float* V2C, float* prevW2V)
     {
-        std::memcpy(sv_prevW2V, sv_W2V, sizeof(sv_W2V));
+        std::memcpy(prevW2V, W2V, 16 * sizeof(float));
         const float* e = camera.origin; const float* at = camera.center; const float* up = camera.up;
         float z[3] = { e[0] - at[0], e[1] - at[1], e[2] - at[2] };
         float il = 1.0f / std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);        // glm::normalize = v * inversesqrt(dot(v, v))
@@ -1729,7 +1732,7 @@ public:
         il = 1.0f / std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
         x[0] *= il; x[1] *= il; x[2] *= il;
         const float y[3] = { z[1] * x[2] - x[1] * z[2], z[2] * x[0] - x[2] * z[0], z[0] * x[1] - x[0] * z[1] };
-        float* m = sv_W2V;
+        float* m = W2V;
         m[0] = x[0]; m[4] = y[0]; m[8] = z[0];
         m[1] = x[1]; m[5] = y[1]; m[9] = z[1];
         m[2] = x[2]; m[6] = y[2]; m[10] = z[2];
@@ -1739,7 +1742,7 @@ public:
         m[15] = 1;
         const float fH = 1 / std::tan((3.14159265358979323846F * (camera.vfov) / 180.0F) * 0.5f);
         const float fW = fH / camera.aspect;
-        float* p = sv_V2C;
+        float* p = V2C;
         p[0] = fW; p[5] = fH;
         p[10] = camera.zfar / (camera.znear - camera.zfar);
         p[11] = camera.znear * camera.zfar / (camera.znear - camera.zfar);
@@ -1923,6 +1926,217 @@ public:
         if (out_host) ATN_HIP(hipMemcpyAsync(out_host, sv_out.p, n * sizeof(float4), hipMemcpyDeviceToHost, fs));
         if (stages_host) ATN_HIP(hipMemcpyAsync(stages_host, sv_stages.p, 3 * n * sizeof(float4), hipMemcpyDeviceToHost, fs));
         if (out_host || stages_host) ATN_HIP(hipStreamSynchronize(fs));
+        return ATN_OK;
+    }
+
+    // ------------------------------------------------------------------------------------------------
+    // ReSTIR (aten::ReSTIRRenderer / idaten::ReSTIRPathTracing, device/restir.hpp): frame-persistent state = the two reservoir and
+    // info sets (ReuseParams, restir_types.h:117-168), the AOVs, the motion/depth buffer and MatricesForRendering
+    // ------------------------------------------------------------------------------------------------
+    DevBuf<float4> rs_res[2][kRestirResPlanes], rs_info[2][kRestirInfoPlanes], rs_nd, rs_am, rs_motion, rs_motion_own, rs_vis, rs_stage;
+    // rs_motion: the caller's motion/depth buffer (atn_restir_set_motion_depth); rs_motion_own: the one compute_motion fills
+    DevBuf<float> rs_dims;
+    int32_t rs_w = 0, rs_h = 0, rs_pos = 0, rs_last = 0;     // rs_pos: the current set of the next frame; rs_last: of the last frame
+    int32_t rs_mode = 1, rs_candidates = 32, rs_capture = 0;
+    bool rs_motion_set = false, rs_pending = false, rs_rendered = false;
+    bool rs_captured = false, rs_last_own_motion = false;      // the last frame wrote the stage buffers / used rs_motion_own
+    size_t rs_motion_count = 0;
+    hipEvent_t rs_ev = nullptr;     // the last frame's reuse passes are done with the sets (the next frame's shade waits for it)
+    float rs_W2V[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    float rs_V2C[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    float rs_prevW2V[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+
+    int restir_set_options(int32_t mode, int32_t n_candidates)
+    {
+        if (mode < 0 || mode > 3) return fail(ATN_ERR_INVALID_ARG, "ReSTIR mode must be 0 (initial candidates), 1 (temporal + spatial), 2 (spatial) or 3 (temporal)");
+        if (n_candidates < 1 || n_candidates > 32) return fail(ATN_ERR_INVALID_ARG, "n_candidates must be in [1, 32]");
+        rs_mode = mode; rs_candidates = n_candidates;
+        return ATN_OK;
+    }
+
+    // ≙ ReSTIRRenderer::SetMotionDepthBuffer (restir.cpp:472-480) / ReSTIRPathTracing::SetGBuffer's motion-depth texture
+    int restir_set_motion_depth(const atn_vec4* md, uint32_t n)
+    {
+        if (!md || n == 0) return fail(ATN_ERR_INVALID_ARG, "empty motion/depth buffer");
+        ATN_HIP(hipSetDevice(device));
+        ATN_HIP(rs_motion.resize(n));
+        ATN_HIP(hipMemcpyAsync(rs_motion.p, md, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        rs_motion_set = true;
+        rs_motion_count = n;
+        return ATN_OK;
+    }
+
+    // forget the history: both sets are re-initialised by the next frame, the camera matrices start from the identity
+    int restir_reset()
+    {
+        rs_w = 0; rs_h = 0; rs_pos = 0; rs_last = 0; rs_rendered = false; rs_captured = false;
+        const float id[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+        std::memcpy(rs_W2V, id, sizeof(id)); std::memcpy(rs_V2C, id, sizeof(id)); std::memcpy(rs_prevW2V, id, sizeof(id));
+        return ATN_OK;
+    }
+
+    // Reservoir() / ReSTIRInfo() of a fresh ReuseParams: y = -1, M = 0, mtrl_idx = mesh_id = -1
+    int restir_ensure(int32_t w, int32_t h)
+    {
+        const size_t n = (size_t)w * h;
+        float neg1;
+        { const int32_t m1 = -1; std::memcpy(&neg1, &m1, 4); }
+        if (w != rs_w || h != rs_h) {
+            for (int k = 0; k < 2; k++) {
+                for (auto& b : rs_res[k]) { ATN_HIP(b.resize(n)); svgf_fill(b.p, n, make_float4(0, 0, 0, 0)); }
+                for (auto& b : rs_info[k]) { ATN_HIP(b.resize(n)); svgf_fill(b.p, n, make_float4(0, 0, 0, 0)); }
+                svgf_fill(rs_res[k][0].p, n, make_float4(0.0F, 0.0F, neg1, 0.0F));
+                svgf_fill(rs_info[k][0].p, n, make_float4(0.0F, 0.0F, 0.0F, neg1));
+                svgf_fill(rs_info[k][3].p, n, make_float4(0.0F, neg1, 0.0F, 0.0F));
+            }
+            ATN_HIP(rs_nd.resize(n)); svgf_fill(rs_nd.p, n, make_float4(0, 0, 0, 1));
+            ATN_HIP(rs_am.resize(n)); svgf_fill(rs_am.p, n, make_float4(0, 0, 0, 1));
+            if (!rs_motion_set || rs_motion_count < n) { ATN_HIP(rs_motion.resize(n)); rs_motion_set = false; rs_motion_count = 0; }
+            rs_w = w; rs_h = h; rs_pos = 0; rs_last = 0;
+        }
+        ATN_HIP(rs_vis.resize(n_slots));
+        if (rs_capture) { ATN_HIP(rs_stage.resize(6 * n)); ATN_HIP(rs_dims.resize(n)); }
+        return ATN_OK;
+    }
+
+    // ≙ idaten::ReSTIRPathTracing::render + OnRender (src/libidaten/restir/restir.cpp:47-100, restir.cu:321-420), with the CPU
+    // renderer's sample stream (docs/RESTIR.md): generate the path once, bounce 0 = ReSTIR shade + visibility + temporal (frame > 1)
+    // + spatial + pixel colour, bounces >= 1 = the path tracer's own k_shade.
+    int restir_render(const atn_destination* d, int32_t compute_motion, atn_vec4* out_host)
+    {
+        int rc = check_ready(d);
+        if (rc) return rc;
+        if (d->sample != 1) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR renders one sample per pixel (destination.sample must be 1)");
+        if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR needs the whole frame on one GPU (spatial reuse reads pixels of other shards)");
+        if (regen_mode != 0) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR runs the serial sample loop: switch path regeneration off (atn_set_regeneration(0))");
+        if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR has no relaxed-math kernels: atn_set_shade_math(0)");
+        if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR frames do not count rays (count_stats must be 0)");
+        if (scene.material_set >= kMsToon) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR does not shade toon / stylised materials");
+        ATN_HIP(hipSetDevice(device));
+        if (frames_in_flight > 1 && (d->width != rs_w || d->height != rs_h)) { rc = quiesce(); if (rc) return rc; }
+        rc = begin_frame(*d, frames_in_flight > 1);
+        if (rc) return rc;
+        rc = restir_ensure(d->width, d->height);
+        if (rc) return rc;
+        const size_t n = (size_t)d->width * d->height;
+        if (!compute_motion && (!rs_motion_set || rs_motion_count < n))
+            return fail(ATN_ERR_INVALID_ARG, "no motion/depth buffer: call atn_restir_set_motion_depth or pass compute_motion = 1");
+        if (compute_motion) ATN_HIP(rs_motion_own.resize(n));
+        if (!rs_ev) ATN_HIP(hipEventCreateWithFlags(&rs_ev, hipEventDisableTiming));
+        const bool prof = d->profile != 0;
+        camera_matrices(camera, rs_W2V, rs_V2C, rs_prevW2V);
+
+        FrameParams fp = frame_params(*d);
+        PathBuffers pb = buffers(false);
+        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
+        fp.chunk_items = plan.shade_items;
+        const int32_t cur = rs_pos, oth = 1 - rs_pos;
+        RestirArgs ra{};
+        for (int k = 0; k < kRestirResPlanes; k++) { ra.cur.res[k] = rs_res[cur][k].p; ra.other.res[k] = rs_res[oth][k].p; }
+        for (int k = 0; k < kRestirInfoPlanes; k++) { ra.cur.info[k] = rs_info[cur][k].p; ra.other.info[k] = rs_info[oth][k].p; }
+        ra.nd = rs_nd.p; ra.am = rs_am.p; ra.motion = compute_motion ? rs_motion_own.p : rs_motion.p; ra.vis = rs_vis.p;
+        mat_mul(rs_V2C, rs_W2V, ra.w2c);
+        mat_mul(rs_V2C, rs_prevW2V, ra.prev_w2c);
+        for (int k = 0; k < 4; k++) ra.w2c3[k] = ra.w2c[12 + k];
+        ra.n_candidates = rs_candidates;
+        ra.stage_res = rs_capture ? rs_stage.p : nullptr;
+        ra.dims = rs_capture ? rs_dims.p : nullptr;
+        PathBuffers pb_vis = pb;        // the visibility rays add their (1, 1, 1) to rs_vis instead of the path's contribution
+        pb_vis.contrib = rs_vis.p;
+
+        const uint32_t g_slots = grid_for(n_slots), g_all = (n_slots + 255u) / 256u;
+        ATN_HIP(hipMemsetAsync(counters.p, 0, (size_t)4 * counters_depth * 4, stream));
+        prof_begin(prof, ATN_K_GEN);
+        hipLaunchKernelGGL(k_gen_path, dim3(g_slots), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
+        prof_end(prof);
+        for (int32_t b = 0; b <= d->maxDepth; b++) {
+            const TraceLaunch tl = trace_launch(plan, b);
+            prof_begin(prof, tl.prof_kind);
+            launch_trace_fused<false>(tl, stream, b == 1 ? pb_vis : pb, scene, b - 1, b < d->maxDepth ? b : -1, b);
+            prof_end(prof);
+            if (b == 1) {
+                // EvaluateVisibility's outcome, ApplyTemporalReuse (frame > 1), ApplySpatialReuse + ComputePixelColor (ReSTIRMode,
+                // restir.h:25-29; restir_reuse.cpp:132-213)
+                const bool temporal = (rs_mode == 1 || rs_mode == 3) && d->frame > 1;
+                prof_begin(prof, ATN_K_SHADE);
+                restir_launch_temporal(scene.material_set, temporal, stream, pb, scene, fp, ra);
+                if (rs_mode == 1 || rs_mode == 2) restir_launch_spatial(scene.material_set, stream, pb, scene, fp, ra);
+                else restir_launch_color(scene.material_set, stream, pb, scene, fp, ra);
+                prof_end(prof);
+                ATN_HIP(hipEventRecord(rs_ev, stream));
+                rs_pending = true;
+            }
+            if (b == d->maxDepth) break;
+            prof_begin(prof, ATN_K_SHADE);
+            if (b == 0) {
+                // the previous frame's reuse passes read the sets, AOVs and visibility plane this frame's bounce 0 overwrites
+                if (rs_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, rs_ev, 0));
+                restir_launch_shade(scene.material_set, plan.shade_grid, stream, pb, scene, fp, camera, ra);
+                if (compute_motion) restir_launch_motion(stream, fp, ra);
+                restir_launch_vis_prep(grid_for(n_slots), stream, pb, scene, fp, ra);
+            }
+            else launch_shade<false>(plan, stream, pb, fp, b, SvgfShade{});
+            prof_end(prof);
+        }
+        rs_last = cur;
+        rs_pos = oth;           // ReuseParams::Update, every frame whatever the mode
+        rs_rendered = true;
+        rs_captured = rs_capture != 0;
+        rs_last_own_motion = compute_motion != 0;
+        rc = wait_film();
+        if (rc) return rc;
+        prof_begin(prof, ATN_K_GATHER);
+        hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
+        prof_end(prof);
+        ATN_HIP(hipGetLastError());
+        rc = end_film_frame();
+        if (rc) return rc;
+        if (out_host) {
+            ATN_HIP(hipMemcpyAsync(out_host, film.p, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            ATN_HIP(hipStreamSynchronize(stream));
+        }
+        return ATN_OK;
+    }
+
+    // stage buffers of the last frame (tests): 0 / 1 / 2 the reservoirs after the shade, temporal (visibility) and spatial passes as
+    // float[n][5] {y, M, W, w_sum, target_pdf_of_y} (atn_restir_capture); 3 the infos float4[4][n]; 4 / 5 the AOVs; 6 motion-depth;
+    // 7 the CMJ dimension of every pixel after bounce 0's passes, uint32[n] (atn_restir_capture)
+    int restir_download(int32_t which, void* out)
+    {
+        if (!rs_rendered || !out) return fail(ATN_ERR_INVALID_ARG, "no ReSTIR frame has been rendered");
+        const size_t n = (size_t)rs_w * rs_h;
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        ATN_HIP(hipStreamSynchronize(stream));
+        if ((which <= 2 || which == 7) && !rs_captured) return fail(ATN_ERR_INVALID_ARG, "the last frame kept no stage buffers: atn_restir_capture(ctx, 1) before the frame");
+        if (which >= 0 && which <= 2) {
+            std::vector<float4> h(2 * n);
+            ATN_HIP(hipMemcpy(h.data(), rs_stage.p + (size_t)which * 2 * n, 2 * n * sizeof(float4), hipMemcpyDeviceToHost));
+            float* o = static_cast<float*>(out);
+            for (size_t i = 0; i < n; i++) {
+                const float4 a = h[i], b = h[n + i];
+                int32_t y, M;
+                std::memcpy(&M, &a.y, 4); std::memcpy(&y, &a.z, 4);
+                o[5 * i] = (float)y; o[5 * i + 1] = (float)M; o[5 * i + 2] = a.w; o[5 * i + 3] = a.x; o[5 * i + 4] = b.x;
+            }
+            return ATN_OK;
+        }
+        if (which == 3) {
+            for (int k = 0; k < kRestirInfoPlanes; k++)
+                ATN_HIP(hipMemcpy(static_cast<float4*>(out) + (size_t)k * n, rs_info[rs_last][k].p, n * sizeof(float4), hipMemcpyDeviceToHost));
+            return ATN_OK;
+        }
+        const void* src = which == 4 ? (const void*)rs_nd.p : which == 5 ? (const void*)rs_am.p : which == 6 ? (const void*)(rs_last_own_motion ? rs_motion_own.p : rs_motion.p)
+                        : which == 7 ? (const void*)rs_dims.p : nullptr;
+        if (!src) return fail(ATN_ERR_INVALID_ARG, "no such ReSTIR buffer");
+        if (which == 7) {
+            std::vector<float> h(n);
+            ATN_HIP(hipMemcpy(h.data(), src, n * sizeof(float), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; i++) static_cast<uint32_t*>(out)[i] = (uint32_t)h[i];
+            return ATN_OK;
+        }
+        ATN_HIP(hipMemcpy(out, src, n * sizeof(float4), hipMemcpyDeviceToHost));
         return ATN_OK;
     }
 
@@ -2197,6 +2411,20 @@ int atn_svgf_download(atn_ctx* ctx, int32_t which, atn_vec4* out_host)
     C_HIP(r, hipStreamSynchronize(r.stream));
     return ATN_OK;
 }
+int atn_restir_set_options(atn_ctx* ctx, int32_t mode, int32_t n_candidates)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    return ctx->r.restir_set_options(mode, n_candidates);
+}
+int atn_restir_render(atn_ctx* ctx, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.restir_render(dst, compute_motion, out_host); });
+}
+int atn_restir_set_motion_depth(atn_ctx* ctx, const atn_vec4* motion_depth, uint32_t n) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.restir_set_motion_depth(motion_depth, n); }); }
+int atn_restir_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return ctx->r.restir_reset(); }
+int atn_restir_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.rs_capture = on != 0; return ATN_OK; }
+int atn_restir_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.restir_download(which, out_host); }); }
 int atn_svgf_denoise(atn_ctx* ctx, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host)
 {
     CTX_QUIET_OR_FAIL(ctx);

@@ -99,4 +99,15 @@ void regen_launch_end(uint32_t grid, hipStream_t st, const PathBuffers& pb, cons
 void relaxed_launch_shade(int material_set, int waves, uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
                           const atn_camera_param& cam, int32_t bounce);
 
+// ---- restir.hip (device/restir.hpp) ----
+struct RestirArgs;
+void restir_launch_shade(int material_set, uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                         const atn_camera_param& cam, const RestirArgs& ra);
+void restir_launch_vis_prep(uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const RestirArgs& ra);
+void restir_launch_temporal(int material_set, bool temporal, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                            const RestirArgs& ra);
+void restir_launch_spatial(int material_set, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const RestirArgs& ra);
+void restir_launch_color(int material_set, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const RestirArgs& ra);
+void restir_launch_motion(hipStream_t st, const FrameParams& fp, const RestirArgs& ra);
+
 } // namespace atn

@@ -37,8 +37,7 @@ __global__ void __launch_bounds__(256) k_svgf_sample_end(PathBuffers pb, FramePa
     if (flags & F_TERMINATED) pb.done[slot] = 1;
 }
 
-// svgf::PrepareForDenoise (svgf_impl.h:119-144) + the motion pass that stands in for the reference's GL raster
-// pass (src/shader/ssrt_fs.glsl:31-47; static geometry): motion = prevNDC01 - curNDC01, z = clip w.
+// svgf::PrepareForDenoise (svgf_impl.h:119-144) + the motion pass (motion_depth, svgf_frame.hpp).
 __global__ void __launch_bounds__(256) k_svgf_prepare(SvgfFrame sf)
 {
     int32_t ix, iy;
@@ -63,23 +62,7 @@ __global__ void __launch_bounds__(256) k_svgf_prepare(SvgfFrame sf)
     sf.tmp[idx] = c;
     if (sf.stages) sf.stages[idx] = make_float4(c.x, c.y, c.z, 1.0F);
     sf.out[idx] = make_float4(c.x, c.y, c.z, 1.0F);
-    if (sf.compute_motion) {
-        const float4 wp = sf.primary[idx];
-        float4 md = make_float4(0.0F, 0.0F, -1.0F, 1.0F);
-        if (wp.w != 0.0F) {
-            const float* a = sf.w2c; const float* b = sf.prev_w2c;
-            const float cx = a[0] * wp.x + a[1] * wp.y + a[2] * wp.z + a[3] * 1.0F;
-            const float cy = a[4] * wp.x + a[5] * wp.y + a[6] * wp.z + a[7] * 1.0F;
-            const float cw = a[12] * wp.x + a[13] * wp.y + a[14] * wp.z + a[15] * 1.0F;
-            const float px = b[0] * wp.x + b[1] * wp.y + b[2] * wp.z + b[3] * 1.0F;
-            const float py = b[4] * wp.x + b[5] * wp.y + b[6] * wp.z + b[7] * 1.0F;
-            const float pw = b[12] * wp.x + b[13] * wp.y + b[14] * wp.z + b[15] * 1.0F;
-            const float csx = (cx / cw) * 0.5F + 0.5F, csy = (cy / cw) * 0.5F + 0.5F;
-            const float psx = (px / pw) * 0.5F + 0.5F, psy = (py / pw) * 0.5F + 0.5F;
-            md = make_float4(psx - csx, psy - csy, cw, 1.0F);
-        }
-        sf.motion[idx] = md;
-    }
+    if (sf.compute_motion) sf.motion[idx] = motion_depth(sf.w2c, sf.prev_w2c, sf.primary[idx]);
 }
 
 // RecomputeTemporalWeightFromSurroundingPixels (svgf_impl.h:386-423): the temporal weight of a non-background pixel becomes

@@ -58,4 +58,24 @@ ATN_DEV float pow128(float x)
 // weights it produces only ever multiply colours
 ATN_DEV float svgf_exp(float x) { return __expf(x); }
 
+// The motion pass that stands in for the reference's GL raster pass (src/shader/ssrt_fs.glsl:31-47; static geometry): motion =
+// prevNDC01 - curNDC01, z = clip w, from the world position of the bounce-0 hit (w = 0: a miss).  SVGF's prepare pass and ReSTIR's
+// motion pass share it.
+ATN_DEV float4 motion_depth(const float* a, const float* b, const float4& wp)
+{
+    float4 md = make_float4(0.0F, 0.0F, -1.0F, 1.0F);
+    if (wp.w != 0.0F) {
+        const float cx = a[0] * wp.x + a[1] * wp.y + a[2] * wp.z + a[3] * 1.0F;
+        const float cy = a[4] * wp.x + a[5] * wp.y + a[6] * wp.z + a[7] * 1.0F;
+        const float cw = a[12] * wp.x + a[13] * wp.y + a[14] * wp.z + a[15] * 1.0F;
+        const float px = b[0] * wp.x + b[1] * wp.y + b[2] * wp.z + b[3] * 1.0F;
+        const float py = b[4] * wp.x + b[5] * wp.y + b[6] * wp.z + b[7] * 1.0F;
+        const float pw = b[12] * wp.x + b[13] * wp.y + b[14] * wp.z + b[15] * 1.0F;
+        const float csx = (cx / cw) * 0.5F + 0.5F, csy = (cy / cw) * 0.5F + 0.5F;
+        const float psx = (px / pw) * 0.5F + 0.5F, psy = (py / pw) * 0.5F + 0.5F;
+        md = make_float4(psx - csx, psy - csy, cw, 1.0F);
+    }
+    return md;
+}
+
 } // namespace atn

@@ -259,6 +259,59 @@ class PathTracing:
         self.width, self.height = width, height
         return (out, st) if stages else out
 
+    # ---- ReSTIR (idaten::ReSTIRPathTracing: UpdateSceneData / SetGBuffer / render; docs/RESTIR.md)
+    RESTIR_MODES = {"initial": 0, "restir": 1, "spatial": 2, "temporal": 3}
+    RESTIR_STAGES = {"initial": 0, "temporal": 1, "spatial": 2}
+
+    def restir_set_options(self, mode=1, n_candidates=32):
+        """mode 0 = initial candidates only, 1 = temporal + spatial (default), 2 = spatial, 3 = temporal; n_candidates in [1, 32]."""
+        self._check(self._l.atn_restir_set_options(self._ctx, self.RESTIR_MODES.get(mode, mode), n_candidates))
+
+    def restir_render(self, width, height, max_depth=5, rr_depth=3, frame=0, progressive=True, compute_motion=False,
+                      download=True, profile=False):
+        """One ReSTIR frame (1 sample per pixel) into the film; returns the film [h, w, 4]."""
+        d = Destination(width, height, max_depth, rr_depth, 1, frame, int(progressive), 1, 0, int(profile))
+        out = np.empty((height, width, 4), np.float32) if download else None
+        self._check(self._l.atn_restir_render(self._ctx, C.byref(d), 1 if compute_motion else 0, out.ctypes.data if download else None))
+        self.width, self.height = width, height
+        return out
+
+    def restir_set_motion_depth(self, md):
+        md = np.ascontiguousarray(md, np.float32).reshape(-1, 4)
+        self._check(self._l.atn_restir_set_motion_depth(self._ctx, md.ctypes.data, len(md)))
+
+    def restir_reset(self):
+        self._check(self._l.atn_restir_reset(self._ctx))
+
+    def restir_capture(self, on=True):
+        """Keep the stage buffers (reservoirs after each pass, CMJ dimensions) of the next frames for restir_buffer."""
+        self._check(self._l.atn_restir_capture(self._ctx, int(on)))
+
+    def restir_buffer(self, name):
+        """The last ReSTIR frame's stage buffers.  'initial' / 'temporal' / 'spatial': dict of [h, w] arrays y, M (int32), W, w_sum,
+        target_pdf (needs restir_capture); 'info': dict nml, wi, p [h, w, 3], u, v, pre_r, mtrl, mesh, hit; 'nd' / 'am' / 'motion':
+        [h, w, 4]; 'dims': uint32 [h, w] (needs restir_capture)."""
+        w, h = self.width, self.height
+        if name in self.RESTIR_STAGES:
+            out = np.empty((h, w, 5), np.float32)
+            self._check(self._l.atn_restir_download(self._ctx, self.RESTIR_STAGES[name], out.ctypes.data))
+            return dict(y=out[..., 0].astype(np.int32), M=out[..., 1].astype(np.int32), W=out[..., 2].copy(),
+                        w_sum=out[..., 3].copy(), target_pdf=out[..., 4].copy())
+        if name == "info":
+            out = np.empty((4, h, w, 4), np.float32)
+            self._check(self._l.atn_restir_download(self._ctx, 3, out.ctypes.data))
+            return dict(nml=out[0, ..., :3].copy(), mtrl=out[0, ..., 3].copy().view(np.int32), wi=out[1, ..., :3].copy(),
+                        u=out[1, ..., 3].copy(), p=out[2, ..., :3].copy(), v=out[2, ..., 3].copy(), pre_r=out[3, ..., 0].copy(),
+                        mesh=out[3, ..., 1].copy().view(np.int32), hit=out[3, ..., 2].copy())
+        if name == "dims":
+            out = np.empty((h, w), np.uint32)
+            self._check(self._l.atn_restir_download(self._ctx, 7, out.ctypes.data))
+            return out
+        which = {"nd": 4, "am": 5, "motion": 6}[name]
+        out = np.empty((h, w, 4), np.float32)
+        self._check(self._l.atn_restir_download(self._ctx, which, out.ctypes.data))
+        return out
+
     def svgf_denoise(self, width, height, frame=0, compute_motion=False, stages=False, download=True, profile=False):
         """The filter passes of OnRender on the buffers as they stand (svgf_upload / a previous path pass)."""
         d = Destination(width, height, 1, 1, 1, frame, 0, 1, 0, int(profile))

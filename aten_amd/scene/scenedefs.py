@@ -75,9 +75,10 @@ def envmap_avg_illum(tex):
     return float((lum * s).sum() / (s.sum() * tex.shape[1]))
 
 
-def sponza_lod(asset_dir=None, mtype=L.MTRL_GGX, ibl=True, use_sbvh=True, textures=True, bvh_options=None, optimize_sbvh=False):
+def sponza_lod(asset_dir=None, mtype=L.MTRL_GGX, ibl=True, use_sbvh=True, textures=True, bvh_options=None, optimize_sbvh=False,
+               add_lights=None):
     """BASELINE config 3 stand-in: sponza_lod.obj (12,852 tris) with the reference-built
-    sponza_lod.sbvh tree, GGX materials, synthetic IBL."""
+    sponza_lod.sbvh tree, GGX materials, synthetic IBL.  add_lights(builder, bbox_min, bbox_max, cam): extra lights."""
     asset_dir = asset_dir or os.path.join(ASSETS, "sponza")
     b = SceneBuilder()
 
@@ -98,12 +99,70 @@ def sponza_lod(asset_dir=None, mtype=L.MTRL_GGX, ibl=True, use_sbvh=True, textur
     if use_sbvh:
         b.import_sbvh(objs[0], os.path.join(asset_dir, "sponza_lod.sbvh"), optimize=optimize_sbvh)
     b.create_instance(objs[0])
+    if add_lights is not None:
+        p = np.asarray(b.pos, np.float32).reshape(-1, 4)[:, :3]
+        add_lights(b, p.min(axis=0), p.max(axis=0), cam)
     if ibl:
         env = synthetic_envmap()
         tid = b.add_texture("synthetic_sky_2048x1024", env)
         b.add_ibl(tid, avg_illum=envmap_avg_illum(env))
     else:
         b.set_background((1.0, 1.0, 1.0))
+    return b.build(), cam
+
+
+def _light_grid(b, bmin, bmax, intensity, scale, step=5):
+    """ManyLightCryteckSponzaScene's grid (scenedefs.cpp:987-1044): step^3 point lights, R / G / B in turn.  As written there,
+    x and z restart from 0 (not from the box's minimum) on every row; y starts at the minimum."""
+    sv = (np.asarray(bmax, np.float32) - np.asarray(bmin, np.float32)) / np.float32(step)
+    colors = [(1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)]
+    num = 0
+    y = np.float32(bmin[1])
+    for _ in range(step):
+        z = np.float32(0.0)
+        for _ in range(step):
+            x = np.float32(0.0)
+            for _ in range(step):
+                b.add_point_light((float(x), float(y), float(z)), colors[num % 3], intensity, scale=scale)
+                x = np.float32(x + sv[0])
+                num += 1
+            z = np.float32(z + sv[2])
+        y = np.float32(y + sv[1])
+
+
+def many_light_sponza(asset_dir=None, textures=True):
+    """ManyLightCryteckSponzaScene (scenedefs.cpp:987-1056) restated on the sponza_lod stand-in: the 5 x 5 x 5 grid of point lights
+    over the scene's bounding box (R / G / B in turn, intensity 500) plus one white light in front of the camera -- 126 lights.
+    The reference's scene is in centimetres and scales its lights by 100; sponza_lod is in metres (its camera sits 1 unit above the
+    floor), so the same irradiance needs scale = 100 / 100^2 = 0.01.  Background: black (no IBL: the lights are the scene's light)."""
+    def add(b, bmin, bmax, cam):
+        _light_grid(b, bmin, bmax, 500.0, 0.01)
+        b.add_point_light(tuple(float(c) for c in cam["at"]), (1.0, 1.0, 1.0), 500.0, scale=0.01)
+    fs, cam = sponza_lod(asset_dir, ibl=False, textures=textures, add_lights=add)
+    return fs, cam
+
+
+def many_light_cornell(n=8, asset_dir=None):
+    """A small many-light test scene (not a reference scene): the Cornell box with white Lambert surfaces and n coloured point
+    lights spread over the ceiling (no area light), black background.  White walls because ReSTIR's pixel colour carries the
+    albedo TEXTURE and not the base colour (docs/RESTIR.md), so that direct light agrees with the path tracer's."""
+    asset_dir = asset_dir or os.path.join(ASSETS, "cornellbox")
+    b = SceneBuilder()
+
+    def create_mtrl(name, mtype, clr, albedo, nml):
+        return b.add_material(name, L.MTRL_DIFFUSE, (1.0, 1.0, 1.0))
+
+    objs = b.load_obj(os.path.join(asset_dir, "orig.obj"), create_mtrl=create_mtrl, separate_objs=True, normal_on_the_fly=True)
+    for o in objs:
+        if b.objects[o]["name"] != "light":
+            b.create_instance(o)
+    rng = np.random.default_rng(7)
+    colors = [(1.0, 0.3, 0.3), (0.3, 1.0, 0.3), (0.3, 0.3, 1.0), (1.0, 1.0, 0.6)]
+    for i in range(n):
+        x, z = rng.uniform(-0.8, 0.8), rng.uniform(-0.8, 0.8)
+        b.add_point_light((float(x), 1.2 + 0.3 * float(rng.uniform()), float(z)), colors[i % 4], 4.0 * 8.0 / max(n, 1))
+    b.set_background((0.0, 0.0, 0.0))
+    cam = dict(pos=(0.0, 1.0, 3.0), at=(0.0, 1.0, 0.0), vfov=45.0)
     return b.build(), cam
 
 

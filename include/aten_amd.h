@@ -334,6 +334,29 @@ int atn_svgf_set_dilate_temporal_weight(atn_ctx* ctx, int32_t on);
  * 4-7 GetPrevAovBuffer() (the set the last frame wrote), 8 temporary colour, 9 motion/depth, 10 primary hit
  * position, 11/12 a-trous ping-pong buffers, 13 output, 14 contributions. */
 int atn_svgf_download(atn_ctx* ctx, int32_t which, atn_vec4* out_host);
+
+/* ---- ReSTIR (idaten::ReSTIRPathTracing; docs/RESTIR.md) ------------------------------------------------------------------
+ * Many-light direct lighting at the primary hit with reservoir resampling (initial candidates, temporal and spatial reuse); the
+ * bounces behind it are the path tracer's.  Frame-persistent state lives in the context (atn_restir_reset forgets it).
+ *   atn_restir_set_options: mode 0 = initial candidates only, 1 = temporal + spatial (default), 2 = spatial, 3 = temporal;
+ *                           n_candidates in [1, 32] (default 32)
+ *   atn_restir_render: one frame (destination.sample must be 1); the film follows atn_render's progressive / overwrite rules.
+ *                      compute_motion != 0: motion/depth from the primary hits (as atn_svgf_render), else the buffer of
+ *                      atn_restir_set_motion_depth.  ATN_ERR_UNSUPPORTED for sample != 1, a screen shard with world > 1, path
+ *                      regeneration, relaxed shade math, count_stats and toon materials.
+ *   atn_restir_capture: keep the stage buffers of the next frames (tests)
+ *   atn_restir_download: which = 0 / 1 / 2 reservoirs after the shade / temporal (visibility) / spatial pass, float[w*h][5]
+ *                        {y, M, W, w_sum, target_pdf} (capture on); 3 the infos, atn_vec4[4][w*h] {nml, mtrl id bits} {wi, u}
+ *                        {p, v} {pre_sampled_r, mesh id bits, hit, 0}; 4 AOV normal+depth; 5 AOV albedo+mesh id; 6 the
+ *                        motion-depth the last frame used (atn_vec4[w*h]: the caller's, or the one compute_motion computed -- it
+ *                        never overwrites the caller's); 7 the CMJ dimension of every pixel after bounce 0's passes, uint32[w*h].
+ *                        0-2 and 7 only for a frame rendered with capture on. */
+int atn_restir_set_options(atn_ctx* ctx, int32_t mode, int32_t n_candidates);
+int atn_restir_render(atn_ctx* ctx, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host);
+int atn_restir_set_motion_depth(atn_ctx* ctx, const atn_vec4* motion_depth, uint32_t n);
+int atn_restir_reset(atn_ctx* ctx);
+int atn_restir_capture(atn_ctx* ctx, int32_t on);
+int atn_restir_download(atn_ctx* ctx, int32_t which, void* out_host);
 /* The filter passes alone (everything of OnRender after the sample loop, svgf.cpp:515-637) on whatever the
  * path pass -- or atn_svgf_upload -- left in the buffers: contributions (which = 14: contrib.xyz, sample count),
  * the current AOVs (0, 1), primary hit positions (10), motion/depth (9).  This is how a caller that already has a

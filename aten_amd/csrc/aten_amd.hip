@@ -20,6 +20,7 @@
 #include "device/launch.hpp"
 #include "device/svgf.hpp"
 #include "device/restir.hpp"
+#include "device/npr.hpp"
 #include "device/lbvh.hpp"
 #include "host/scene_upload.hpp"
 #include "host/ibl_precompute.hpp"
@@ -745,6 +746,7 @@ public:
         scene.lights = lights.p; scene.light_plane = light_plane.p; scene.texels = texels.p; scene.texels8 = texels8.p; scene.textures = textures.p;
         scene.mtx_quads = (uint32_t)img.matrices.size();
         has_scene = true;
+        { const int nrc = npr_decode(s, img); if (nrc) return nrc; }
         env_host.clear(); env_w = env_h = 0; ibl_tables_ready = false;
         {
             const int32_t ei = s->config.bg.envmap_tex_idx;
@@ -2140,6 +2142,199 @@ public:
         return ATN_OK;
     }
 
+    // ------------------------------------------------------------------------------------------------
+    // NPR feature lines (aten::NprPathTracer::radiance_with_feature_line / idaten::NPRPathTracing, device/npr.hpp; docs/NPR.md):
+    // per-slot sample-ray state, the bounce's ray list, and what the upload decoded of FeatureLineConfig / FeatureLineMtrlConfig
+    // (read by the NPR kernels only)
+    // ------------------------------------------------------------------------------------------------
+    DevBuf<float4> np_disc_c, np_disc_n, np_desc_p, np_desc_n, np_ray_o, np_ray_d, np_ray_hit, np_st_line, np_st_desc, np_st_disc;
+    DevBuf<uint32_t> np_live, np_work, np_counters, np_queue, np_mflags, np_st_dims;
+    DevBuf<float> np_hpd;
+    std::vector<uint32_t> np_mflags_host;
+    atn_feature_line_config np_cfg{};
+    bool np_stencil = false, np_alpha = false, np_carpaint = false;     // what the refusals need (upload)
+    uint32_t np_slots = 0;
+    int32_t np_w = 0, np_h = 0, np_capture = 0, np_depth = 0;
+    bool np_captured = false, np_pending = false;
+    hipEvent_t np_ev = nullptr;     // the last NPR frame's kernels are done with the sample-ray state (the next frame waits for it)
+
+    int npr_decode(const atn_scene_desc* s, const HostSceneImage& img)
+    {
+        std::memcpy(&np_cfg, s->config.feature_line, sizeof(np_cfg));
+        np_mflags_host.assign((size_t)s->n_materials + 1, 0u);        // (+ the white-diffuse fallback: no lines)
+        np_stencil = false; np_carpaint = false;
+        bool maybe_alpha = false;
+        for (uint32_t i = 0; i < s->n_materials; i++) {
+            atn_feature_line_mtrl fl;
+            std::memcpy(&fl, s->materials[i].feature_line, sizeof(fl));
+            np_mflags_host[i] = (fl.enable ? 1u : 0u) | ((uint32_t)fl.metric_flag << 8);
+            if (s->materials[i].stencil_type == 2) np_stencil = true;         // StencilType::STENCIL
+            if (s->materials[i].type == ATN_MTRL_CARPAINT) np_carpaint = true;
+        }
+        for (const DevMaterial& dm : img.materials) if (dm.attrib & kAttrMaybeAlpha) maybe_alpha = true;
+        np_alpha = s->config.enable_alpha_blending != 0 && maybe_alpha;
+        ATN_HIP(np_mflags.upload(np_mflags_host, stream));
+        return ATN_OK;
+    }
+
+    // the per-slot state: previous hit points and normals start at zero (SampleRayInfo's vec3s) and persist across samples and frames
+    int npr_ensure(int32_t w, int32_t h, int32_t max_depth)
+    {
+        if (n_slots != np_slots) {
+            const size_t r = (size_t)kNprRays * n_slots;
+            if (r >= ((size_t)1 << 28)) return fail(ATN_ERR_UNSUPPORTED, "NPR frames list at most 2^28 sample rays per bounce (shard the screen)");
+            ATN_HIP(np_disc_c.resize(n_slots)); ATN_HIP(np_disc_n.resize(n_slots));
+            ATN_HIP(np_desc_p.resize(r)); ATN_HIP(np_desc_n.resize(r));
+            ATN_HIP(np_ray_o.resize(r)); ATN_HIP(np_ray_d.resize(r)); ATN_HIP(np_ray_hit.resize(r));
+            ATN_HIP(np_live.resize(n_slots)); ATN_HIP(np_work.resize(n_slots)); ATN_HIP(np_hpd.resize(n_slots)); ATN_HIP(np_queue.resize(n_slots));
+            ATN_HIP(hipMemsetAsync(np_desc_p.p, 0, r * sizeof(float4), stream));
+            ATN_HIP(hipMemsetAsync(np_desc_n.p, 0, r * sizeof(float4), stream));
+            np_slots = n_slots;
+        }
+        if (max_depth > np_depth) { ATN_HIP(np_counters.resize((size_t)kNprCounters * max_depth)); np_depth = max_depth; }
+        if (np_capture) {
+            const size_t n = (size_t)w * h;
+            ATN_HIP(np_st_line.resize(n)); ATN_HIP(np_st_desc.resize(kNprRays * n)); ATN_HIP(np_st_disc.resize(2 * n)); ATN_HIP(np_st_dims.resize(n));
+        }
+        np_w = w; np_h = h;
+        return ATN_OK;
+    }
+
+    // Camera::ComputePixelWidthAtDistance (camera.h:182-197): the "hfov" is vfov * H / W, in degrees
+    static float pixel_width_at(const atn_camera_param& c, float d)
+    {
+        d = std::fabs(d);
+        float hfov = c.vfov * c.height / float(c.width);
+        hfov = 3.14159265358979323846F * hfov / 180.0F;
+        const float half = std::tan(hfov / 2) * d;
+        return (half * 2) / float(c.width);
+    }
+
+    // ≙ NPRPathTracing::OnRender = PathTracing::OnRender with the hooks of npr_pathtracing.cu:388-517, the per-path arithmetic of the
+    // CPU renderer (npr.cpp:101-200): one pass of the sample loop per frame (docs/NPR.md)
+    int npr_render(const atn_destination* d, atn_vec4* out_host)
+    {
+        int rc = check_ready(d);
+        if (rc) return rc;
+        if (!np_cfg.enabled) return fail(ATN_ERR_UNSUPPORTED, "feature lines are off in the scene's config (FeatureLineConfig.enabled == 0): render with atn_render");
+        if (np_stencil) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not skip through StencilType::STENCIL materials (AdvanceNPRPath)");
+        if (np_alpha) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not skip through translucent-by-alpha surfaces: alpha blending is on and a material's alpha may be < 1 (AdvanceNPRPath)");
+        if (np_carpaint) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not draw AdvanceNPRPath's extra CarPaint dimension: CarPaint materials are refused");
+        if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "NPR frames need the whole frame on one GPU (atn_set_screen_shard world 1)");
+        if (regen_mode != 0) return fail(ATN_ERR_UNSUPPORTED, "NPR frames run the serial sample loop: switch path regeneration off (atn_set_regeneration(0))");
+        if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "NPR frames have no relaxed-math kernels: atn_set_shade_math(0)");
+        if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not count rays (count_stats must be 0)");
+        ATN_HIP(hipSetDevice(device));
+        rc = begin_frame(*d, frames_in_flight > 1);
+        if (rc) return rc;
+        rc = npr_ensure(d->width, d->height, d->maxDepth);
+        if (rc) return rc;
+        if (!np_ev) ATN_HIP(hipEventCreateWithFlags(&np_ev, hipEventDisableTiming));
+        const bool prof = d->profile != 0;
+        FrameParams fp = frame_params(*d);
+        PathBuffers pb = buffers(false);
+        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
+        fp.chunk_items = plan.shade_items;
+        NprArgs na{};
+        na.disc_c = np_disc_c.p; na.disc_n = np_disc_n.p; na.desc_p = np_desc_p.p; na.desc_n = np_desc_n.p;
+        na.live = np_live.p; na.work = np_work.p; na.hpd = np_hpd.p;
+        na.ray_o = np_ray_o.p; na.ray_d = np_ray_d.p; na.ray_hit = np_ray_hit.p;
+        na.counters = np_counters.p; na.queue = np_queue.p; na.mflags = np_mflags.p;
+        for (int k = 0; k < 3; k++) na.line_color[k] = np_cfg.line_color[k];
+        na.line_width = np_cfg.line_width; na.albedo_threshold = np_cfg.albedo_threshold; na.normal_threshold = np_cfg.normal_threshold;
+        na.pixel_width = pixel_width_at(camera, 1.0F);
+        if (np_capture) { na.st_line = np_st_line.p; na.st_desc = np_st_desc.p; na.st_disc = np_st_disc.p; na.st_dims = np_st_dims.p; }
+        // the walk of the sample rays: the frame's walk, LDS copy and block, 8 rays per path
+        NprLaunch nl{};
+        nl.grid = grid_for(n_slots);
+        nl.refill = plan.refill;
+        nl.lds_bytes = plan.lds_bytes;
+        nl.trace_block = plan.refill ? (uint32_t)kTraceBlock : plan.block;
+        nl.trace_grid = plan.refill ? trace_grid(kNprRays * n_slots, true) : grid_for(kNprRays * n_slots) * (256u / plan.block);
+
+        const uint32_t g_slots = grid_for(n_slots), g_all = (n_slots + 255u) / 256u;
+        // the previous NPR frame (another bank's stream) still reads and writes the sample-ray state
+        if (np_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, np_ev, 0));
+        if (np_capture) ATN_HIP(hipMemsetAsync(np_st_line.p, 0, (size_t)d->width * d->height * sizeof(float4), stream));
+        ATN_HIP(hipMemsetAsync(counters.p, 0, (size_t)4 * counters_depth * 4, stream));
+        for (int32_t s = 0; s < d->sample; s++) {
+            fp.sample = s;
+            if (s > 0) ATN_HIP(hipMemsetAsync(pb.q_count, 0, (size_t)4 * counters_depth * 4, stream));
+            ATN_HIP(hipMemsetAsync(np_counters.p, 0, (size_t)kNprCounters * d->maxDepth * sizeof(uint32_t), stream));
+            prof_begin(prof, ATN_K_GEN);
+            hipLaunchKernelGGL(k_gen_path, dim3(g_slots), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
+            npr_launch_gen(g_slots, stream, pb, fp, na);
+            prof_end(prof);
+            for (int32_t b = 0; b <= d->maxDepth; b++) {
+                const TraceLaunch tl = trace_launch(plan, b);
+                prof_begin(prof, tl.prof_kind);
+                launch_trace_fused<false>(tl, stream, pb, scene, b - 1, b < d->maxDepth ? b : -1, b);
+                prof_end(prof);
+                if (b == d->maxDepth) break;
+                // prep, the sample rays' walk, eval: the paths a line ended leave the queue k_shade reads
+                npr_launch_bounce(nl, stream, pb, scene, fp, camera, na, b);
+                PathBuffers pbs = pb;
+                pbs.queue[b & 1] = np_queue.p;
+                prof_begin(prof, ATN_K_SHADE);
+                launch_shade<false>(plan, stream, pbs, fp, b, SvgfShade{});
+                prof_end(prof);
+                if (b == 0 && np_capture) npr_launch_capture0(g_all, stream, pb, fp, na);
+            }
+            if (d->sample > 1) {
+                prof_begin(prof, ATN_K_ACCUM);
+                hipLaunchKernelGGL(k_accumulate_sample, dim3(g_all), dim3(256), 0, stream, pb, fp);
+                prof_end(prof);
+            }
+        }
+        ATN_HIP(hipEventRecord(np_ev, stream));
+        np_pending = true;
+        np_captured = np_capture != 0;
+        rc = wait_film();
+        if (rc) return rc;
+        prof_begin(prof, ATN_K_GATHER);
+        if (d->sample == 1) hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
+        else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
+        prof_end(prof);
+        ATN_HIP(hipGetLastError());
+        rc = end_film_frame();
+        if (rc) return rc;
+        if (out_host) {
+            ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            ATN_HIP(hipStreamSynchronize(stream));
+        }
+        return ATN_OK;
+    }
+
+    // the film and the sample-ray state of a fresh context
+    int npr_reset()
+    {
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        if (np_desc_p.p) {
+            ATN_HIP(hipMemsetAsync(np_desc_p.p, 0, np_desc_p.n * sizeof(float4), stream));
+            ATN_HIP(hipMemsetAsync(np_desc_n.p, 0, np_desc_n.n * sizeof(float4), stream));
+        }
+        np_captured = false;
+        return reset();
+    }
+
+    int npr_download(int32_t which, void* out)
+    {
+        if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
+        if (!np_captured) return fail(ATN_ERR_INVALID_ARG, "the last NPR frame kept no stage buffers: atn_npr_capture(ctx, 1) before the frame");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        ATN_HIP(hipStreamSynchronize(stream));
+        const size_t n = (size_t)np_w * np_h;
+        switch (which) {
+        case 0: ATN_HIP(hipMemcpy(out, np_st_line.p, n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 1: ATN_HIP(hipMemcpy(out, np_st_desc.p, kNprRays * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 2: ATN_HIP(hipMemcpy(out, np_st_disc.p, 2 * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 3: ATN_HIP(hipMemcpy(out, np_st_dims.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
+        }
+        return fail(ATN_ERR_INVALID_ARG, "no such NPR buffer");
+    }
+
     // ≙ idaten::Renderer::reset, renderer.h:40-43
     int reset()
     {
@@ -2425,6 +2620,14 @@ int atn_restir_set_motion_depth(atn_ctx* ctx, const atn_vec4* motion_depth, uint
 int atn_restir_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return ctx->r.restir_reset(); }
 int atn_restir_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.rs_capture = on != 0; return ATN_OK; }
 int atn_restir_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.restir_download(which, out_host); }); }
+int atn_npr_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.npr_render(dst, out_host); });
+}
+int atn_npr_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.npr_reset(); }); }
+int atn_npr_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.np_capture = on != 0; return ATN_OK; }
+int atn_npr_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.npr_download(which, out_host); }); }
 int atn_svgf_denoise(atn_ctx* ctx, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host)
 {
     CTX_QUIET_OR_FAIL(ctx);

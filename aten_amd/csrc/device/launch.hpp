@@ -110,4 +110,18 @@ void restir_launch_spatial(int material_set, hipStream_t st, const PathBuffers& 
 void restir_launch_color(int material_set, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const RestirArgs& ra);
 void restir_launch_motion(hipStream_t st, const FrameParams& fp, const RestirArgs& ra);
 
+// ---- npr.hip (device/npr.hpp) ----
+struct NprArgs;
+// one bounce's NPR launches: prep and eval over the bounce's queue, the sample rays through the frame's walk (the plan's walk, LDS copy
+// and block; the grid for 8 rays per path)
+struct NprLaunch {
+    uint32_t grid;              // prep / eval blocks of 256 (grid-stride over the bounce's queue)
+    bool refill;
+    uint32_t trace_grid, trace_block, lds_bytes;
+};
+void npr_launch_gen(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const NprArgs& na);
+void npr_launch_bounce(const NprLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                       const atn_camera_param& cam, const NprArgs& na, int32_t bounce);
+void npr_launch_capture0(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const NprArgs& na);
+
 } // namespace atn

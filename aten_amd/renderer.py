@@ -312,6 +312,47 @@ class PathTracing:
         self._check(self._l.atn_restir_download(self._ctx, which, out.ctypes.data))
         return out
 
+    # ---- NPR feature lines (idaten::NPRPathTracing / aten::NprPathTracer; docs/NPR.md)
+    def npr_render(self, width, height, max_depth=5, rr_depth=3, spp=1, frame=0, progressive=True, break_on_terminate=True,
+                   download=True, profile=False):
+        """One frame with feature lines (the scene's FeatureLineConfig must be enabled) into the film; returns the film [h, w, 4]."""
+        d = Destination(width, height, max_depth, rr_depth, spp, frame, int(progressive), int(break_on_terminate), 0, int(profile))
+        out = np.empty((height, width, 4), np.float32) if download else None
+        self._check(self._l.atn_npr_render(self._ctx, C.byref(d), out.ctypes.data if download else None))
+        self.width, self.height = width, height
+        return out
+
+    def npr_reset(self):
+        """Film and sample-ray state of a fresh context."""
+        self._check(self._l.atn_npr_reset(self._ctx))
+
+    def npr_capture(self, on=True):
+        """Keep the stage buffers (line decision, sample-ray descriptors, disc, CMJ dimension) of the next frames for npr_buffer."""
+        self._check(self._l.atn_npr_capture(self._ctx, int(on)))
+
+    def npr_buffer(self, name):
+        """The last NPR frame's stage buffers (needs npr_capture).  'line': dict found (bool), bounce (int32), distance [h, w];
+        'desc': dict u, v, live [h, w, 8] after bounce 0; 'disc': dict center [h, w, 3], radius, normal [h, w, 3], acc after
+        bounce 0; 'dims': uint32 [h, w], the CMJ dimension after bounce 0."""
+        w, h = self.width, self.height
+        if name == "line":
+            out = np.empty((h, w, 4), np.float32)
+            self._check(self._l.atn_npr_download(self._ctx, 0, out.ctypes.data))
+            return dict(found=out[..., 0] != 0, bounce=out[..., 1].astype(np.int32), distance=out[..., 2].copy())
+        if name == "desc":
+            out = np.empty((h, w, 8, 4), np.float32)
+            self._check(self._l.atn_npr_download(self._ctx, 1, out.ctypes.data))
+            return dict(u=out[..., 0].copy(), v=out[..., 1].copy(), live=out[..., 2] != 0)
+        if name == "disc":
+            out = np.empty((h, w, 2, 4), np.float32)
+            self._check(self._l.atn_npr_download(self._ctx, 2, out.ctypes.data))
+            return dict(center=out[..., 0, :3].copy(), radius=out[..., 0, 3].copy(), normal=out[..., 1, :3].copy(), acc=out[..., 1, 3].copy())
+        if name == "dims":
+            out = np.empty((h, w), np.uint32)
+            self._check(self._l.atn_npr_download(self._ctx, 3, out.ctypes.data))
+            return out
+        raise ValueError("no NPR buffer %r" % (name,))
+
     def svgf_denoise(self, width, height, frame=0, compute_motion=False, stages=False, download=True, profile=False):
         """The filter passes of OnRender on the buffers as they stand (svgf_upload / a previous path pass)."""
         d = Destination(width, height, 1, 1, 1, frame, 0, 1, 0, int(profile))

@@ -36,6 +36,23 @@ def _length3(x, y, z):
     return np.sqrt((x * x + y * y) + z * z, dtype=F32)
 
 
+# aten::FeatureLineMetricFlag (material/material.h:230-235)
+FEATURE_LINE_MESH, FEATURE_LINE_ALBEDO, FEATURE_LINE_NORMAL, FEATURE_LINE_DEPTH = 1, 2, 4, 8
+FEATURE_LINE_ALL = 15
+
+
+def write_feature_line_config(config, enabled, color=(0.0, 0.0, 0.0), width=1.0, albedo_threshold=0.1, normal_threshold=0.1):
+    """atn_feature_line_config (28 B: enabled, pad 3, line_color[3], line_width, albedo_threshold, normal_threshold) into the
+    `feature_line` bytes of a SceneRenderingConfig."""
+    b = struct.pack("<B3x3ffff", 1 if enabled else 0, *[float(c) for c in color], float(width), float(albedo_threshold), float(normal_threshold))
+    C.memmove(C.addressof(config) + L.SceneRenderingConfig.feature_line.offset, b, len(b))
+
+
+def write_feature_line_mtrl(m, enable, metric_flag):
+    """atn_feature_line_mtrl (8 B: enable, pad 3, int32 metric_flag) into a MATERIAL_PARAM record's `feature_line` bytes."""
+    m["feature_line"] = np.frombuffer(struct.pack("<B3xi", 1 if enable else 0, int(metric_flag)), np.uint8)
+
+
 class FlatScene:
     """Owns the numpy arrays behind an atn_scene_desc."""
 
@@ -120,7 +137,14 @@ class SceneBuilder:
         self.config.bg.enable_env_map = 1
 
     # ---------------------------------------------------------------- materials / textures
-    def add_material(self, name, mtype, base_color, albedo_map=-1, normal_map=-1, roughness_map=-1, **std):
+    def set_feature_line(self, enabled, color=(0.0, 0.0, 0.0), width=1.0, albedo_threshold=0.1, normal_threshold=0.1):
+        """aten::FeatureLineConfig (renderer/npr/feature_line_config.h:7-13): bytes 4-31 of the scene rendering config.  Lines are
+        drawn by PathTracing.npr_render; a builder that never calls this leaves the bytes zero (lines off)."""
+        write_feature_line_config(self.config, enabled, color, width, albedo_threshold, normal_threshold)
+
+    def add_material(self, name, mtype, base_color, albedo_map=-1, normal_map=-1, roughness_map=-1, feature_line=(0, 0), **std):
+        """feature_line = (enable, metric_flag): aten::FeatureLineMtrlConfig, bytes 240-247 (material.h:237-240).  The default
+        (0, 0) keeps the bytes zero -- the reference's own defaults are enable = 1, metric_flag = 15 (FEATURE_LINE_ALL)."""
         m = np.zeros((), L.MATERIAL_PARAM)
         bc = list(base_color)
         m["baseColor"] = (bc + [0.0])[:4] if len(bc) == 3 else bc      # vec4 = vec3 -> w = 0 (vec4.h:135-141 keeps w)
@@ -136,6 +160,7 @@ class SceneBuilder:
         m["standard"] = [s[k] for k in L.STANDARD_FIELDS]
         m["medium"][3] = np.int32(-1).view(F32)     # MediumParameter.grid_idx = -1
         m["medium"][4] = -1.0                       # majorant
+        write_feature_line_mtrl(m, *feature_line)
         self.materials.append((name, m))
         return len(self.materials) - 1
 
@@ -155,13 +180,14 @@ class SceneBuilder:
         return mid
 
     def add_toon_material(self, name, base_color, stylized=False, toon_type=None, target_light_idx=-1, remap_texture=-1,
-                          albedo_map=-1, normal_map=-1, **p):
+                          albedo_map=-1, normal_map=-1, feature_line=(0, 0), **p):
         """aten::Toon / aten::StylizedBrdf (material/toon.h:20-34,80-90): ToonParameter with the defaults of material.h:124-161,
-        attrib = Diffuse's or Microfacet's by toon_type.  `p`: roughness / ior (standard part) and any TOON_PARAM field."""
+        attrib = Diffuse's or Microfacet's by toon_type.  `p`: roughness / ior (standard part) and any TOON_PARAM field.
+        feature_line: as add_material."""
         toon_type = L.MTRL_DIFFUSE if toon_type is None else toon_type
         std = {k: p.pop(k) for k in list(p) if k in L.STANDARD_FIELDS}
         mid = self.add_material(name, L.MTRL_STYLIZED if stylized else L.MTRL_TOON, base_color, albedo_map=albedo_map,
-                                normal_map=normal_map, **std)
+                                normal_map=normal_map, feature_line=feature_line, **std)
         m = self.materials[mid][1]
         m["attrib"] = 0 if toon_type == L.MTRL_DIFFUSE else L.ATTR_GLOSSY
         t = m["toon"]

@@ -502,3 +502,29 @@ def toon_room(asset_dir=None, target="point", screen_shadow=None, alpha_blocker=
     b.set_background((0.0, 0.0, 0.0))
     cam = dict(pos=(0.0, 1.0, 3.0), at=(0.0, 1.0, 0.0), vfov=45.0)
     return b.build(), cam
+
+
+def with_feature_lines(scene, enabled=True, color=(0.0, 0.0, 0.0), width=1.5, albedo_threshold=0.1, normal_threshold=0.1,
+                       materials=None, metric_flag=15):
+    """A built scene with feature lines (PathTracing.npr_render): FeatureLineConfig in the scene rendering config and
+    FeatureLineMtrlConfig = (1, metric_flag) on the materials named by index in `materials` (None = all; [] = none).  Writes the
+    same bytes SceneBuilder.set_feature_line / add_material(feature_line=...) write."""
+    from .builder import write_feature_line_config, write_feature_line_mtrl
+    fs, cam = scene
+    write_feature_line_config(fs.desc.config, enabled, color, width, albedo_threshold, normal_threshold)
+    mats = fs.arrays["materials"]
+    for i in range(len(mats)):
+        on = materials is None or i in materials
+        write_feature_line_mtrl(mats[i], 1 if on else 0, metric_flag if on else 0)
+    return fs, cam
+
+
+def npr_room(asset_dir=None, **lines):
+    """toon_room (point target light, no stylized shadow) with black feature lines on every material."""
+    return with_feature_lines(toon_room(asset_dir), **lines)
+
+
+def npr_sponza(asset_dir=None, **lines):
+    """sponza_lod with GGX materials -- glossy, so sample rays keep bouncing -- and black feature lines on every material: the NPR
+    benchmark scene."""
+    return with_feature_lines(sponza_lod(asset_dir), **lines)

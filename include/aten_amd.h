@@ -357,6 +357,25 @@ int atn_restir_set_motion_depth(atn_ctx* ctx, const atn_vec4* motion_depth, uint
 int atn_restir_reset(atn_ctx* ctx);
 int atn_restir_capture(atn_ctx* ctx, int32_t on);
 int atn_restir_download(atn_ctx* ctx, int32_t which, void* out_host);
+
+/* ---- NPR feature lines (aten::NprPathTracer / idaten::NPRPathTracing; docs/NPR.md) ------------------------------------------
+ * The path tracer's sample loop with 8 sample rays per path that find feature lines (mesh, albedo, normal and depth edges) around
+ * the path's query ray; a found line sets the path's contribution to the MIS-weighted line colour and ends the path.  Settings:
+ * atn_scene_rendering_config.feature_line (atn_feature_line_config) and atn_material_param.feature_line (atn_feature_line_mtrl).
+ *   atn_npr_render: one frame; the film follows atn_render's progressive / overwrite rules.  ATN_ERR_UNSUPPORTED for a config
+ *                   with feature lines off, StencilType::STENCIL materials, alpha blending with a material whose alpha may be < 1,
+ *                   CarPaint materials, a screen shard with world > 1, path regeneration, relaxed shade math and count_stats.
+ *   atn_npr_reset: the film and the sample-ray state start over (a fresh context's)
+ *   atn_npr_capture: keep the stage buffers of the next frames (tests)
+ *   atn_npr_download: which = 0 the line decision per pixel, atn_vec4[w*h] {found, bounce, closest distance, 0} of the frame's
+ *                     last sample that found one; 1 the sample-ray descriptors after bounce 0, atn_vec4[w*h][8] {u, v, live, 0};
+ *                     2 the disc after bounce 0, atn_vec4[w*h][2] {center, radius} {normal, accumulated distance}; 3 the CMJ
+ *                     dimension after bounce 0, uint32[w*h].  All for a frame rendered with capture on.
+ * Additive entry points: atn_abi_version stays 3. */
+int atn_npr_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host);
+int atn_npr_reset(atn_ctx* ctx);
+int atn_npr_capture(atn_ctx* ctx, int32_t on);
+int atn_npr_download(atn_ctx* ctx, int32_t which, void* out_host);
 /* The filter passes alone (everything of OnRender after the sample loop, svgf.cpp:515-637) on whatever the
  * path pass -- or atn_svgf_upload -- left in the buffers: contributions (which = 14: contrib.xyz, sample count),
  * the current AOVs (0, 1), primary hit positions (10), motion/depth (9).  This is how a caller that already has a

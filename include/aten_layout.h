@@ -195,6 +195,26 @@ typedef struct atn_scene_rendering_config {
     atn_background bg;                    /* 40 */
 } atn_scene_rendering_config;
 
+/* Typed views of the NPR bytes (atn_npr_render; the byte members above stay as they are):
+ * aten::FeatureLineConfig, 28 B (renderer/npr/feature_line_config.h:7-13) = atn_scene_rendering_config.feature_line, and
+ * aten::FeatureLineMtrlConfig, 8 B (material/material.h:237-240) = atn_material_param.feature_line.  The reference's member
+ * defaults are enabled = 0 / line_width = 1 / thresholds 0.1 and enable = 1 / metric_flag = 15; zero bytes here mean "off". */
+typedef struct atn_feature_line_config {
+    uint8_t enabled; uint8_t _pad[3];     /*  0 */
+    float line_color[3];                  /*  4 */
+    float line_width;                     /* 16: in pixels */
+    float albedo_threshold;               /* 20 */
+    float normal_threshold;               /* 24 */
+} atn_feature_line_config;
+#define ATN_FEATURE_LINE_MESH   0x1     /* FeatureLineMetricFlag, material.h:230-235 */
+#define ATN_FEATURE_LINE_ALBEDO 0x2
+#define ATN_FEATURE_LINE_NORMAL 0x4
+#define ATN_FEATURE_LINE_DEPTH  0x8
+typedef struct atn_feature_line_mtrl {
+    uint8_t enable; uint8_t _pad[3];      /*  0 */
+    int32_t metric_flag;                  /*  4 */
+} atn_feature_line_mtrl;
+
 /* ---- aten::Intersection, 32 B (src/libaten/scene/hit_parameter.h:28-64) */
 typedef struct atn_intersection {
     float t;
@@ -287,6 +307,14 @@ static_assert(offsetof(atn_camera_param, dist) == 100, "CameraParameter.dist");
 static_assert(sizeof(atn_scene_rendering_config) == 68, "SceneRenderingConfig");
 static_assert(offsetof(atn_scene_rendering_config, bvh_hit_min) == 32, "SceneRenderingConfig.bvh_hit_min");
 static_assert(offsetof(atn_scene_rendering_config, bg) == 40, "SceneRenderingConfig.bg");
+static_assert(sizeof(atn_feature_line_config) == 28, "FeatureLineConfig");
+static_assert(offsetof(atn_feature_line_config, line_color) == 4 && offsetof(atn_feature_line_config, line_width) == 16
+              && offsetof(atn_feature_line_config, albedo_threshold) == 20 && offsetof(atn_feature_line_config, normal_threshold) == 24,
+              "FeatureLineConfig members");
+static_assert(sizeof(atn_feature_line_mtrl) == 8 && offsetof(atn_feature_line_mtrl, metric_flag) == 4, "FeatureLineMtrlConfig");
+static_assert(sizeof(((atn_scene_rendering_config*)0)->feature_line) == sizeof(atn_feature_line_config)
+              && offsetof(atn_scene_rendering_config, feature_line) == 4, "SceneRenderingConfig.feature_line");
+static_assert(sizeof(((atn_material_param*)0)->feature_line) == sizeof(atn_feature_line_mtrl), "MaterialParameter.feature_line");
 static_assert(sizeof(atn_intersection) == 32, "Intersection");
 static_assert(sizeof(atn_ray) == 24, "ray");
 #endif

@@ -105,10 +105,11 @@ def build_host(force=False):
 #   regen.hip         -fno-slp-vectorize  (the path-regeneration kernels: same sources and flags as aten_amd.hip's, compiled beside them)
 #   restir.hip        -fno-slp-vectorize  (the ReSTIR kernels, device/restir.hpp)
 #   npr.hip           -fno-slp-vectorize  (the NPR feature-line kernels, device/npr.hpp)
+#   volume.hip        -fno-slp-vectorize  (the volume path tracer's kernels, device/volume.hpp)
 #   shade_relaxed.hip  k_shade with the reference GPU build's --use_fast_math rules (opt-in, atn_set_shade_math): contraction, approximate
 #                      division / sqrt, flushed denormals (the unit itself redirects sinf / cosf / expf / logf / powf to the hardware forms)
 RELAXED_FLAGS = ["-fno-slp-vectorize", "-ffp-contract=fast", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero"]
-HIP_UNITS = [("aten_amd.hip", ["-fno-slp-vectorize"]), ("regen.hip", ["-fno-slp-vectorize"]), ("restir.hip", ["-fno-slp-vectorize"]), ("npr.hip", ["-fno-slp-vectorize"]), ("shade_relaxed.hip", RELAXED_FLAGS), ("svgf_atrous.hip", [])]
+HIP_UNITS = [("aten_amd.hip", ["-fno-slp-vectorize"]), ("regen.hip", ["-fno-slp-vectorize"]), ("restir.hip", ["-fno-slp-vectorize"]), ("npr.hip", ["-fno-slp-vectorize"]), ("volume.hip", ["-fno-slp-vectorize"]), ("shade_relaxed.hip", RELAXED_FLAGS), ("svgf_atrous.hip", [])]
 
 
 def hip_compile(out_lib, extra_flags=(), objdir=None, hipcc=None):

@@ -21,6 +21,7 @@
 #include "device/svgf.hpp"
 #include "device/restir.hpp"
 #include "device/npr.hpp"
+#include "device/volume.hpp"
 #include "device/lbvh.hpp"
 #include "host/scene_upload.hpp"
 #include "host/ibl_precompute.hpp"
@@ -747,6 +748,7 @@ public:
         scene.mtx_quads = (uint32_t)img.matrices.size();
         has_scene = true;
         { const int nrc = npr_decode(s, img); if (nrc) return nrc; }
+        { const int vrc = vol_decode(s, img); if (vrc) return vrc; }
         env_host.clear(); env_w = env_h = 0; ibl_tables_ready = false;
         {
             const int32_t ei = s->config.bg.envmap_tex_idx;
@@ -2335,6 +2337,209 @@ public:
         return fail(ATN_ERR_INVALID_ARG, "no such NPR buffer");
     }
 
+    // ------------------------------------------------------------------------------------------------
+    // Volume rendering (aten::VolumePathTracing::radiance / Nee, device/volume.hpp; docs/VOLUME.md): per-slot medium stack and
+    // connection records, and what the upload decoded of is_medium / type / MediumParameter (read by the volume kernels only)
+    // ------------------------------------------------------------------------------------------------
+    DevBuf<VolMedium> vl_med;
+    DevBuf<uint4> vl_stack, vl_c_stack, vl_st_state, vl_st_stack;
+    DevBuf<uint32_t> vl_meta, vl_conn_q, vl_counters;
+    DevBuf<float> vl_hit_t;
+    DevBuf<float4> vl_ev_o, vl_ev_d, vl_c_o, vl_c_d, vl_c_w, vl_c_a, vl_c_b, vl_c_c, vl_st_ray, vl_st_conn;
+    DevBuf<uint2> vl_segs;
+    std::string vl_refuse;          // why the uploaded scene's media cannot be rendered ("" = they can)
+    bool vl_stencil = false, vl_alpha = false, vl_carpaint = false, vl_toon = false;
+    float vl_eps_bias = 0.0F;
+    uint32_t vl_slots = 0;
+    int32_t vl_w = 0, vl_h = 0, vl_capture = -1, vl_captured = -1;
+    bool vl_rendered = false, vl_pending = false;
+    hipEvent_t vl_ev = nullptr;     // the last volume frame's kernels are done with the per-slot state (the next frame waits for it)
+
+    int vol_decode(const atn_scene_desc* s, const HostSceneImage& img)
+    {
+        std::vector<VolMedium> med((size_t)s->n_materials + 1, VolMedium{});       // (+ the white-diffuse fallback: no medium)
+        vl_refuse.clear();
+        vl_stencil = vl_carpaint = vl_toon = false;
+        bool maybe_alpha = false;
+        for (uint32_t i = 0; i < s->n_materials; i++) {
+            const atn_material_param& m = s->materials[i];
+            if (m.stencil_type == 2) vl_stencil = true;         // StencilType::STENCIL
+            if (m.type == ATN_MTRL_CARPAINT) vl_carpaint = true;
+            if (m.type == ATN_MTRL_TOON || m.type == ATN_MTRL_STYLIZED_BRDF) vl_toon = true;
+            if (!m.is_medium) continue;
+            atn_medium_param mp;
+            std::memcpy(&mp, m.medium, sizeof(mp));
+            VolMedium& v = med[i];
+            v.g = mp.phase_function_g; v.sigma_a = mp.sigma_a; v.sigma_s = mp.sigma_s;
+            v.flags = kVolMediumFlag | (m.type == ATN_MTRL_VOLUME ? kVolPureFlag : 0u);
+            v.le[0] = mp.le[0]; v.le[1] = mp.le[1]; v.le[2] = mp.le[2];
+            v.sigma_t = mp.sigma_a + mp.sigma_s;
+            if (!vl_refuse.empty()) continue;
+            if (mp.grid_idx >= 0) vl_refuse = "material " + std::to_string(i) + " is a heterogeneous medium (grid_idx >= 0): NanoVDB grids are not supported";
+            else if (!(mp.sigma_a + mp.sigma_s > 0.0F)) vl_refuse = "material " + std::to_string(i) + " is a medium with sigma_a + sigma_s <= 0";
+            else if ((uint32_t)m.id != i) vl_refuse = "material " + std::to_string(i) + " is a medium whose id is not its index (the medium stack holds material ids)";
+        }
+        for (const DevMaterial& dm : img.materials) if (dm.attrib & kAttrMaybeAlpha) maybe_alpha = true;
+        vl_alpha = s->config.enable_alpha_blending != 0 && maybe_alpha;
+        vl_eps_bias = s->config.epsilon_bias_for_traversing_shadow_ray_in_medium;
+        ATN_HIP(vl_med.upload(med, stream));
+        return ATN_OK;
+    }
+
+    int vol_ensure(int32_t w, int32_t h)
+    {
+        if (n_slots != vl_slots) {
+            const size_t n = n_slots;
+            ATN_HIP(vl_stack.resize(n)); ATN_HIP(vl_meta.resize(n)); ATN_HIP(vl_hit_t.resize(n)); ATN_HIP(vl_ev_o.resize(n)); ATN_HIP(vl_ev_d.resize(n));
+            ATN_HIP(vl_c_o.resize(n)); ATN_HIP(vl_c_d.resize(n)); ATN_HIP(vl_c_w.resize(n)); ATN_HIP(vl_c_a.resize(n)); ATN_HIP(vl_c_b.resize(n));
+            ATN_HIP(vl_c_c.resize(n)); ATN_HIP(vl_c_stack.resize(n)); ATN_HIP(vl_conn_q.resize(n)); ATN_HIP(vl_segs.resize(n));
+            vl_slots = n_slots;
+        }
+        ATN_HIP(vl_counters.resize(kVolCounters));
+        if (vl_capture >= 0) {
+            const size_t n = (size_t)w * h;
+            ATN_HIP(vl_st_state.resize(n)); ATN_HIP(vl_st_stack.resize(n)); ATN_HIP(vl_st_ray.resize(2 * n)); ATN_HIP(vl_st_conn.resize(3 * n));
+        }
+        vl_w = w; vl_h = h;
+        return ATN_OK;
+    }
+
+    // ≙ VolumePathTracing::OnRender (volume_pathtracing.cpp:436-533) in idaten::VolumeRendering's wavefront shape: per sample, 8
+    // iterations of closest hit, shade and connection walk -- a fixed number of launches, nothing is read back
+    int volume_render(const atn_destination* d, atn_vec4* out_host)
+    {
+        int rc = check_ready(d);
+        if (rc) return rc;
+        if (!vl_refuse.empty()) return fail(ATN_ERR_UNSUPPORTED, ("volume frames: " + vl_refuse).c_str());
+        if (vl_stencil) return fail(ATN_ERR_UNSUPPORTED, "volume frames do not skip through StencilType::STENCIL materials");
+        if (vl_alpha) return fail(ATN_ERR_UNSUPPORTED, "volume frames do not skip through translucent-by-alpha surfaces: alpha blending is on and a material's alpha may be < 1");
+        if (vl_carpaint) return fail(ATN_ERR_UNSUPPORTED, "volume frames do not draw CarPaint's extra dimension: CarPaint materials are refused");
+        if (vl_toon) return fail(ATN_ERR_UNSUPPORTED, "volume frames do not shade Toon / Stylized materials");
+        if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "volume frames need the whole frame on one GPU (atn_set_screen_shard world 1)");
+        if (regen_mode != 0) return fail(ATN_ERR_UNSUPPORTED, "volume frames run the serial sample loop: switch path regeneration off (atn_set_regeneration(0))");
+        if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "volume frames have no relaxed-math kernels: atn_set_shade_math(0)");
+        if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "volume frames do not count rays (count_stats must be 0)");
+        if (d->maxDepth > 254) return fail(ATN_ERR_UNSUPPORTED, "volume frames keep depth_count in 8 bits (maxDepth <= 254)");
+        ATN_HIP(hipSetDevice(device));
+        rc = begin_frame(*d, frames_in_flight > 1);
+        if (rc) return rc;
+        rc = vol_ensure(d->width, d->height);
+        if (rc) return rc;
+        if (!vl_ev) ATN_HIP(hipEventCreateWithFlags(&vl_ev, hipEventDisableTiming));
+        const bool prof = d->profile != 0;
+        FrameParams fp = frame_params(*d);
+        PathBuffers pb = buffers(false);
+        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
+        const VolLaunch vlc = vol_launch(plan, n_slots, grid_for(n_slots), grid_for(n_slots));
+        VolArgs va{};
+        va.med = vl_med.p; va.stack = vl_stack.p; va.meta = vl_meta.p; va.hit_t = vl_hit_t.p; va.ev_o = vl_ev_o.p; va.ev_d = vl_ev_d.p;
+        va.c_o = vl_c_o.p; va.c_d = vl_c_d.p; va.c_w = vl_c_w.p; va.c_a = vl_c_a.p; va.c_b = vl_c_b.p; va.c_c = vl_c_c.p; va.c_stack = vl_c_stack.p;
+        va.conn_q = vl_conn_q.p; va.segs = vl_segs.p; va.counters = vl_counters.p; va.eps_bias = vl_eps_bias;
+        va.capture = vl_capture;
+        if (vl_capture >= 0) { va.st_state = vl_st_state.p; va.st_stack = vl_st_stack.p; va.st_ray = vl_st_ray.p; va.st_conn = vl_st_conn.p; }
+        // the iteration's queue counters are the volume renderer's own (9 entries: the frame's are sized by maxDepth)
+        pb.q_count = vl_counters.p + kVolCntQueue;
+
+        const uint32_t g_slots = grid_for(n_slots), g_all = (n_slots + 255u) / 256u;
+        // the previous volume frame (another bank's stream) still reads and writes the per-slot state
+        if (vl_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, vl_ev, 0));
+        if (vl_capture >= 0) {
+            const size_t n = (size_t)d->width * d->height;
+            ATN_HIP(hipMemsetAsync(vl_st_state.p, 0, n * sizeof(uint4), stream)); ATN_HIP(hipMemsetAsync(vl_st_stack.p, 0, n * sizeof(uint4), stream));
+            ATN_HIP(hipMemsetAsync(vl_st_ray.p, 0, 2 * n * sizeof(float4), stream)); ATN_HIP(hipMemsetAsync(vl_st_conn.p, 0, 3 * n * sizeof(float4), stream));
+        }
+        ATN_HIP(hipMemsetAsync(vl_counters.p, 0, (size_t)kVolCounters * sizeof(uint32_t), stream));
+        for (int32_t s = 0; s < d->sample; s++) {
+            fp.sample = s;
+            if (s > 0) ATN_HIP(hipMemsetAsync(vl_counters.p, 0, (size_t)kVolCntFrame * sizeof(uint32_t), stream));
+            prof_begin(prof, ATN_K_GEN);
+            hipLaunchKernelGGL(k_gen_path, dim3(g_slots), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
+            vol_launch_begin(vlc, stream, fp, va);
+            prof_end(prof);
+            for (int32_t it = 0; it < kVolIterations; it++) {
+                prof_begin(prof, ATN_K_TRACE_CLOSEST);
+                vol_launch_closest(vlc, stream, pb, scene, va, it);
+                prof_end(prof);
+                prof_begin(prof, ATN_K_SHADE);
+                vol_launch_shade(scene.material_set, vlc, stream, pb, scene, fp, camera, va, it);
+                prof_end(prof);
+                prof_begin(prof, ATN_K_TRACE_FUSED);
+                vol_launch_transmit(vlc, stream, pb, scene, va, it);
+                prof_end(prof);
+            }
+            if (d->sample > 1) {
+                prof_begin(prof, ATN_K_ACCUM);
+                hipLaunchKernelGGL(k_accumulate_sample, dim3(g_all), dim3(256), 0, stream, pb, fp);
+                prof_end(prof);
+            }
+        }
+        vol_launch_reduce(vlc, stream, fp, va);
+        ATN_HIP(hipEventRecord(vl_ev, stream));
+        vl_pending = true;
+        vl_captured = vl_capture;
+        vl_rendered = true;
+        rc = wait_film();
+        if (rc) return rc;
+        prof_begin(prof, ATN_K_GATHER);
+        if (d->sample == 1) hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
+        else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
+        prof_end(prof);
+        ATN_HIP(hipGetLastError());
+        rc = end_film_frame();
+        if (rc) return rc;
+        if (out_host) {
+            ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            ATN_HIP(hipStreamSynchronize(stream));
+        }
+        return ATN_OK;
+    }
+
+    int volume_reset()
+    {
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        vl_captured = -1; vl_rendered = false;
+        return reset();
+    }
+
+    int volume_download(int32_t which, void* out)
+    {
+        if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
+        if (!vl_rendered) return fail(ATN_ERR_INVALID_ARG, "no volume frame has been rendered");
+        if (which != 4 && vl_captured < 0) return fail(ATN_ERR_INVALID_ARG, "the last volume frame kept no stage buffers: atn_volume_capture(ctx, iteration) before the frame");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        ATN_HIP(hipStreamSynchronize(stream));
+        const size_t n = (size_t)vl_w * vl_h;
+        switch (which) {
+        case 0: ATN_HIP(hipMemcpy(out, vl_st_state.p, n * sizeof(uint4), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 1: ATN_HIP(hipMemcpy(out, vl_st_stack.p, n * sizeof(uint4), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 2: ATN_HIP(hipMemcpy(out, vl_st_ray.p, 2 * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 3: ATN_HIP(hipMemcpy(out, vl_st_conn.p, 3 * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 4: ATN_HIP(hipMemcpy(out, vl_counters.p + kVolCntFrame, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
+        }
+        return fail(ATN_ERR_INVALID_ARG, "no such volume buffer");
+    }
+
+    int volume_phase_table(float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo, float* out_dir, float* out_eval)
+    {
+        if (!n || !w || !r1 || !r2 || !wo || !out_dir || !out_eval) return fail(ATN_ERR_INVALID_ARG, "null argument / no cases");
+        ATN_HIP(hipSetDevice(device));
+        DevBuf<float> dw, d1, d2, dwo, dd, de;
+        ATN_HIP(dw.resize(3 * (size_t)n)); ATN_HIP(d1.resize(n)); ATN_HIP(d2.resize(n)); ATN_HIP(dwo.resize(3 * (size_t)n));
+        ATN_HIP(dd.resize(3 * (size_t)n)); ATN_HIP(de.resize(n));
+        ATN_HIP(hipMemcpyAsync(dw.p, w, 12 * (size_t)n, hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipMemcpyAsync(d1.p, r1, 4 * (size_t)n, hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipMemcpyAsync(d2.p, r2, 4 * (size_t)n, hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipMemcpyAsync(dwo.p, wo, 12 * (size_t)n, hipMemcpyHostToDevice, stream));
+        vol_launch_phase_table(stream, g, n, dw.p, d1.p, d2.p, dwo.p, dd.p, de.p);
+        ATN_HIP(hipGetLastError());
+        ATN_HIP(hipMemcpyAsync(out_dir, dd.p, 12 * (size_t)n, hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipMemcpyAsync(out_eval, de.p, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        return ATN_OK;
+    }
+
     // ≙ idaten::Renderer::reset, renderer.h:40-43
     int reset()
     {
@@ -2628,6 +2833,25 @@ int atn_npr_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host)
 int atn_npr_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.npr_reset(); }); }
 int atn_npr_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.np_capture = on != 0; return ATN_OK; }
 int atn_npr_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.npr_download(which, out_host); }); }
+int atn_volume_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.volume_render(dst, out_host); });
+}
+int atn_volume_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.volume_reset(); }); }
+int atn_volume_capture(atn_ctx* ctx, int32_t iteration)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    if (iteration >= atn::kVolIterations) return ctx->r.fail(ATN_ERR_INVALID_ARG, "a path runs 8 iterations: capture 0..7, or < 0 for none");
+    ctx->r.vl_capture = iteration < 0 ? -1 : iteration;
+    return ATN_OK;
+}
+int atn_volume_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.volume_download(which, out_host); }); }
+int atn_volume_phase_table(atn_ctx* ctx, float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo, float* out_dir, float* out_eval)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.volume_phase_table(g, n, w, r1, r2, wo, out_dir, out_eval); });
+}
 int atn_svgf_denoise(atn_ctx* ctx, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host)
 {
     CTX_QUIET_OR_FAIL(ctx);

@@ -124,4 +124,31 @@ void npr_launch_bounce(const NprLaunch& l, hipStream_t st, const PathBuffers& pb
                        const atn_camera_param& cam, const NprArgs& na, int32_t bounce);
 void npr_launch_capture0(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const NprArgs& na);
 
+// ---- volume.hip (device/volume.hpp) ----
+struct VolArgs;
+// one iteration's volume launches: the closest-hit walk and the connection walk through the frame's walk (the plan's walk, LDS copy and
+// block; one job per path), the shade over the iteration's queue
+struct VolLaunch {
+    uint32_t grid;              // shade blocks of 256 (grid-stride over the iteration's queue)
+    uint32_t slot_grid;         // blocks of 256 over all slots (begin, reduce)
+    bool refill;
+    uint32_t trace_grid, trace_block, lds_bytes;
+};
+inline VolLaunch vol_launch(const PassPlan& p, uint32_t n_slots, uint32_t shade_grid, uint32_t plain_trace_grid)
+{
+    VolLaunch l{};
+    l.grid = shade_grid; l.slot_grid = (n_slots + 255u) / 256u;
+    l.refill = p.refill; l.lds_bytes = p.lds_bytes;
+    l.trace_block = p.refill ? (uint32_t)kTraceBlock : p.block;
+    l.trace_grid = p.refill ? p.trace_grid : plain_trace_grid * (256u / p.block);
+    return l;
+}
+void vol_launch_begin(const VolLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va);
+void vol_launch_closest(const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it);
+void vol_launch_shade(int material_set, const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                      const atn_camera_param& cam, const VolArgs& va, int32_t it);
+void vol_launch_transmit(const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it);
+void vol_launch_reduce(const VolLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va);
+void vol_launch_phase_table(hipStream_t st, float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo, float* out_dir, float* out_eval);
+
 } // namespace atn

@@ -89,6 +89,7 @@ OBJ_POLYGONS, OBJ_INSTANCE, OBJ_SPHERE = 0, 1, 2
  MTRL_BECKMAN, MTRL_VELVET, MTRL_MICROFACET_REFRACTION, MTRL_RETROREFLECTIVE, MTRL_CARPAINT,
  MTRL_DISNEY, MTRL_TOON, MTRL_STYLIZED) = range(14)
 MTRL_TOON_SPECULAR = 16
+MTRL_VOLUME = 15        # MaterialType::Volume: a pure medium boundary (material.cpp:212-232)
 ATTR_EMISSIVE, ATTR_SINGULAR, ATTR_TRANSLUCENT, ATTR_GLOSSY = 1, 2, 4, 8
 # aten::MaterialAttribute* constants, src/libaten/material/material.h:34-39
 MTRL_ATTRIB = {

@@ -353,6 +353,70 @@ class PathTracing:
             return out
         raise ValueError("no NPR buffer %r" % (name,))
 
+    # ---- volume rendering: path tracing through homogeneous media (aten::VolumePathTracing; docs/VOLUME.md)
+    def volume_render(self, width, height, max_depth=5, rr_depth=3, spp=1, frame=0, progressive=True, break_on_terminate=True,
+                      download=True, profile=False):
+        """One frame through the scene's media (materials with is_medium set) into the film; returns the film [h, w, 4]."""
+        d = Destination(width, height, max_depth, rr_depth, spp, frame, int(progressive), int(break_on_terminate), 0, int(profile))
+        out = np.empty((height, width, 4), np.float32) if download else None
+        self._check(self._l.atn_volume_render(self._ctx, C.byref(d), out.ctypes.data if download else None))
+        self.width, self.height = width, height
+        return out
+
+    def volume_reset(self):
+        """The film of a fresh context."""
+        self._check(self._l.atn_volume_reset(self._ctx))
+
+    def volume_capture(self, iteration=0):
+        """Keep the per-pixel state after `iteration` (0..7) of sample 0 of the next frames for volume_buffer; None or < 0: off."""
+        self._check(self._l.atn_volume_capture(self._ctx, -1 if iteration is None else int(iteration)))
+
+    def volume_buffer(self, name):
+        """The last volume frame's stage buffers (needs volume_capture, except 'counters').  'state': dict of bool [h, w] processed,
+        hit, sampled, absorbed, scattered, passed, connection, terminated and int32 depth_count, stack_size, uint32 dim;
+        'stack': int32 [h, w, 8], the medium stack in the order entered (entries beyond stack_size are 0);
+        'ray': dict org [h, w, 3], dir [h, w, 3], s, hit_t; 'conn': dict org, dir, t_max, transmittance, segments (int32), visible;
+        'counters': dict stack_overflow, walk_overflow, connections, segments of the last frame."""
+        w, h = self.width, self.height
+        if name == "counters":
+            out = np.zeros(4, np.uint32)
+            self._check(self._l.atn_volume_download(self._ctx, 4, out.ctypes.data))
+            return dict(stack_overflow=int(out[0]), walk_overflow=int(out[1]), connections=int(out[2]), segments=int(out[3]))
+        if name == "state":
+            out = np.empty((h, w, 4), np.uint32)
+            self._check(self._l.atn_volume_download(self._ctx, 0, out.ctypes.data))
+            return unpack_volume_state(out)
+        if name == "stack":
+            st = np.empty((h, w, 4), np.uint32)
+            self._check(self._l.atn_volume_download(self._ctx, 0, st.ctypes.data))
+            out = np.empty((h, w, 4), np.uint32)
+            self._check(self._l.atn_volume_download(self._ctx, 1, out.ctypes.data))
+            return unpack_volume_stack(out, st[..., 2])
+        if name == "ray":
+            out = np.empty((h, w, 2, 4), np.float32)
+            self._check(self._l.atn_volume_download(self._ctx, 2, out.ctypes.data))
+            return dict(org=out[..., 0, :3].copy(), s=out[..., 0, 3].copy(), dir=out[..., 1, :3].copy(), hit_t=out[..., 1, 3].copy())
+        if name == "conn":
+            out = np.empty((h, w, 3, 4), np.float32)
+            self._check(self._l.atn_volume_download(self._ctx, 3, out.ctypes.data))
+            return dict(org=out[..., 0, :3].copy(), t_max=out[..., 0, 3].copy(), dir=out[..., 1, :3].copy(), transmittance=out[..., 1, 3].copy(),
+                        segments=out[..., 2, 0].astype(np.int32), visible=out[..., 2, 1] != 0)
+        raise ValueError("no volume buffer %r" % (name,))
+
+    def volume_phase_table(self, g, w, r1, r2, wo):
+        """HenyeyGreensteinPhaseFunction on the device for n cases: (SampleDirection(r1, r2, g, w) [n, 3], Evaluate(g, w, wo) [n])."""
+        w = np.ascontiguousarray(w, np.float32).reshape(-1, 3)
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        r1 = np.ascontiguousarray(r1, np.float32).reshape(-1)
+        r2 = np.ascontiguousarray(r2, np.float32).reshape(-1)
+        n = len(r1)
+        assert len(w) == n and len(wo) == n and len(r2) == n
+        out_dir = np.empty((n, 3), np.float32)
+        out_eval = np.empty(n, np.float32)
+        self._check(self._l.atn_volume_phase_table(self._ctx, float(g), n, w.ctypes.data, r1.ctypes.data, r2.ctypes.data, wo.ctypes.data,
+                                                   out_dir.ctypes.data, out_eval.ctypes.data))
+        return out_dir, out_eval
+
     def svgf_denoise(self, width, height, frame=0, compute_motion=False, stages=False, download=True, profile=False):
         """The filter passes of OnRender on the buffers as they stand (svgf_upload / a previous path pass)."""
         d = Destination(width, height, 1, 1, 1, frame, 0, 1, 0, int(profile))
@@ -590,3 +654,24 @@ class MultiGpuPathTracing:
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(self._l.atn_mgpu_download_film(self._mg, out.ctypes.data))
         return out
+
+
+VOLUME_STATE_FLAGS = dict(processed=1, hit=2, sampled=4, absorbed=8, scattered=16, passed=32, connection=64, terminated=256)
+
+
+def unpack_volume_state(raw):
+    """uint32 [h, w, 4] {flags, depth_count, stack size, CMJ dimension} of atn_volume_download(0) -> dict."""
+    out = {k: (raw[..., 0] & v) != 0 for k, v in VOLUME_STATE_FLAGS.items()}
+    out.update(depth_count=raw[..., 1].astype(np.int32), stack_size=raw[..., 2].astype(np.int32), dim=raw[..., 3].copy())
+    return out
+
+
+def unpack_volume_stack(raw, size):
+    """uint32 [h, w, 4] (eight 16-bit ids, the newest in the low half of word 0) + the stack size -> int32 [h, w, 8] in the order the
+    media were entered, zeros beyond the size."""
+    half = np.stack([(raw[..., k // 2] >> (16 * (k % 2))) & 0xffff for k in range(8)], axis=-1).astype(np.int32)      # newest first
+    size = np.asarray(size, np.int64)
+    k = np.arange(8)
+    src = size[..., None] - 1 - k
+    out = np.take_along_axis(half, np.clip(src, 0, 7), axis=-1)
+    return np.where(src >= 0, out, 0).astype(np.int32)

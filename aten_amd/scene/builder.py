@@ -48,6 +48,13 @@ def write_feature_line_config(config, enabled, color=(0.0, 0.0, 0.0), width=1.0,
     C.memmove(C.addressof(config) + L.SceneRenderingConfig.feature_line.offset, b, len(b))
 
 
+def write_medium(m, g, sigma_a, sigma_s, le=(0.0, 0.0, 0.0)):
+    """atn_medium_param (32 B: phase_function_g, sigma_a, sigma_s, int32 grid_idx = -1, majorant = -1, le[3]) into a MATERIAL_PARAM
+    record's `medium` bytes, and is_medium = 1."""
+    m["medium"] = np.frombuffer(struct.pack("<fffif3f", float(g), float(sigma_a), float(sigma_s), -1, -1.0, *[float(c) for c in le]), F32)
+    m["is_medium"] = 1
+
+
 def write_feature_line_mtrl(m, enable, metric_flag):
     """atn_feature_line_mtrl (8 B: enable, pad 3, int32 metric_flag) into a MATERIAL_PARAM record's `feature_line` bytes."""
     m["feature_line"] = np.frombuffer(struct.pack("<B3xi", 1 if enable else 0, int(metric_flag)), np.uint8)
@@ -142,9 +149,11 @@ class SceneBuilder:
         drawn by PathTracing.npr_render; a builder that never calls this leaves the bytes zero (lines off)."""
         write_feature_line_config(self.config, enabled, color, width, albedo_threshold, normal_threshold)
 
-    def add_material(self, name, mtype, base_color, albedo_map=-1, normal_map=-1, roughness_map=-1, feature_line=(0, 0), **std):
+    def add_material(self, name, mtype, base_color, albedo_map=-1, normal_map=-1, roughness_map=-1, feature_line=(0, 0), medium=None, **std):
         """feature_line = (enable, metric_flag): aten::FeatureLineMtrlConfig, bytes 240-247 (material.h:237-240).  The default
-        (0, 0) keeps the bytes zero -- the reference's own defaults are enable = 1, metric_flag = 15 (FEATURE_LINE_ALL)."""
+        (0, 0) keeps the bytes zero -- the reference's own defaults are enable = 1, metric_flag = 15 (FEATURE_LINE_ALL).
+        medium = dict(g, sigma_a, sigma_s, le): a surface with a scattering interior (is_medium = 1, MediumParameter at 108),
+        rendered by PathTracing.volume_render.  None leaves is_medium 0 and the medium bytes at MaterialParameter's defaults."""
         m = np.zeros((), L.MATERIAL_PARAM)
         bc = list(base_color)
         m["baseColor"] = (bc + [0.0])[:4] if len(bc) == 3 else bc      # vec4 = vec3 -> w = 0 (vec4.h:135-141 keeps w)
@@ -161,8 +170,17 @@ class SceneBuilder:
         m["medium"][3] = np.int32(-1).view(F32)     # MediumParameter.grid_idx = -1
         m["medium"][4] = -1.0                       # majorant
         write_feature_line_mtrl(m, *feature_line)
+        if medium is not None:
+            write_medium(m, medium["g"], medium["sigma_a"], medium["sigma_s"], medium.get("le", (0.0, 0.0, 0.0)))
         self.materials.append((name, m))
         return len(self.materials) - 1
+
+    def add_medium_material(self, name, g, sigma_a, sigma_s, le=(0.0, 0.0, 0.0)):
+        """material::CreateMaterialMediumParameter (material/material.cpp:212-232): type Volume, is_medium, no attribute bits -- a
+        pure medium boundary (a closed mesh around a homogeneous medium).  Everything else is MaterialParameter's default."""
+        mid = self.add_material(name, L.MTRL_VOLUME, (0.0, 0.0, 0.0), medium=dict(g=g, sigma_a=sigma_a, sigma_s=sigma_s, le=le))
+        self.materials[mid][1]["attrib"] = 0
+        return mid
 
     def add_carpaint_material(self, name, base_color=(1.0, 1.0, 1.0), albedo_map=-1, **cp):
         """aten::CarPaint: CarPaintMaterialParameter (material.h:163-198, defaults of Init()) in the union next to `standard`."""

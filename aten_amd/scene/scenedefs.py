@@ -528,3 +528,106 @@ def npr_sponza(asset_dir=None, **lines):
     """sponza_lod with GGX materials -- glossy, so sample rays keep bouncing -- and black feature lines on every material: the NPR
     benchmark scene."""
     return with_feature_lines(sponza_lod(asset_dir), **lines)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Homogeneous media (PathTracing.volume_render; docs/VOLUME.md), after scenedefs.cpp:1058-1250
+# ---------------------------------------------------------------------------------------------------
+def _box_mesh(bmin, bmax):
+    """An axis-aligned box as 12 triangles wound so that the geometric normals face outwards."""
+    x0, y0, z0 = bmin
+    x1, y1, z1 = bmax
+    p = np.array([(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)], np.float32)
+    quads = [(0, 3, 2, 1), (4, 5, 6, 7), (0, 4, 7, 3), (1, 2, 6, 5), (0, 1, 5, 4), (3, 7, 6, 2)]      # -z +z -x +x -y +y
+    tri = np.array([t for (a, b_, c, d) in quads for t in ((a, b_, c), (a, c, d))], np.int64)
+    return p, tri
+
+
+def _cornell_with(create_mtrl, light_intensity=20.0):
+    b = SceneBuilder()
+    emit = b.add_material("light", L.MTRL_EMISSIVE, (1.0, 1.0, 1.0))
+    objs = b.load_obj(os.path.join(ASSETS, "cornellbox", "orig.obj"), create_mtrl=lambda *a: create_mtrl(b, *a),
+                      separate_objs=True, normal_on_the_fly=True)
+    light = b.create_instance(objs[0])
+    b.add_area_light(light, b.materials[emit][1]["baseColor"][:3], light_intensity)
+    for o in objs[1:]:
+        b.create_instance(o)
+    b.set_background((0.0, 0.0, 0.0))
+    return b, dict(pos=(0.0, 1.0, 3.0), at=(0.0, 1.0, 0.0), vfov=45.0)
+
+
+def cornell_box_medium():
+    """CornellBoxHomogeneousMediumScene (scenedefs.cpp:1121-1190): orig.obj with shortBox and tallBox as homogeneous media
+    (g -0.4, sigma_a 0.5, sigma_s 0.5, le red / green)."""
+    def create_mtrl(b, name, mtype, clr, albedo, nml):
+        if name == "shortBox":
+            return b.add_medium_material(name, -0.4, 0.5, 0.5, (1.0, 0.0, 0.0))
+        if name == "tallBox":
+            return b.add_medium_material(name, -0.4, 0.5, 0.5, (0.0, 1.0, 0.0))
+        return b.add_material(name, mtype, clr)
+    b, cam = _cornell_with(create_mtrl)
+    return b.build(), cam
+
+
+def cornell_box_smoke(bmin=(-0.9, 0.02, -0.9), bmax=(0.9, 1.5, 0.9)):
+    """CornellBoxSmokeScene (scenedefs.cpp:1058-1118) with the smoke box built here instead of box_smoke.obj: the Cornell box with a
+    box of smoke (g -0.4, sigma_a 0, sigma_s 0.5, le red) around the two boxes -- surfaces inside a medium, connections that leave it."""
+    b, cam = _cornell_with(lambda b, name, mtype, clr, albedo, nml: b.add_material(name, mtype, clr))
+    smoke = b.add_medium_material("medium", -0.4, 0.0, 0.5, (1.0, 0.0, 0.0))
+    p, tri = _box_mesh(bmin, bmax)
+    b.create_instance(b.add_mesh("smoke", p, tri, smoke))
+    return b.build(), cam
+
+
+def cornell_box_subsurface(center=(0.0, 0.6, 0.2), radius=0.45, level=3):
+    """HomogeneousMediumRefractionBunnyScene (scenedefs.cpp:1192-1250) with an icosphere standing in for the bunny (its mesh is a
+    missing blob): a Refraction surface (ior 1.333) with an interior (g 0.4, sigma_a 0, sigma_s 0.9, le 0.8) in the empty Cornell box."""
+    def create_mtrl(b, name, mtype, clr, albedo, nml):
+        return b.add_material(name, mtype, clr)
+    b = SceneBuilder()
+    emit = b.add_material("light", L.MTRL_EMISSIVE, (1.0, 1.0, 1.0))
+    objs = b.load_obj(os.path.join(ASSETS, "cornellbox", "orig.obj"), create_mtrl=lambda *a: create_mtrl(b, *a),
+                      separate_objs=True, normal_on_the_fly=True)
+    light = b.create_instance(objs[0])
+    b.add_area_light(light, b.materials[emit][1]["baseColor"][:3], 20.0)
+    short_box, tall_box = b.find_material("shortBox"), b.find_material("tallBox")
+    for o in objs[1:]:
+        mtrls = {m["mtrl"] for m in b.objects[o]["meshes"]}
+        if mtrls & {short_box, tall_box}:
+            continue        # the two boxes make room for the sphere
+        b.create_instance(o)
+    mid = b.add_material("material_0", L.MTRL_REFRACTION, (0.58, 0.58, 0.58), ior=1.333, roughness=0.011,
+                         medium=dict(g=0.4, sigma_a=0.0, sigma_s=0.9, le=(0.8, 0.8, 0.8)))
+    v, f = _icosphere(level)
+    p = (v * radius + np.asarray(center, np.float64)).astype(np.float32)
+    # face normals, as the reference loads its meshes here (ObjLoader::Load(..., true, true)): with interpolated normals a grazing
+    # connection can read "leaving" off the shading normal while it geometrically enters, and step along the surface facet by facet
+    b.create_instance(b.add_mesh("sphere", p, f, mid, need_normal=True))
+    b.set_background((0.0, 0.0, 0.0))
+    return b.build(), dict(pos=(0.0, 1.0, 3.0), at=(0.0, 1.0, 0.0), vfov=45.0)
+
+
+def fog_sponza(sigma_s=0.15, g=0.2):
+    """sponza_lod with a slab of thin fog across the nave, the camera outside the slab: the volume benchmark scene.  (A camera inside
+    a closed medium starts with an empty medium stack, as in the reference: the medium would not be seen from inside.)"""
+    def add_fog(b, bmin, bmax, cam):
+        fog = b.add_medium_material("fog", g, 0.0, sigma_s, (0.0, 0.0, 0.0))
+        lo = np.asarray(bmin, np.float64) + 0.02 * (np.asarray(bmax, np.float64) - np.asarray(bmin, np.float64))
+        hi = np.asarray(bmax, np.float64) - 0.02 * (np.asarray(bmax, np.float64) - np.asarray(bmin, np.float64))
+        # in front of the camera (it looks down -z from z = 3): the slab ends before it
+        hi[2] = min(hi[2], cam["pos"][2] - 1.0)
+        lo[2] = min(lo[2], hi[2] - 1.0)
+        p, tri = _box_mesh(tuple(lo), tuple(hi))
+        b.create_instance(b.add_mesh("fog", p, tri, fog))
+    return sponza_lod(add_lights=add_fog)
+
+
+def absorbing_slab(sigma=1.0, thickness=1.0, bg=(1.0, 1.0, 1.0), half=50.0):
+    """One Volume box (sigma_s 0, le 0: an absorbing slab, z in [-thickness, 0], +-half wide) in front of a constant background, no
+    lights: the film estimates bg * exp(-sigma * chord) (Beer-Lambert).  The camera looks down -z from z = 2."""
+    b = SceneBuilder()
+    m = b.add_medium_material("slab", 0.0, sigma, 0.0, (0.0, 0.0, 0.0))
+    p, tri = _box_mesh((-half, -half, -thickness), (half, half, 0.0))
+    b.create_instance(b.add_mesh("slab", p, tri, m))
+    b.set_background(bg)
+    return b.build(), dict(pos=(0.0, 0.0, 2.0), at=(0.0, 0.0, 0.0), vfov=45.0)

@@ -376,6 +376,33 @@ int atn_npr_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host)
 int atn_npr_reset(atn_ctx* ctx);
 int atn_npr_capture(atn_ctx* ctx, int32_t on);
 int atn_npr_download(atn_ctx* ctx, int32_t which, void* out_host);
+
+/* ---- Volume rendering: path tracing through homogeneous media (aten::VolumePathTracing / idaten::VolumeRendering; docs/VOLUME.md)
+ * Materials with is_medium set carry a medium (atn_medium_param): type ATN_MTRL_VOLUME is a pure boundary the ray passes through,
+ * any other type a surface with a scattering interior.  A path runs at most 8 iterations (the reference's cap); light connections
+ * walk through medium boundaries and collect transmittance.
+ *   atn_volume_render: one frame; the film follows atn_render's progressive / overwrite rules.  ATN_ERR_UNSUPPORTED for a medium
+ *                      with grid_idx >= 0 (NanoVDB grids) or sigma_a + sigma_s <= 0, a screen shard with world > 1, path
+ *                      regeneration, relaxed shade math, count_stats, alpha blending with a material whose alpha may be < 1,
+ *                      StencilType::STENCIL materials, CarPaint and Toon / Stylized materials.  A scene without media renders.
+ *   atn_volume_reset: the film starts over (a fresh context's)
+ *   atn_volume_capture: keep the per-pixel state after iteration `iteration` (0..7) of sample 0 of the next frames; < 0: off
+ *   atn_volume_download: which = 0 uint32[w*h][4] {flags, depth_count, stack size, CMJ dimension}; flags: 1 processed, 2 hit,
+ *                        4 free flight sampled, 8 absorbed, 16 scattered, 32 passed through a boundary, 64 connection made,
+ *                        256 terminated;  1 uint32[w*h][4] the medium stack, eight 16-bit ids, the newest in the low half of word 0;
+ *                        2 atn_vec4[w*h][2] {next ray org, sampled distance s} {next ray dir, hit distance};
+ *                        3 atn_vec4[w*h][3] the connection {org, t_max} {dir, transmittance} {segments, visible, 0, 0};
+ *                        4 uint32[4] the last frame's counters {pushes dropped on a full stack, connections that crossed 64
+ *                        boundaries, connections, segments} (needs no capture).
+ *   atn_volume_phase_table: HenyeyGreensteinPhaseFunction::SampleDirection(r1, r2, g, w) -> out_dir[3 n] and Evaluate(g, w, wo) ->
+ *                        out_eval[n] for n cases (host arrays; w, wo: float[3 n])
+ * Additive entry points: atn_abi_version stays 3. */
+int atn_volume_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host);
+int atn_volume_reset(atn_ctx* ctx);
+int atn_volume_capture(atn_ctx* ctx, int32_t iteration);
+int atn_volume_download(atn_ctx* ctx, int32_t which, void* out_host);
+int atn_volume_phase_table(atn_ctx* ctx, float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo,
+                           float* out_dir, float* out_eval);
 /* The filter passes alone (everything of OnRender after the sample loop, svgf.cpp:515-637) on whatever the
  * path pass -- or atn_svgf_upload -- left in the buffers: contributions (which = 14: contrib.xyz, sample count),
  * the current AOVs (0, 1), primary hit positions (10), motion/depth (9).  This is how a caller that already has a

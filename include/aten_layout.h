@@ -215,6 +215,19 @@ typedef struct atn_feature_line_mtrl {
     int32_t metric_flag;                  /*  4 */
 } atn_feature_line_mtrl;
 
+/* Typed view of the medium bytes (atn_volume_render; the float member above stays as it is): aten::MediumParameter, 32 B
+ * (material/material.h) = atn_material_param.medium, read when atn_material_param.is_medium != 0.  A pure medium boundary has
+ * type ATN_MTRL_VOLUME (material::CreateMaterialMediumParameter, material.cpp:212-232); a surface type with is_medium set is a
+ * surface with a scattering interior.  grid_idx >= 0 names a NanoVDB grid: refused (docs/VOLUME.md). */
+typedef struct atn_medium_param {
+    float phase_function_g;               /*  0: Henyey-Greenstein g, clamped to [-1, 1] */
+    float sigma_a;                        /*  4 */
+    float sigma_s;                        /*  8 */
+    int32_t grid_idx;                     /* 12: -1 = homogeneous */
+    float majorant;                       /* 16: heterogeneous media only */
+    float le[3];                          /* 20: multiplied into the throughput at an absorption event */
+} atn_medium_param;
+
 /* ---- aten::Intersection, 32 B (src/libaten/scene/hit_parameter.h:28-64) */
 typedef struct atn_intersection {
     float t;
@@ -315,6 +328,11 @@ static_assert(sizeof(atn_feature_line_mtrl) == 8 && offsetof(atn_feature_line_mt
 static_assert(sizeof(((atn_scene_rendering_config*)0)->feature_line) == sizeof(atn_feature_line_config)
               && offsetof(atn_scene_rendering_config, feature_line) == 4, "SceneRenderingConfig.feature_line");
 static_assert(sizeof(((atn_material_param*)0)->feature_line) == sizeof(atn_feature_line_mtrl), "MaterialParameter.feature_line");
+static_assert(sizeof(atn_medium_param) == 32 && offsetof(atn_medium_param, grid_idx) == 12 && offsetof(atn_medium_param, majorant) == 16
+              && offsetof(atn_medium_param, le) == 20, "MediumParameter");
+static_assert(sizeof(((atn_material_param*)0)->medium) == sizeof(atn_medium_param) && offsetof(atn_material_param, medium) == 108
+              && offsetof(atn_material_param, is_medium) == 27, "MaterialParameter.medium");
+static_assert(offsetof(atn_scene_rendering_config, epsilon_bias_for_traversing_shadow_ray_in_medium) == 36, "SceneRenderingConfig.epsilon_bias");
 static_assert(sizeof(atn_intersection) == 32, "Intersection");
 static_assert(sizeof(atn_ray) == 24, "ray");
 #endif

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <random>
 #include <string>
 #include <vector>
@@ -23,6 +24,7 @@
 #include "device/npr.hpp"
 #include "device/volume.hpp"
 #include "device/lbvh.hpp"
+#include "device/skinning.hpp"
 #include "host/scene_upload.hpp"
 #include "host/ibl_precompute.hpp"
 
@@ -708,6 +710,7 @@ public:
         ATN_HIP(hipSetDevice(device));
         { int q = quiesce(); if (q) return q; }
         drop_alt_set(); cur_set = 0; scene_in_place = false; frame_since_update = true;
+        skins.clear();          // a skin is bound to ranges of the scene it was created on
         HostSceneImage img;
         std::string err;
         // (the upload options are context state: the environment was read ONCE, when the context was created; atn_set_upload_options
@@ -915,6 +918,7 @@ public:
             for (int v = 0; v < 3; v++)
                 if (tr[i].idx[v] < 0 || (uint32_t)tr[i].idx[v] >= n_scene_vtx) return fail(ATN_ERR_UNSUPPORTED, "triangle vertex index out of range");
         }
+        skins_note_triangles(tr, n_tr, tri_offset);
         ATN_HIP(hipSetDevice(device));
         // a light's vertices or triangles may be among these: then its shadow rays walk to their closest hit from here on
         if (scene.planar_lights && !planar_certs_survive_geometry(vtx_offset, n_vtx, tri_offset, n_tr)) scene.planar_lights = 0;
@@ -963,15 +967,19 @@ public:
 
     // Morton codes -> sort -> hierarchy -> links -> boxes, all enqueued on `stream`; the tree is left in lb.ref_nodes in
     // the reference's node order.  `tr` points at the first of the n triangles, `vtx` at the vertex array.
+    // (box_dev: the box in device memory instead of bmin / bmax -- a skin's, atn_lbvh_rebuild_list_skinned)
     int lbvh_enqueue(const atn_triangle_param* tr, uint32_t n, int32_t tri_id_offset, const float* bmin, const float* bmax,
-                     const float4* vtx, int32_t vtx_offset, uint32_t image_base, hipStream_t st)
+                     const float4* vtx, int32_t vtx_offset, uint32_t image_base, hipStream_t st, const float* box_dev = nullptr)
     {
         { int r = lbvh_reserve(n); if (r) return r; }
         const uint32_t rounds = radix_rounds(n), tile = kSortThreads * rounds, nb = (n + tile - 1) / tile, nn = 2 * n - 1;
         const dim3 b256(256);
-        f3 mn, mx;
-        mn.x = bmin[0]; mn.y = bmin[1]; mn.z = bmin[2]; mx.x = bmax[0]; mx.y = bmax[1]; mx.z = bmax[2];
-        hipLaunchKernelGGL(k_lbvh_morton, dim3((n + 255) / 256), b256, 0, st, tr, vtx, vtx_offset, n, mn, mx, lb.codes[0].p, lb.indices[0].p);
+        if (box_dev) skin_launch_morton(st, tr, vtx, vtx_offset, n, box_dev, lb.codes[0].p, lb.indices[0].p);
+        else {
+            f3 mn, mx;
+            mn.x = bmin[0]; mn.y = bmin[1]; mn.z = bmin[2]; mx.x = bmax[0]; mx.y = bmax[1]; mx.z = bmax[2];
+            hipLaunchKernelGGL(k_lbvh_morton, dim3((n + 255) / 256), b256, 0, st, tr, vtx, vtx_offset, n, mn, mx, lb.codes[0].p, lb.indices[0].p);
+        }
         for (uint32_t pass = 0; pass < 4; pass++) {
             const int in = pass & 1, out = in ^ 1;
             hipLaunchKernelGGL(k_radix_count, dim3(nb), dim3(kSortThreads), 0, st, (const uint32_t*)lb.codes[in].p, n, pass * 8u, lb.counts.p, nb, rounds);
@@ -1027,10 +1035,10 @@ public:
     // the device NOW, and write its records over the list's region of the node image.  The region keeps its size: an
     // LBVH over n triangles is n - 1 inner records and n triangle leaves, so the list must have been uploaded with one
     // leaf per triangle (any full binary tree over the n triangles, e.g. atns_build_blas's).
-    int lbvh_rebuild_list(uint32_t list, uint32_t tri_offset, uint32_t n, const float* bmin, const float* bmax, bool sync)
+    int lbvh_rebuild_list(uint32_t list, uint32_t tri_offset, uint32_t n, const float* bmin, const float* bmax, bool sync, const float* box_dev = nullptr)
     {
         if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
-        if (!bmin || !bmax) return fail(ATN_ERR_INVALID_ARG, "null bounding box");
+        if (!box_dev && (!bmin || !bmax)) return fail(ATN_ERR_INVALID_ARG, "null bounding box");
         if (list == 0 || list >= list_base.size()) return fail(ATN_ERR_INVALID_ARG, "not a bottom-level BVH list");
         if (n < 2) return fail(ATN_ERR_INVALID_ARG, "an LBVH needs at least two triangles");
         if (n > kLbvhMaxTris) return fail(ATN_ERR_UNSUPPORTED, "too many triangles: node indices are stored as floats");
@@ -1045,8 +1053,9 @@ public:
         if (twin_word != 0 && twin_delta != list_bytes[list]) return fail(ATN_ERR_UNSUPPORTED, "the list's twins do not lie at the list's own size apart");
         { int r = begin_scene_update(64); if (r) return r; }
         // a caller may have written the scene arrays in place (atn_scene_device_arrays): refresh this mesh's shading records
-        { int r = repack_shade_tris(tri_offset, n); if (r) return r; }
-        { int r = lbvh_enqueue(tris.p + tri_offset, n, (int32_t)tri_offset, bmin, bmax, vtx_pos.p, 0, list_base[list], upd); if (r) return r; }
+        // (a skin's compute has written them already)
+        if (!box_dev) { int r = repack_shade_tris(tri_offset, n); if (r) return r; }
+        { int r = lbvh_enqueue(tris.p + tri_offset, n, (int32_t)tri_offset, bmin, bmax, vtx_pos.p, 0, list_base[list], upd, box_dev); if (r) return r; }
         const uint32_t nn = 2 * n - 1;
         hipLaunchKernelGGL(k_lbvh_emit, dim3((nn + 255) / 256), dim3(256), 0, upd, n, (const atn_bvh_node*)lb.ref_nodes.p, (const uint32_t*)lb.offs.p,
                            (const atn_triangle_param*)tris.p, (const float4*)vtx_pos.p, nodes.p);
@@ -1064,6 +1073,200 @@ public:
         // the root is node 0 = an inner record at the start of the region: the TLAS leaves' root link (and twin word) stay valid
         { int r = end_scene_update(); if (r) return r; }
         if (sync) ATN_HIP(hipStreamSynchronize(upd));
+        return ATN_OK;
+    }
+
+    // ---------------------------------------------------------------------------------------------------------------
+    // Skinning on the device (device/skinning.hpp, docs/SKINNING.md): ≙ idaten::Skinning, src/libidaten/kernel/Skinning.cu:147-375.
+    struct Skin {
+        uint32_t handle = 0, n_vtx = 0, vtx_off = 0, tri_off = 0, n_tri = 0, n_mtx = 0;
+        bool has_palette = false, computed = false, stale = false;
+        DevBuf<atn_skinning_vertex> verts;
+        DevBuf<float4> palette, prev;
+        DevBuf<uint32_t> partial;       // per block of the vertex pass: the block's box as keys
+        DevBuf<float> box;              // min xyz, max xyz
+    };
+    std::vector<std::unique_ptr<Skin>> skins;
+    uint32_t skin_counter = 0;          // handles are never reused: a dead handle stays dead
+    Skin* find_skin(atn_skin h)
+    {
+        for (auto& k : skins) if (k->handle == h && h != 0) return k.get();
+        return nullptr;
+    }
+    // an atn_update_geometry that rewrites a skin's triangles: the skin computes on only while they still name its own vertices
+    void skins_note_triangles(const atn_triangle_param* tr, uint32_t n_tr, uint32_t tri_offset)
+    {
+        for (auto& k : skins) {
+            const uint64_t lo = std::max<uint64_t>(tri_offset, k->tri_off), hi = std::min<uint64_t>((uint64_t)tri_offset + n_tr, (uint64_t)k->tri_off + k->n_tri);
+            for (uint64_t t = lo; t < hi; t++)
+                for (int v = 0; v < 3; v++) {
+                    const int64_t j = (int64_t)tr[t - tri_offset].idx[v] - (int64_t)k->vtx_off;
+                    if (j < 0 || j >= (int64_t)k->n_vtx) k->stale = true;
+                }
+        }
+    }
+
+    int skin_create(const atn_skinning_vertex* v, uint32_t n_vtx, uint32_t vtx_off, uint32_t tri_off, uint32_t n_tr, uint32_t n_mtx, atn_skin* out)
+    {
+        if (!out) return fail(ATN_ERR_INVALID_ARG, "null skin handle");
+        *out = 0;
+        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+        if (scene_in_place) return fail(ATN_ERR_UNSUPPORTED, "skins are not supported once the caller writes the scene arrays itself (atn_scene_device_arrays)");
+        if (!v || n_vtx == 0) return fail(ATN_ERR_INVALID_ARG, "empty skinning vertex array");
+        if (n_mtx == 0) return fail(ATN_ERR_INVALID_ARG, "a skin needs at least one matrix");
+        if (n_mtx > kSkinMaxMatrices) return fail(ATN_ERR_UNSUPPORTED, "too many matrices in the skin's palette");
+        if ((uint64_t)vtx_off + n_vtx > n_scene_vtx) return fail(ATN_ERR_INVALID_ARG, "vertex range outside the uploaded scene");
+        if ((uint64_t)tri_off + n_tr > n_scene_tris) return fail(ATN_ERR_INVALID_ARG, "triangle range outside the uploaded scene");
+        for (uint32_t i = 0; i < n_vtx; i++)
+            for (int k = 0; k < 4; k++) {
+                const float f = v[i].blend_index[k];
+                // (int)f in [0, n_mtx); a NaN fails the first comparison
+                if (!(f > -1.0F && f < (float)n_mtx)) return fail(ATN_ERR_UNSUPPORTED, "blend index " + std::to_string(k) + " of vertex " + std::to_string(i) + " is outside the palette");
+            }
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        // the triangles as they are on the device now (the host keeps no copy)
+        std::vector<atn_triangle_param> tr(n_tr);
+        if (n_tr) {
+            ATN_HIP(hipMemcpyAsync(tr.data(), tris.p + tri_off, (size_t)n_tr * sizeof(atn_triangle_param), hipMemcpyDeviceToHost, stream));
+            ATN_HIP(hipStreamSynchronize(stream));
+        }
+        for (uint32_t t = 0; t < n_tr; t++)
+            for (int k = 0; k < 3; k++) {
+                const int64_t j = (int64_t)tr[t].idx[k] - (int64_t)vtx_off;
+                if (j < 0 || j >= (int64_t)n_vtx) return fail(ATN_ERR_INVALID_ARG, "triangle " + std::to_string(tri_off + t) + " names a vertex outside the skin's vertex range");
+            }
+        std::unique_ptr<Skin> k(new Skin());
+        k->n_vtx = n_vtx; k->vtx_off = vtx_off; k->tri_off = tri_off; k->n_tri = n_tr; k->n_mtx = n_mtx;
+        const SkinLaunch l = skin_launch(n_vtx, n_tr, n_mtx, kSkinPaletteLds);
+        ATN_HIP(k->verts.resize(n_vtx)); ATN_HIP(k->palette.resize(4u * (size_t)n_mtx)); ATN_HIP(k->prev.resize(n_vtx));
+        ATN_HIP(k->partial.resize(6u * (size_t)l.vtx_grid)); ATN_HIP(k->box.resize(6));
+        ATN_HIP(hipMemcpyAsync(k->verts.p, v, (size_t)n_vtx * sizeof(atn_skinning_vertex), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipMemsetAsync(k->prev.p, 0, (size_t)n_vtx * sizeof(float4), stream));
+        ATN_HIP(hipMemsetAsync(k->box.p, 0, 6 * sizeof(float), stream));
+        ATN_HIP(hipStreamSynchronize(stream));      // `v` is pageable host memory
+        k->handle = ++skin_counter;
+        *out = k->handle;
+        skins.push_back(std::move(k));
+        return ATN_OK;
+    }
+
+    int skin_destroy(atn_skin h)
+    {
+        if (!find_skin(h)) return fail(ATN_ERR_INVALID_ARG, "not a live skin (destroyed, or older than the last atn_upload_scene)");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }     // its buffers may be in use on the update stream
+        for (size_t i = 0; i < skins.size(); i++) if (skins[i]->handle == h) { skins.erase(skins.begin() + (long)i); break; }
+        return ATN_OK;
+    }
+
+    // ≙ Skinning::update, Skinning.cu:214-225
+    int skin_update(atn_skin h, const atn_mat4* m, uint32_t n)
+    {
+        Skin* k = find_skin(h);
+        if (!k) return fail(ATN_ERR_INVALID_ARG, "not a live skin (destroyed, or older than the last atn_upload_scene)");
+        if (!m) return fail(ATN_ERR_INVALID_ARG, "null matrix array");
+        if (n != k->n_mtx) return fail(ATN_ERR_INVALID_ARG, "the palette must hold the skin's " + std::to_string(k->n_mtx) + " matrices");
+        ATN_HIP(hipSetDevice(device));
+        const size_t bytes = (size_t)n * sizeof(atn_mat4);
+        { int r = begin_scene_update(bytes + 256); if (r) return r; }
+        { int r = stage_copy(k->palette.p, m, bytes); if (r) return r; }      // atn_mat4 is four float4 rows
+        { int r = end_scene_update(); if (r) return r; }
+        k->has_palette = true;
+        return ATN_OK;
+    }
+
+    // ≙ Skinning::compute, Skinning.cu:227-345
+    int skin_compute(atn_skin h, bool restart, float* bmin, float* bmax)
+    {
+        Skin* k = find_skin(h);
+        if (!k) return fail(ATN_ERR_INVALID_ARG, "not a live skin (destroyed, or older than the last atn_upload_scene)");
+        if ((bmin == nullptr) != (bmax == nullptr)) return fail(ATN_ERR_INVALID_ARG, "give both corners of the box or neither");
+        if (!k->has_palette) return fail(ATN_ERR_INVALID_ARG, "atn_skin_update has not been called on this skin");
+        if (scene_in_place) return fail(ATN_ERR_UNSUPPORTED, "skins are not supported once the caller writes the scene arrays itself (atn_scene_device_arrays)");
+        if (k->stale) return fail(ATN_ERR_UNSUPPORTED, "atn_update_geometry rewrote the skin's triangles with vertices outside the skin's range");
+        ATN_HIP(hipSetDevice(device));
+        // the lamp's vertices or triangles may be among these (updateGeometry's rule)
+        if (scene.planar_lights && !planar_certs_survive_geometry(k->vtx_off, k->n_vtx, k->tri_off, k->n_tri)) scene.planar_lights = 0;
+        { int r = begin_scene_update(64); if (r) return r; }
+        const SkinLaunch l = skin_launch(k->n_vtx, k->n_tri, k->n_mtx, kSkinPaletteLds);
+        SkinVtxArgs va{};
+        va.verts = reinterpret_cast<const uint2*>(k->verts.p); va.palette = k->palette.p;
+        va.pos = vtx_pos.p + k->vtx_off; va.nml = vtx_nml.p + k->vtx_off; va.prev = k->prev.p; va.partial = k->partial.p;
+        va.n_vtx = k->n_vtx; va.n_mtx = k->n_mtx; va.restart = restart ? 1 : 0;
+        skin_launch_vertices(l, upd, va);
+        SkinTriArgs ta{};
+        ta.tris = tris.p; ta.vtx_pos = vtx_pos.p; ta.vtx_nml = vtx_nml.p; ta.shade_tris = shade_tris.p;
+        ta.first = k->tri_off; ta.count = k->n_tri; ta.partial = k->partial.p; ta.n_partial = l.vtx_grid; ta.box = k->box.p;
+        skin_launch_triangles(l, upd, ta);
+        ATN_HIP(hipGetLastError());
+        const size_t vb = (size_t)k->n_vtx * sizeof(float4);
+        log_range(SB_VTX_POS, (size_t)k->vtx_off * sizeof(float4), vb);
+        log_range(SB_VTX_NML, (size_t)k->vtx_off * sizeof(float4), vb);
+        log_range(SB_TRIS, (size_t)k->tri_off * sizeof(atn_triangle_param), (size_t)k->n_tri * sizeof(atn_triangle_param));
+        log_range(SB_SHADE, (size_t)k->tri_off * kShadeTriQuads * sizeof(float4), (size_t)k->n_tri * kShadeTriQuads * sizeof(float4));
+        { int r = end_scene_update(); if (r) return r; }
+        k->computed = true;
+        if (bmin) {
+            float b[6];
+            ATN_HIP(hipMemcpyAsync(b, k->box.p, sizeof(b), hipMemcpyDeviceToHost, upd));
+            ATN_HIP(hipStreamSynchronize(upd));
+            for (int c = 0; c < 3; c++) { bmin[c] = b[c]; bmax[c] = b[3 + c]; }
+        }
+        return ATN_OK;
+    }
+
+    int lbvh_rebuild_list_skinned(uint32_t list, atn_skin h)
+    {
+        Skin* k = find_skin(h);
+        if (!k) return fail(ATN_ERR_INVALID_ARG, "not a live skin (destroyed, or older than the last atn_upload_scene)");
+        if (!k->computed) return fail(ATN_ERR_INVALID_ARG, "atn_skin_compute has not been called on this skin: there is no box yet");
+        if (scene_in_place) return fail(ATN_ERR_UNSUPPORTED, "skins are not supported once the caller writes the scene arrays itself (atn_scene_device_arrays)");
+        return lbvh_rebuild_list(list, k->tri_off, k->n_tri, nullptr, nullptr, false, k->box.p);
+    }
+
+    int skin_download(atn_skin h, int32_t which, void* out)
+    {
+        Skin* k = find_skin(h);
+        if (!k) return fail(ATN_ERR_INVALID_ARG, "not a live skin (destroyed, or older than the last atn_upload_scene)");
+        if (!out || which < 0 || which > 8) return fail(ATN_ERR_INVALID_ARG, "atn_skin_download: null output or unknown buffer");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        const size_t vb = (size_t)k->n_vtx * sizeof(float4);
+        if (which == 0) ATN_HIP(hipMemcpyAsync(out, vtx_pos.p + k->vtx_off, vb, hipMemcpyDeviceToHost, stream));
+        else if (which == 1) ATN_HIP(hipMemcpyAsync(out, vtx_nml.p + k->vtx_off, vb, hipMemcpyDeviceToHost, stream));
+        else if (which == 2) ATN_HIP(hipMemcpyAsync(out, k->prev.p, vb, hipMemcpyDeviceToHost, stream));
+        else if (which == 3) ATN_HIP(hipMemcpyAsync(out, k->box.p, 6 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        // the WHOLE scene as new frames read it: what a tick must leave alone outside the skin's ranges
+        else if (which == 5) ATN_HIP(hipMemcpyAsync(out, shade_tris.p, (size_t)n_scene_tris * kShadeTriQuads * sizeof(float4), hipMemcpyDeviceToHost, stream));
+        else if (which == 6) ATN_HIP(hipMemcpyAsync(out, vtx_pos.p, (size_t)n_scene_vtx * sizeof(float4), hipMemcpyDeviceToHost, stream));
+        else if (which == 7) ATN_HIP(hipMemcpyAsync(out, vtx_nml.p, (size_t)n_scene_vtx * sizeof(float4), hipMemcpyDeviceToHost, stream));
+        else if (which == 8) ATN_HIP(hipMemcpyAsync(out, tris.p, (size_t)n_scene_tris * sizeof(atn_triangle_param), hipMemcpyDeviceToHost, stream));
+        else {
+            std::vector<atn_triangle_param> tr(k->n_tri);
+            if (k->n_tri) ATN_HIP(hipMemcpyAsync(tr.data(), tris.p + k->tri_off, (size_t)k->n_tri * sizeof(atn_triangle_param), hipMemcpyDeviceToHost, stream));
+            ATN_HIP(hipStreamSynchronize(stream));
+            for (uint32_t t = 0; t < k->n_tri; t++) static_cast<float*>(out)[t] = tr[t].area;
+        }
+        ATN_HIP(hipStreamSynchronize(stream));
+        return ATN_OK;
+    }
+
+    int download_list(uint32_t list, void* out, uint32_t capacity, uint32_t* n_bytes)
+    {
+        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+        if (list == 0 || list >= list_base.size()) return fail(ATN_ERR_INVALID_ARG, "not a bottom-level BVH list");
+        const int32_t twin_word = list < list_twin_delta.size() ? list_twin_delta[list] : 0;
+        const uint32_t twin_delta = (uint32_t)(twin_word & ~15), twin_dirs = twin_word == 0 ? 0u : ((twin_word & 1) ? 8u : 1u);
+        const uint64_t bytes = twin_dirs ? (uint64_t)twin_delta * (1u + twin_dirs) : list_bytes[list];
+        if ((uint64_t)list_base[list] + bytes > nodes.n * sizeof(float4)) return fail(ATN_ERR_UNSUPPORTED, "the list's region leaves the node image (internal)");
+        if (n_bytes) *n_bytes = (uint32_t)bytes;
+        if (!out) return ATN_OK;
+        if (capacity < bytes) return fail(ATN_ERR_INVALID_ARG, "output buffer too small for the list");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        ATN_HIP(hipMemcpyAsync(out, reinterpret_cast<char*>(nodes.p) + list_base[list], bytes, hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
         return ATN_OK;
     }
 
@@ -2656,6 +2859,42 @@ int atn_lbvh_build(atn_ctx* ctx, const atn_triangle_param* triangles, uint32_t n
     CTX_QUIET_OR_FAIL(ctx);
     return guarded(ctx, [&] { return ctx->r.lbvh_build(triangles, n_triangles, tri_id_offset, bbox_min, bbox_max, vtx_pos, n_vertices, vtx_offset,
                                                        out_nodes, out_sorted_codes, out_sorted_indices); });
+}
+int atn_skin_create(atn_ctx* ctx, const atn_skinning_vertex* vertices, uint32_t n_vertices, uint32_t vtx_offset, uint32_t tri_offset, uint32_t n_triangles,
+                    uint32_t n_matrices, atn_skin* out_skin)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.skin_create(vertices, n_vertices, vtx_offset, tri_offset, n_triangles, n_matrices, out_skin); });
+}
+int atn_skin_update(atn_ctx* ctx, atn_skin skin, const atn_mat4* matrices, uint32_t n)
+{
+    CTX_OR_FAIL(ctx);      // enqueued behind the frames in flight, like the other scene updates
+    return guarded(ctx, [&] { return ctx->r.skin_update(skin, matrices, n); });
+}
+int atn_skin_compute(atn_ctx* ctx, atn_skin skin, int32_t is_restart, float* bbox_min, float* bbox_max)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.skin_compute(skin, is_restart != 0, bbox_min, bbox_max); });
+}
+int atn_lbvh_rebuild_list_skinned(atn_ctx* ctx, uint32_t list_index, atn_skin skin)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.lbvh_rebuild_list_skinned(list_index, skin); });
+}
+int atn_skin_download(atn_ctx* ctx, atn_skin skin, int32_t which, void* out_host)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.skin_download(skin, which, out_host); });
+}
+int atn_skin_download_list(atn_ctx* ctx, uint32_t list_index, void* out_host, uint32_t capacity_bytes, uint32_t* n_bytes)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.download_list(list_index, out_host, capacity_bytes, n_bytes); });
+}
+int atn_skin_destroy(atn_ctx* ctx, atn_skin skin)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.skin_destroy(skin); });
 }
 int atn_scene_device_arrays(atn_ctx* ctx, void** vtx_pos, void** vtx_nml, void** triangles)
 {

@@ -151,4 +151,27 @@ void vol_launch_transmit(const VolLaunch& l, hipStream_t st, const PathBuffers& 
 void vol_launch_reduce(const VolLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va);
 void vol_launch_phase_table(hipStream_t st, float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo, float* out_dir, float* out_eval);
 
+// ---- skinning.hip (device/skinning.hpp) ----
+struct SkinVtxArgs;
+struct SkinTriArgs;
+// one skinning tick's two launches: a block of 256 per 256 vertices / triangles (the triangle pass always has its block 0: it
+// finishes the box), the palette in LDS when it fits
+struct SkinLaunch {
+    uint32_t vtx_grid, tri_grid;
+    bool palette_lds;
+};
+inline SkinLaunch skin_launch(uint32_t n_vtx, uint32_t n_tri, uint32_t n_matrices, uint32_t palette_lds_max)
+{
+    SkinLaunch l{};
+    l.vtx_grid = (n_vtx + 255u) / 256u;
+    l.tri_grid = n_tri ? (n_tri + 255u) / 256u : 1u;
+    l.palette_lds = n_matrices <= palette_lds_max;
+    return l;
+}
+void skin_launch_vertices(const SkinLaunch& l, hipStream_t st, const SkinVtxArgs& a);
+void skin_launch_triangles(const SkinLaunch& l, hipStream_t st, const SkinTriArgs& a);
+// k_lbvh_morton with the box in device memory (min xyz, max xyz)
+void skin_launch_morton(hipStream_t st, const atn_triangle_param* tris, const float4* vtx, int32_t vtx_offset, uint32_t n, const float* box,
+                        uint32_t* codes, uint32_t* indices);
+
 } // namespace atn

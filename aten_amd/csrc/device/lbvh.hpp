@@ -67,6 +67,7 @@ __device__ __forceinline__ void lbvh_triangle_box(const atn_triangle_param* tris
     mx = mk3(fmaxf(fmaxf(v0.x, v1.x), v2.x), fmaxf(fmaxf(v0.y, v1.y), v2.y), fmaxf(fmaxf(v0.z, v1.z), v2.z));
 }
 
+#ifndef ATN_LBVH_HELPERS_ONLY     // (skinning.hip takes the helpers above for its Morton pass; the kernels belong to aten_amd.hip)
 __global__ __launch_bounds__(256) void k_lbvh_morton(const atn_triangle_param* __restrict__ tris, const float4* __restrict__ vtx,
                                                      int32_t vtx_offset, uint32_t n, f3 bmin, f3 bmax,
                                                      uint32_t* __restrict__ codes, uint32_t* __restrict__ indices)
@@ -456,5 +457,6 @@ __global__ __launch_bounds__(256) void k_lbvh_twin_emit(uint32_t n, LbvhTopo t, 
         q[2] = make_float4(c.x - a.x, c.y - a.y, c.z - a.z, 0.0F);
     }
 }
+#endif  // ATN_LBVH_HELPERS_ONLY
 
 } // namespace atn

@@ -73,6 +73,12 @@ INTERSECTION = np.dtype([
 
 RAY = np.dtype([("org", f4, 3), ("dir", f4, 3)])
 
+# aten::SkinningVertex, 72 B (src/libaten/deformable/SkinningVertex.h:7-14)
+SKINNING_VERTEX = np.dtype([
+    ("position", f4, 4), ("normal", f4, 3), ("clr", np.uint8, 4), ("uv", f4, 2),
+    ("blend_index", f4, 4), ("blend_weight", f4, 4),
+])
+
 assert VEC4.itemsize == 16 and MAT4.itemsize == 64
 assert BVH_NODE.itemsize == 48
 assert OBJECT_PARAM.itemsize == 64
@@ -82,6 +88,7 @@ assert MATERIAL_PARAM.fields["medium"][1] == 108 and MATERIAL_PARAM.fields["toon
 assert LIGHT_PARAM.itemsize == 80 and LIGHT_PARAM.fields["attrib"][1] == 56
 assert CAMERA_PARAM.itemsize == 124
 assert INTERSECTION.itemsize == 32 and RAY.itemsize == 24
+assert SKINNING_VERTEX.itemsize == 72 and SKINNING_VERTEX.fields["blend_index"][1] == 40
 
 # enums (include/aten_layout.h)
 OBJ_POLYGONS, OBJ_INSTANCE, OBJ_SPHERE = 0, 1, 2

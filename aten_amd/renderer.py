@@ -28,6 +28,7 @@ class PathTracing:
         if self._l.atn_sizeof_destination() != C.sizeof(Destination):
             raise AtenAmdError("atn_destination ABI mismatch")
         self.width = self.height = 0
+        self._skin_sizes = {}       # skin handle -> (vertices, triangles), for skin_buffer's output shapes
 
     def close(self):
         if self._ctx:
@@ -89,6 +90,64 @@ class PathTracing:
         self._check(self._l.atn_lbvh_build(self._ctx, tr.ctypes.data, n, tri_id_offset, f3(bbox_min), f3(bbox_max), pos.ctypes.data, len(pos),
                                            vtx_offset, out.ctypes.data, codes.ctypes.data, idx.ctypes.data))
         return (out, codes, idx) if with_keys else out
+
+    # ---- skinning on the device (idaten::Skinning, src/libidaten/kernel/Skinning.cu; docs/SKINNING.md)
+    def skin_create(self, vertices, vtx_offset, tri_offset, n_triangles, n_matrices):
+        """Skinning::initWithTriangles + setVtxOffset: binds SkinningVertex records to a vertex / triangle range of the uploaded
+        scene; returns the skin's handle."""
+        v = np.ascontiguousarray(vertices, L.SKINNING_VERTEX)
+        h = C.c_uint32(0)
+        self._check(self._l.atn_skin_create(self._ctx, v.ctypes.data, len(v), vtx_offset, tri_offset, n_triangles, n_matrices, C.byref(h)))
+        self._skin_sizes[h.value] = (len(v), n_triangles)
+        return h.value
+
+    def skin_update(self, skin, matrices):
+        """Skinning::update: the mat4 palette of the next skin_compute."""
+        m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 4, 4)
+        self._check(self._l.atn_skin_update(self._ctx, skin, m.ctypes.data, len(m)))
+
+    def skin_compute(self, skin, is_restart=False, want_bbox=True):
+        """Skinning::compute on the device, behind the frames in flight.  want_bbox: wait and return (min, max) as the reference
+        does; False: return None at once, the box stays in device memory (lbvh_rebuild_list_skinned reads it there)."""
+        if not want_bbox:
+            self._check(self._l.atn_skin_compute(self._ctx, skin, int(bool(is_restart)), None, None))
+            return None
+        mn, mx = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._check(self._l.atn_skin_compute(self._ctx, skin, int(bool(is_restart)), mn.ctypes.data, mx.ctypes.data))
+        return mn, mx
+
+    def lbvh_rebuild_list_skinned(self, list_index, skin):
+        """lbvh_rebuild_list over the skin's triangles, normalised by the skin's box as it lies in device memory."""
+        self._check(self._l.atn_lbvh_rebuild_list_skinned(self._ctx, list_index, skin))
+
+    def skin_buffer(self, skin, name):
+        """For tests: "pos", "nml", "prev" (float32 [n, 4]), "bbox" (float32 [6]) or "area" (float32 [n_triangles])."""
+        which = {"pos": 0, "nml": 1, "prev": 2, "bbox": 3, "area": 4}[name]
+        nv, nt = self._skin_sizes.get(skin, (0, 0))
+        out = np.zeros((max(nv, 1), 4), np.float32) if which < 3 else np.zeros(6 if which == 3 else max(nt, 1), np.float32)
+        self._check(self._l.atn_skin_download(self._ctx, skin, which, out.ctypes.data))
+        return out[:nv] if which < 3 else (out if which == 3 else out[:nt])
+
+    def skin_scene_arrays(self, skin, n_vertices, n_triangles):
+        """For tests: the whole scene on the device as new frames read it -- dict(shade float32 [T, 8, 4], vtx_pos / vtx_nml float32
+        [V, 4], triangles TRIANGLE_PARAM [T]) for a scene of V vertices and T triangles."""
+        out = dict(shade=np.zeros((n_triangles, 8, 4), np.float32), vtx_pos=np.zeros((n_vertices, 4), np.float32),
+                   vtx_nml=np.zeros((n_vertices, 4), np.float32), triangles=np.zeros(n_triangles, L.TRIANGLE_PARAM))
+        for which, k in ((5, "shade"), (6, "vtx_pos"), (7, "vtx_nml"), (8, "triangles")):
+            self._check(self._l.atn_skin_download(self._ctx, skin, which, out[k].ctypes.data))
+        return out
+
+    def bvh_list_bytes(self, list_index):
+        """For tests: the bytes of a bottom-level list in the device's node image, any-hit twins included."""
+        n = C.c_uint32(0)
+        self._check(self._l.atn_skin_download_list(self._ctx, list_index, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        self._check(self._l.atn_skin_download_list(self._ctx, list_index, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def skin_close(self, skin):
+        self._check(self._l.atn_skin_destroy(self._ctx, skin))
+        self._skin_sizes.pop(skin, None)
 
     def scene_device_arrays(self):
         """(vtx_pos, vtx_nml, triangles) device addresses of the uploaded scene."""

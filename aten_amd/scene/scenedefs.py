@@ -439,6 +439,88 @@ def deformable_room(t=0.0, asset_dir=None, **blob):
     return b, oid, cam
 
 
+def _skin_chain(n_bones, base=(0.33, 0.12, 0.3), height=1.5):
+    """Joint j of the bone chain in the bind pose: `base` + j * (0, height / n_bones, 0)."""
+    return np.asarray(base, np.float64), float(height) / n_bones
+
+
+def skinned_pose(t, n_bones):
+    """The mat4 palette of skinned_room's bone chain at phase t: palette[j] = (joint j's pose) * (joint j's bind pose)^-1, each
+    joint bending a little further than its parent around z and x.  skinned_pose(0, n) is not the identity (the chain has a
+    phase per joint); an all-identity palette returns the rest pose.  float32 [n_bones, 4, 4], row-major, applied as M * p."""
+    base, seg = _skin_chain(n_bones)
+
+    def trans(v):
+        m = np.eye(4); m[:3, 3] = v
+        return m
+
+    def rot(az, ax):
+        cz, sz, cx, sx = np.cos(az), np.sin(az), np.cos(ax), np.sin(ax)
+        rz = np.array([[cz, -sz, 0, 0], [sz, cz, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1.0]])
+        rx = np.array([[1, 0, 0, 0], [0, cx, -sx, 0], [0, sx, cx, 0], [0, 0, 0, 1.0]])
+        return rz @ rx
+    out = np.zeros((n_bones, 4, 4), np.float32)
+    world = trans(base)
+    for j in range(n_bones):
+        amp = 0.7 / n_bones
+        world = world @ (trans((0.0, seg, 0.0)) if j else np.eye(4)) @ rot(amp * np.sin(t + 0.6 * j), 0.6 * amp * np.cos(0.7 * t + 0.4 * j))
+        out[j] = (world @ trans(-(base + np.array([0.0, j * seg, 0.0])))).astype(np.float32)
+    return out
+
+
+def skinned_room(nu=48, nv=24, n_bones=8, asset_dir=None, radius=0.13):
+    """The Cornell box with a skinned tube in it: the stand-in for the reference's skinned character (asset/converted_unitychan, a
+    blob that is absent from the snapshot) in the deformation-renderer sequence, with what a character has -- a bone chain, a
+    weight falloff over two to four bones, and rings of vertices bound to a single bone.
+    2 nu nv triangles, built with add_mesh(deformable=True).  Returns (builder, tube object id, camera, vertices): `vertices`
+    is the aten::SkinningVertex array (layout.SKINNING_VERTEX) in the order of the scene's vertices of the tube -- the builder
+    stores three vertices per triangle -- for atn_skin_create; skinned_pose(t, n_bones) is its palette."""
+    asset_dir = asset_dir or os.path.join(ASSETS, "cornellbox")
+    b = SceneBuilder()
+    emit = b.add_material("light", L.MTRL_EMISSIVE, (1.0, 1.0, 1.0))
+    objs = b.load_obj(os.path.join(asset_dir, "orig.obj"), create_mtrl=lambda name, mt, clr, a, n: b.add_material(name, mt, clr),
+                      separate_objs=True, normal_on_the_fly=True)
+    light = b.create_instance(objs[0])
+    b.add_area_light(light, b.materials[emit][1]["baseColor"][:3], 200.0)
+    for o in objs[1:]:
+        b.create_instance(o)
+    mtrl = b.add_material("skin", L.MTRL_GGX, (0.8, 0.45, 0.3), roughness=0.35, ior=1.4)
+    base, seg = _skin_chain(n_bones)
+    f = np.float32
+    ph = (np.arange(nu, dtype=np.float64) / nu) * 2 * np.pi
+    hv = np.arange(nv + 1, dtype=np.float64) / nv
+    HV, PH = np.meshgrid(hv, ph, indexing="ij")
+    d = np.stack([np.cos(PH), np.zeros_like(PH), np.sin(PH)], axis=-1)
+    pos = (base[None, None, :] + radius * d + np.stack([np.zeros_like(HV), HV * seg * n_bones, np.zeros_like(HV)], -1)).reshape(-1, 3).astype(f)
+    nml = d.reshape(-1, 3).astype(f)
+    uv = np.stack([PH / (2 * np.pi), HV], -1).reshape(-1, 2).astype(f)
+    idx = []
+    for i in range(nv):
+        for j in range(nu):
+            a, c = i * nu + j, i * nu + (j + 1) % nu
+            idx.append((a, a + nu, c)); idx.append((c, a + nu, c + nu))
+    idx = np.asarray(idx, np.int64)
+    # weights: a tent of half-width 2 bones around the vertex (two to four bones); every fourth ring of vertices follows its bone alone
+    s = np.clip(HV.reshape(-1) * n_bones, 0.0, n_bones - 1e-6)
+    b0 = np.floor(s).astype(np.int64)
+    cand = b0[:, None] + np.array([-1, 0, 1, 2])[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs(s[:, None] - (cand + 0.5)) / 2.0)
+    w[(cand < 0) | (cand >= n_bones)] = 0.0
+    single = (np.arange(nv + 1)[:, None] % 4 == 2).repeat(nu, 1).reshape(-1)
+    w[single] = np.array([0.0, 1.0, 0.0, 0.0])
+    w /= w.sum(1, keepdims=True)
+    cand = np.clip(cand, 0, n_bones - 1)        # (a weight of 0 still names a matrix: all four are read)
+    sv = np.zeros(len(pos), L.SKINNING_VERTEX)
+    sv["position"][:, :3] = pos; sv["position"][:, 3] = 1.0
+    sv["normal"] = nml; sv["clr"] = 255; sv["uv"] = uv
+    sv["blend_index"] = cand.astype(f); sv["blend_weight"] = w.astype(f)
+    oid = b.add_mesh("tube", pos, idx, mtrl, normals=nml, uvs=uv, deformable=True)
+    b.create_instance(oid)
+    b.set_background((0.0, 0.0, 0.0))
+    cam = dict(pos=(0.0, 1.0, 3.0), at=(0.0, 1.0, 0.0), vfov=45.0)
+    return b, oid, cam, np.ascontiguousarray(sv[idx.reshape(-1)])
+
+
 def toon_ramp(steps=(0.15, 0.45, 0.8, 1.0), width=64, tint=(1.0, 1.0, 1.0)):
     """A 1-D remap texture (ToonParameter::remap_texture): `width` texels in `len(steps)` flat bands."""
     t = np.ones((1, width, 4), np.float32)

@@ -116,6 +116,41 @@ int atn_lbvh_build(atn_ctx* ctx, const atn_triangle_param* triangles, uint32_t n
                    const float bbox_min[3], const float bbox_max[3], const atn_vec4* vtx_pos, uint32_t n_vertices, int32_t vtx_offset,
                    atn_bvh_node* out_nodes, uint32_t* out_sorted_codes, uint32_t* out_sorted_indices);
 
+/* ---- skinning on the device: the first step of that sequence (idaten::Skinning, src/libidaten/kernel/Skinning.cu; docs/SKINNING.md).
+ * A tick uploads one matrix per bone; the skinned vertices, the triangles' areas, the shading records and the mesh's box are
+ * computed in device memory behind the frames in flight.  A skin is named by a handle (never 0); it dies with atn_skin_destroy
+ * and with every atn_upload_scene, and every call on a dead handle returns ATN_ERR_INVALID_ARG.  Refused (ATN_ERR_UNSUPPORTED):
+ * a context whose scene arrays the caller writes itself (atn_scene_device_arrays).  There is no atn_mgpu_* form.
+ * Additive entry points: atn_abi_version stays 3. */
+typedef uint32_t atn_skin;
+/* ≙ Skinning::initWithTriangles + setVtxOffset: binds `vertices` to vertices [vtx_offset, vtx_offset + n_vertices) and triangles
+ * [tri_offset, tri_offset + n_triangles) of the uploaded scene (n_triangles may be 0).  The scene's triangles hold final vertex
+ * indices: there is no index offset to maintain.  Checked here, once, on the host -- nothing out of range reaches a kernel:
+ * ATN_ERR_INVALID_ARG for a range outside the scene or a triangle of the range naming a vertex outside the skin's vertices,
+ * ATN_ERR_UNSUPPORTED for an (int)blend_index outside [0, n_matrices) (also under a weight of 0: all four matrices are read) or
+ * n_matrices > 65536.  Waits for the frames in flight. */
+int atn_skin_create(atn_ctx* ctx, const atn_skinning_vertex* vertices, uint32_t n_vertices, uint32_t vtx_offset,
+                    uint32_t tri_offset, uint32_t n_triangles, uint32_t n_matrices, atn_skin* out_skin);
+/* ≙ Skinning::update: the palette for the next atn_skin_compute; n must be the skin's n_matrices.  Enqueued; `matrices` is free on return. */
+int atn_skin_update(atn_ctx* ctx, atn_skin skin, const atn_mat4* matrices, uint32_t n);
+/* ≙ Skinning::compute, enqueued behind the frames in flight: writes the skin's range of the scene's vertex positions (w = uv[0]) and
+ * normals (w = uv[1]), the triangles' areas (|cross|, not halved) and shading records, keeps the previous positions (is_restart: the
+ * new ones; otherwise the positions before this call, w = 1) and leaves the mesh's box in device memory.  With bbox_min and bbox_max
+ * it then waits and returns the box (the reference's read-back); with both NULL it returns at once.  ATN_ERR_INVALID_ARG before the
+ * first atn_skin_update.  Bottom-level lists over the triangles must be rebuilt before the next render. */
+int atn_skin_compute(atn_ctx* ctx, atn_skin skin, int32_t is_restart, float bbox_min[3], float bbox_max[3]);
+/* atn_lbvh_rebuild_list over the skin's triangles with the Morton codes normalised by the skin's box AS IT IS IN DEVICE MEMORY (after
+ * atn_skin_compute): no read-back.  Same tree, same refusals. */
+int atn_lbvh_rebuild_list_skinned(atn_ctx* ctx, uint32_t list_index, atn_skin skin);
+/* For tests; waits for everything.  which = 0 positions, 1 normals, 2 previous positions (atn_vec4[n_vertices]), 3 the box
+ * (float[6]: min, max), 4 the triangles' areas (float[n_triangles]); and of the WHOLE scene as new frames read it: 5 the shading
+ * records (8 atn_vec4 per triangle), 6 positions, 7 normals (atn_vec4 per vertex), 8 triangles (atn_triangle_param). */
+int atn_skin_download(atn_ctx* ctx, atn_skin skin, int32_t which, void* out_host);
+/* For tests; waits for everything.  The bytes of bottom-level list `list_index` in the node image, any-hit twins included;
+ * out_host may be NULL (size only). */
+int atn_skin_download_list(atn_ctx* ctx, uint32_t list_index, void* out_host, uint32_t capacity_bytes, uint32_t* n_bytes);
+int atn_skin_destroy(atn_ctx* ctx, atn_skin skin);
+
 /* ≙ aten::initSampler(width, height, seed) (src/libaten/sampler/sampler.cpp:8-18) followed by
  * idaten::PathTracing::initSamplerParameter's upload of aten::getRandom()
  * (src/libidaten/kernel/renderer.h:113-124): one std::mt19937(seed) draw per pixel. */

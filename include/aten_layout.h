@@ -74,6 +74,17 @@ typedef struct atn_triangle_param {
     int32_t mesh_id;
 } atn_triangle_param;
 
+/* ---- aten::SkinningVertex, 72 B, align 4 (src/libaten/deformable/SkinningVertex.h:7-14).  blend_index holds matrix indices as
+ * floats (the kernel converts with (int)); all four matrices are read, also where a weight is 0 (Skinning.cu:31-39). */
+typedef struct atn_skinning_vertex {
+    float position[4];
+    float normal[3];
+    uint8_t clr[4];
+    float uv[2];
+    float blend_index[4];
+    float blend_weight[4];
+} atn_skinning_vertex;
+
 /* ---- aten::MaterialParameter, 248 B, align 4 (src/libaten/material/material.h:234-317) */
 enum {
     ATN_MTRL_EMISSIVE = 0, ATN_MTRL_DIFFUSE = 1, ATN_MTRL_OREN_NAYAR = 2, ATN_MTRL_SPECULAR = 3,
@@ -298,6 +309,9 @@ static_assert(sizeof(atn_object_param) == 64, "ObjectParameter");
 static_assert(offsetof(atn_object_param, light_id) == 24, "ObjectParameter.light_id");
 static_assert(offsetof(atn_object_param, sphere) == 32, "ObjectParameter.sphere");
 static_assert(sizeof(atn_triangle_param) == 32, "TriangleParameter");
+static_assert(sizeof(atn_skinning_vertex) == 72, "SkinningVertex");
+static_assert(offsetof(atn_skinning_vertex, normal) == 16 && offsetof(atn_skinning_vertex, clr) == 28 && offsetof(atn_skinning_vertex, uv) == 32
+              && offsetof(atn_skinning_vertex, blend_index) == 40 && offsetof(atn_skinning_vertex, blend_weight) == 56, "SkinningVertex members");
 static_assert(sizeof(atn_standard_mtrl) == 48, "StandardMaterialParameter");
 static_assert(sizeof(atn_material_param) == 248, "MaterialParameter");
 static_assert(offsetof(atn_material_param, type) == 16, "MaterialParameter.type");

@@ -22,6 +22,7 @@
 #include "device/svgf.hpp"
 #include "device/restir.hpp"
 #include "device/npr.hpp"
+#include "device/ao.hpp"
 #include "device/volume.hpp"
 #include "device/lbvh.hpp"
 #include "device/skinning.hpp"
@@ -680,6 +681,7 @@ public:
         }
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (rs_ev) (void)hipEventDestroy(rs_ev);
+        if (ao_ev) (void)hipEventDestroy(ao_ev);
         if (ev_gather) (void)hipEventDestroy(ev_gather);
         for (auto& e : sv_ev_prepare) if (e) (void)hipEventDestroy(e);
         if (ev_film) (void)hipEventDestroy(ev_film);
@@ -2743,6 +2745,169 @@ public:
         return ATN_OK;
     }
 
+    // ------------------------------------------------------------------------------------------------
+    // Ambient occlusion (aten::AORenderer / idaten::AORenderer, device/ao.hpp; docs/AO.md): the ray list, the per-slot and per-pixel
+    // planes.  The state is shared by the banks: an event orders consecutive AO frames.
+    // ------------------------------------------------------------------------------------------------
+    DevBuf<float4> ao_ray_o, ao_ray_d, ao_ray_n, ao_ray_res, ao_st_ray, ao_st_ans;
+    DevBuf<uint32_t> ao_work, ao_row_min, ao_counters, ao_state;
+    DevBuf<float> ao_depth_s, ao_value, ao_depth;
+    int32_t ao_num_rays = 1, ao_filter = 0;     // AORenderer's member defaults (aorenderer.h) and its active branch
+    float ao_radius = 1.0F;
+    size_t ao_rays_cap = 0;
+    uint32_t ao_slots = 0;
+    int32_t ao_w = 0, ao_h = 0, ao_capture = 0;
+    bool ao_captured = false, ao_pending = false, ao_rendered = false;
+    hipEvent_t ao_ev = nullptr;     // the last AO frame's kernels are done with the AO state (the next frame waits for it)
+
+    int ao_set_params(int32_t num_rays, float radius, int32_t filter)
+    {
+        if (num_rays < 1 || num_rays > kAoMaxRays) return fail(ATN_ERR_INVALID_ARG, "AO: num_rays must be 1..64");
+        if (!(radius > 0.0F) || !std::isfinite(radius)) return fail(ATN_ERR_INVALID_ARG, "AO: the radius must be positive and finite");
+        if (filter != 0 && filter != 1) return fail(ATN_ERR_INVALID_ARG, "AO: filter is 0 or 1");
+        ao_num_rays = num_rays; ao_radius = radius; ao_filter = filter;
+        return ATN_OK;
+    }
+
+    // the planes start at zero (path_host_'s contributions, the film) and persist across frames
+    int ao_ensure(int32_t w, int32_t h)
+    {
+        const size_t r = (size_t)ao_num_rays * n_slots;
+        if (r > (size_t)kAoRayMask) return fail(ATN_ERR_UNSUPPORTED, "AO frames list at most 2^28 rays (fewer rays per pixel, or a smaller frame)");
+        if (r > ao_rays_cap) {
+            ATN_HIP(ao_ray_o.resize(r)); ATN_HIP(ao_ray_d.resize(r)); ATN_HIP(ao_ray_n.resize(r)); ATN_HIP(ao_ray_res.resize(r));
+            ao_rays_cap = r;
+        }
+        if (n_slots != ao_slots) { ATN_HIP(ao_work.resize(n_slots)); ATN_HIP(ao_depth_s.resize(n_slots)); ao_slots = n_slots; }
+        if (!ao_counters.p) ATN_HIP(ao_counters.resize(kAoCounters));
+        const size_t n = (size_t)w * h;
+        if (w != ao_w || h != ao_h) {
+            ATN_HIP(ao_state.resize(n)); ATN_HIP(ao_value.resize(n)); ATN_HIP(ao_depth.resize(n)); ATN_HIP(ao_row_min.resize((size_t)h));
+            ATN_HIP(hipMemsetAsync(ao_state.p, 0, n * sizeof(uint32_t), stream));
+            ATN_HIP(hipMemsetAsync(ao_value.p, 0, n * sizeof(float), stream));
+            ATN_HIP(hipMemsetAsync(ao_depth.p, 0, n * sizeof(float), stream));
+            ao_w = w; ao_h = h;
+        }
+        if (ao_capture) { ATN_HIP(ao_st_ray.resize(2 * n)); ATN_HIP(ao_st_ans.resize(n)); }
+        return ATN_OK;
+    }
+
+    // ≙ AORenderer::RenderAO / RenderAOWithBilateralFilter (aorenderer.cpp:71-275) in idaten::AORenderer's wavefront shape: a fixed
+    // number of launches, nothing is read back
+    int ao_render(const atn_destination* dst, atn_vec4* out_host)
+    {
+        if (!dst) return fail(ATN_ERR_INVALID_ARG, "null destination");
+        atn_destination d1 = *dst;      // the reference reads neither sample nor maxDepth
+        d1.maxDepth = 1; d1.russianRouletteDepth = 1; d1.sample = 1;
+        const atn_destination* d = &d1;
+        int rc = check_ready(d);
+        if (rc) return rc;
+        if (np_carpaint) return fail(ATN_ERR_UNSUPPORTED, "AO frames do not draw applyNormal's CarPaint flake samples: CarPaint materials are refused");
+        if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "AO frames need the whole frame on one GPU (atn_set_screen_shard world 1)");
+        if (regen_mode != 0) return fail(ATN_ERR_UNSUPPORTED, "AO frames have one sample per pixel: switch path regeneration off (atn_set_regeneration(0))");
+        if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "AO frames have no relaxed-math kernels: atn_set_shade_math(0)");
+        if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "AO frames do not count rays (count_stats must be 0)");
+        if (ao_filter && d->break_on_terminate) return fail(ATN_ERR_UNSUPPORTED, "AO: the bilateral filter over rows the CPU renderer leaves unwritten would filter earlier frames' planes: filter = 1 needs break_on_terminate = 0");
+        ATN_HIP(hipSetDevice(device));
+        if (frames_in_flight > 1 && (d->width != ao_w || d->height != ao_h || (size_t)ao_num_rays * n_slots > ao_rays_cap || (ao_capture && !ao_st_ans.p))) { rc = quiesce(); if (rc) return rc; }
+        rc = begin_frame(*d, frames_in_flight > 1);
+        if (rc) return rc;
+        if (frames_in_flight > 1 && (size_t)ao_num_rays * n_slots > ao_rays_cap) { rc = quiesce(); if (rc) return rc; }
+        rc = ao_ensure(d->width, d->height);
+        if (rc) return rc;
+        if (!ao_ev) ATN_HIP(hipEventCreateWithFlags(&ao_ev, hipEventDisableTiming));
+        const bool prof = d->profile != 0;
+        FrameParams fp = frame_params(*d);
+        PathBuffers pb = buffers(false);
+        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
+        fp.chunk_items = plan.shade_items;
+        AoArgs aa{};
+        aa.ray_o = ao_ray_o.p; aa.ray_d = ao_ray_d.p; aa.ray_n = ao_ray_n.p; aa.ray_res = ao_ray_res.p;
+        aa.work = ao_work.p; aa.depth_s = ao_depth_s.p; aa.row_min = ao_row_min.p; aa.counters = ao_counters.p;
+        aa.state = ao_state.p; aa.value = ao_value.p; aa.depth = ao_depth.p;
+        aa.num_rays = ao_num_rays; aa.radius = ao_radius; aa.literal = d->break_on_terminate ? 1 : 0; aa.filter = ao_filter;
+        if (ao_capture) { aa.st_ray = ao_st_ray.p; aa.st_ans = ao_st_ans.p; }
+        // the walk of the AO rays: the frame's walk, LDS copy and block, num_rays rays per path
+        const uint32_t n_rays = (uint32_t)ao_num_rays * n_slots;
+        AoLaunch al{};
+        al.grid = grid_for(n_slots); al.slot_grid = (n_slots + 255u) / 256u;
+        al.refill = plan.refill; al.lds_bytes = plan.lds_bytes;
+        al.trace_block = plan.refill ? (uint32_t)kTraceBlock : plan.block;
+        al.trace_grid = plan.refill ? trace_grid(n_rays, true) : grid_for(n_rays) * (256u / plan.block);
+
+        // the previous AO frame (another bank's stream) still reads and writes the AO state
+        if (ao_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, ao_ev, 0));
+        if (ao_capture) {
+            const size_t n = (size_t)d->width * d->height;
+            ATN_HIP(hipMemsetAsync(ao_st_ray.p, 0, 2 * n * sizeof(float4), stream));
+            ATN_HIP(hipMemsetAsync(ao_st_ans.p, 0, n * sizeof(float4), stream));
+        }
+        ATN_HIP(hipMemsetAsync(counters.p, 0, (size_t)4 * counters_depth * 4, stream));
+        ATN_HIP(hipMemsetAsync(ao_counters.p, 0, (size_t)kAoCounters * sizeof(uint32_t), stream));
+        ATN_HIP(hipMemsetAsync(ao_row_min.p, 0xff, (size_t)d->height * sizeof(uint32_t), stream));
+        prof_begin(prof, ATN_K_GEN);
+        hipLaunchKernelGGL(k_gen_path, dim3(grid_for(n_slots)), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
+        prof_end(prof);
+        prof_begin(prof, ATN_K_TRACE_CLOSEST);
+        ao_launch_primary(trace_launch(plan, 0), stream, pb, scene, aa);
+        prof_end(prof);
+        prof_begin(prof, ATN_K_SHADE);
+        ao_launch_rays(al, stream, pb, scene, fp, aa);
+        prof_end(prof);
+        rc = wait_film();
+        if (rc) return rc;
+        prof_begin(prof, ATN_K_GATHER);
+        ao_launch_resolve(al, stream, fp, aa, film.p, tile_out.p);
+        prof_end(prof);
+        ATN_HIP(hipGetLastError());
+        ATN_HIP(hipEventRecord(ao_ev, stream));
+        ao_pending = true;
+        ao_captured = ao_capture != 0;
+        ao_rendered = true;
+        rc = end_film_frame();
+        if (rc) return rc;
+        if (out_host) {
+            ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            ATN_HIP(hipStreamSynchronize(stream));
+        }
+        return ATN_OK;
+    }
+
+    // the film and the AO planes of a fresh context
+    int ao_reset()
+    {
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        if (ao_state.p) {
+            const size_t n = (size_t)ao_w * ao_h;
+            ATN_HIP(hipMemsetAsync(ao_state.p, 0, n * sizeof(uint32_t), stream));
+            ATN_HIP(hipMemsetAsync(ao_value.p, 0, n * sizeof(float), stream));
+            ATN_HIP(hipMemsetAsync(ao_depth.p, 0, n * sizeof(float), stream));
+        }
+        ao_captured = false; ao_rendered = false;
+        return reset();
+    }
+
+    int ao_download(int32_t which, void* out)
+    {
+        if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
+        if (!ao_rendered) return fail(ATN_ERR_INVALID_ARG, "no AO frame has been rendered");
+        if (which >= 4 && !ao_captured) return fail(ATN_ERR_INVALID_ARG, "the last AO frame kept no stage buffers: atn_ao_capture(ctx, 1) before the frame");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        ATN_HIP(hipStreamSynchronize(stream));
+        const size_t n = (size_t)ao_w * ao_h;
+        switch (which) {
+        case 0: ATN_HIP(hipMemcpy(out, ao_state.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 1: ATN_HIP(hipMemcpy(out, ao_value.p, n * sizeof(float), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 2: ATN_HIP(hipMemcpy(out, ao_depth.p, n * sizeof(float), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 3: ATN_HIP(hipMemcpy(out, ao_row_min.p, (size_t)ao_h * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 4: ATN_HIP(hipMemcpy(out, ao_st_ray.p, 2 * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
+        case 5: ATN_HIP(hipMemcpy(out, ao_st_ans.p, n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
+        }
+        return fail(ATN_ERR_INVALID_ARG, "no such AO buffer");
+    }
+
     // ≙ idaten::Renderer::reset, renderer.h:40-43
     int reset()
     {
@@ -3091,6 +3256,15 @@ int atn_volume_phase_table(atn_ctx* ctx, float g, uint32_t n, const float* w, co
     CTX_QUIET_OR_FAIL(ctx);
     return guarded(ctx, [&] { return ctx->r.volume_phase_table(g, n, w, r1, r2, wo, out_dir, out_eval); });
 }
+int atn_ao_set_params(atn_ctx* ctx, int32_t num_rays, float radius, int32_t filter) { CTX_QUIET_OR_FAIL(ctx); return ctx->r.ao_set_params(num_rays, radius, filter); }
+int atn_ao_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.ao_render(dst, out_host); });
+}
+int atn_ao_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.ao_reset(); }); }
+int atn_ao_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.ao_capture = on != 0; return ATN_OK; }
+int atn_ao_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.ao_download(which, out_host); }); }
 int atn_svgf_denoise(atn_ctx* ctx, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host)
 {
     CTX_QUIET_OR_FAIL(ctx);

@@ -124,6 +124,20 @@ void npr_launch_bounce(const NprLaunch& l, hipStream_t st, const PathBuffers& pb
                        const atn_camera_param& cam, const NprArgs& na, int32_t bounce);
 void npr_launch_capture0(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const NprArgs& na);
 
+// ---- ao.hip (device/ao.hpp) ----
+struct AoArgs;
+// one AO frame's launches after k_gen_path: the primary rays (the pass's first trace launch, with the AO job), shade over the queue,
+// the AO rays through the frame's walk (the plan's walk, LDS copy and block; the grid for num_rays rays per path), resolve per slot
+struct AoLaunch {
+    uint32_t grid;              // shade blocks of 256 (grid-stride over the queue)
+    uint32_t slot_grid;         // blocks of 256 over all slots (resolve, filter)
+    bool refill;
+    uint32_t trace_grid, trace_block, lds_bytes;
+};
+void ao_launch_primary(const TraceLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const AoArgs& aa);
+void ao_launch_rays(const AoLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const AoArgs& aa);
+void ao_launch_resolve(const AoLaunch& l, hipStream_t st, const FrameParams& fp, const AoArgs& aa, float4* film, float4* tile_out);
+
 // ---- volume.hip (device/volume.hpp) ----
 struct VolArgs;
 // one iteration's volume launches: the closest-hit walk and the connection walk through the frame's walk (the plan's walk, LDS copy and

@@ -476,6 +476,53 @@ class PathTracing:
                                                    out_dir.ctypes.data, out_eval.ctypes.data))
         return out_dir, out_eval
 
+    # ---- ambient occlusion (aten::AORenderer / idaten::AORenderer; docs/AO.md)
+    def ao_set_params(self, num_rays=1, radius=1.0, filter=False):
+        """AO rays per pixel (1..64), their radius, and whether the depth-aware bilateral filter runs (AORenderer's defaults)."""
+        self._check(self._l.atn_ao_set_params(self._ctx, int(num_rays), float(radius), int(filter)))
+
+    def ao_render(self, width, height, frame=0, progressive=True, break_on_terminate=True, download=True, profile=False, count_stats=False):
+        """One AO frame into the film; returns the film [h, w, 4].  break_on_terminate=True is the CPU renderer as written: in every
+        row the pixels from the first primary miss on are not written (the Cornell box at 4:3 misses at x = 0 of every row: nothing is
+        written); False is idaten's rule: a primary miss is 1.0 and every pixel is written."""
+        d = Destination(width, height, 1, 1, 1, frame, int(progressive), int(break_on_terminate), int(count_stats), int(profile))
+        out = np.empty((height, width, 4), np.float32) if download else None
+        self._check(self._l.atn_ao_render(self._ctx, C.byref(d), out.ctypes.data if download else None))
+        self.width, self.height = width, height
+        return out
+
+    def ao_reset(self):
+        """Film and AO planes of a fresh context."""
+        self._check(self._l.atn_ao_reset(self._ctx))
+
+    def ao_capture(self, on=True):
+        """Keep the first AO ray and its answer of the next frames for ao_buffer('ray' / 'answer')."""
+        self._check(self._l.atn_ao_capture(self._ctx, int(on)))
+
+    def ao_buffer(self, name):
+        """The last AO frame's planes.  'state': uint32 [h, w], 0 not rendered / 1 hit / 2 miss; 'value': float32 [h, w], the AO value
+        handed to the film (before the filter); 'depth': float32 [h, w], the primary hit's t (inf: a miss); 'first_miss': int64 [h], the
+        row's first primary miss x (width: none).  With ao_capture: 'ray': dict org, dir [h, w, 3] of the pixel's first AO ray;
+        'answer': dict kind (0 miss / 1 hit / 2 ten skip-throughs), t, c, skips [h, w] of that ray (pixels in state 1)."""
+        w, h = self.width, self.height
+        if name in ("state", "value", "depth"):
+            out = np.empty((h, w), np.uint32 if name == "state" else np.float32)
+            self._check(self._l.atn_ao_download(self._ctx, ("state", "value", "depth").index(name), out.ctypes.data))
+            return out
+        if name == "first_miss":
+            out = np.empty(h, np.uint32)
+            self._check(self._l.atn_ao_download(self._ctx, 3, out.ctypes.data))
+            return np.minimum(out.astype(np.int64), w)
+        if name == "ray":
+            out = np.empty((h, w, 2, 4), np.float32)
+            self._check(self._l.atn_ao_download(self._ctx, 4, out.ctypes.data))
+            return dict(org=out[..., 0, :3].copy(), dir=out[..., 1, :3].copy())
+        if name == "answer":
+            out = np.empty((h, w, 4), np.float32)
+            self._check(self._l.atn_ao_download(self._ctx, 5, out.ctypes.data))
+            return dict(kind=out[..., 0].astype(np.int32), t=out[..., 1].copy(), c=out[..., 2].copy(), skips=out[..., 3].astype(np.int32))
+        raise ValueError("no AO buffer %r" % (name,))
+
     def svgf_denoise(self, width, height, frame=0, compute_motion=False, stages=False, download=True, profile=False):
         """The filter passes of OnRender on the buffers as they stand (svgf_upload / a previous path pass)."""
         d = Destination(width, height, 1, 1, 1, frame, 0, 1, 0, int(profile))

@@ -713,3 +713,27 @@ def absorbing_slab(sigma=1.0, thickness=1.0, bg=(1.0, 1.0, 1.0), half=50.0):
     b.create_instance(b.add_mesh("slab", p, tri, m))
     b.set_background(bg)
     return b.build(), dict(pos=(0.0, 0.0, 2.0), at=(0.0, 0.0, 0.0), vfov=45.0)
+
+
+def ao_room(asset_dir=None, pane_height=0.25):
+    """toon_room(alpha_blocker=True)'s geometry with plain diffuse materials: the AO test scene (PathTracing.ao_render).  The
+    half-transparent pane (alpha 0.5) hangs `pane_height` above the floor: AO rays that start under it pass through it
+    (material::isTranslucentByAlpha).  At the default height and an AO radius of 1.0 the CPU twin counts far more than 50 such rays
+    at 64 x 48 (the CPU tests assert it)."""
+    asset_dir = asset_dir or os.path.join(ASSETS, "cornellbox")
+    b = SceneBuilder()
+    emit = b.add_material("light", L.MTRL_EMISSIVE, (1.0, 1.0, 1.0))
+    objs = b.load_obj(os.path.join(asset_dir, "orig.obj"), create_mtrl=lambda name, mtype, clr, albedo, nml: b.add_material(name, L.MTRL_DIFFUSE, clr),
+                      separate_objs=True, normal_on_the_fly=True)
+    light = b.create_instance(objs[0])
+    b.add_area_light(light, b.materials[emit][1]["baseColor"][:3], 200.0)
+    for o in objs[1:]:
+        b.create_instance(o)
+    glass = b.add_material("pane", L.MTRL_DIFFUSE, (0.9, 0.9, 0.9, 0.5))
+    b.config.enable_alpha_blending = 1
+    y = float(pane_height)
+    q = np.array([[-0.6, y, -0.4], [0.6, y, -0.4], [0.6, y, 0.6], [-0.6, y, 0.6]], np.float32)
+    b.create_instance(b.add_mesh("pane", q, [[0, 1, 2], [0, 2, 3]], glass))
+    b.set_background((0.0, 0.0, 0.0))
+    cam = dict(pos=(0.0, 1.0, 3.0), at=(0.0, 1.0, 0.0), vfov=45.0)
+    return b.build(), cam

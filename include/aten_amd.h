@@ -438,6 +438,33 @@ int atn_volume_capture(atn_ctx* ctx, int32_t iteration);
 int atn_volume_download(atn_ctx* ctx, int32_t which, void* out_host);
 int atn_volume_phase_table(atn_ctx* ctx, float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo,
                            float* out_dir, float* out_eval);
+
+/* ---- Ambient occlusion (aten::AORenderer / idaten::AORenderer; docs/AO.md) ----------------------------------------------------
+ * Per pixel: the primary hit, num_rays cosine-weighted AO rays of length `radius` from it, ao = sum of t / radius * c / pdf over the
+ * rays that hit (a ray that misses SETS the value to 1), / num_rays; hits on translucent-by-alpha materials are skipped through, up to
+ * 10 walks per ray.  One sample per pixel.
+ *   atn_ao_set_params: num_rays 1..64 (default 1), radius > 0 and finite (default 1.0), filter 0 / 1 (default 0: RenderAO; 1:
+ *                      RenderAOWithBilateralFilter's two 7-tap depth-aware passes and its halving).  ATN_ERR_INVALID_ARG otherwise.
+ *   atn_ao_render: one frame; reads dst->frame, width, height, progressive (atn_render's film rules) and break_on_terminate; sample
+ *                  and maxDepth are ignored.  break_on_terminate = 1 is the CPU renderer as written: in every row the pixels from the
+ *                  first primary miss on are NOT written and keep what the film held (zero in a fresh context and after
+ *                  atn_ao_reset) -- the Cornell box at 4:3 has a miss at x = 0 of every row, so nothing is written there.
+ *                  break_on_terminate = 0 is idaten's rule: a primary miss is 1.0 and every pixel is written.  ATN_ERR_UNSUPPORTED
+ *                  for a screen shard with world > 1, path regeneration, relaxed shade math, count_stats, CarPaint materials, and
+ *                  filter = 1 together with break_on_terminate = 1.
+ *   atn_ao_reset: the film and the AO planes start over (a fresh context's)
+ *   atn_ao_capture: keep the first AO ray and its answer of the next frames (tests)
+ *   atn_ao_download: which = 0 uint32[w*h] the state word, 0 not rendered / 1 hit / 2 miss; 1 float[w*h] the AO value handed to the
+ *                    film (before the filter); 2 float[w*h] the primary hit's t (inf: a miss); 3 uint32[h] the row's first primary
+ *                    miss x (0xffffffff: none) -- all of the last frame, pixels not rendered keeping earlier content;  with capture
+ *                    on: 4 atn_vec4[w*h][2] the first AO ray {org, 0} {dir, 0}; 5 atn_vec4[w*h] its answer {0 miss | 1 hit | 2 ten
+ *                    skip-throughs, t, c, skip-throughs}, of pixels in state 1.
+ * Additive entry points: atn_abi_version stays 3. */
+int atn_ao_set_params(atn_ctx* ctx, int32_t num_rays, float radius, int32_t filter);
+int atn_ao_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host);
+int atn_ao_reset(atn_ctx* ctx);
+int atn_ao_capture(atn_ctx* ctx, int32_t on);
+int atn_ao_download(atn_ctx* ctx, int32_t which, void* out_host);
 /* The filter passes alone (everything of OnRender after the sample loop, svgf.cpp:515-637) on whatever the
  * path pass -- or atn_svgf_upload -- left in the buffers: contributions (which = 14: contrib.xyz, sample count),
  * the current AOVs (0, 1), primary hit positions (10), motion/depth (9).  This is how a caller that already has a

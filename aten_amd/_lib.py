@@ -32,6 +32,7 @@ SYMBOLS = [
     "atn_mgpu_update_geometry", "atn_mgpu_lbvh_rebuild_list",
     "atn_skin_create", "atn_skin_update", "atn_skin_compute", "atn_lbvh_rebuild_list_skinned", "atn_skin_download",
     "atn_skin_download_list", "atn_skin_destroy",
+    "atn_set_geometry_motion", "atn_geometry_motion_stats", "atn_geometry_motion_matrices",
     "atn_mgpu_create", "atn_mgpu_destroy", "atn_mgpu_last_error", "atn_mgpu_shard_count", "atn_mgpu_shard_device",
     "atn_mgpu_upload_scene", "atn_mgpu_update_tlas", "atn_mgpu_update_camera", "atn_mgpu_init_sampler",
     "atn_mgpu_set_random", "atn_mgpu_render", "atn_mgpu_reset", "atn_mgpu_synchronize", "atn_mgpu_film_device",
@@ -76,6 +77,9 @@ def lib():
         l.atn_skin_download.argtypes = [vp, C.c_uint32, C.c_int32, vp]
         l.atn_skin_download_list.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         l.atn_skin_destroy.argtypes = [vp, C.c_uint32]
+        l.atn_set_geometry_motion.argtypes = [vp, C.c_int32]
+        l.atn_geometry_motion_stats.argtypes = [vp, vp]
+        l.atn_geometry_motion_matrices.argtypes = [vp, vp, vp]
         l.atn_mgpu_update_geometry.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32]
         l.atn_mgpu_lbvh_rebuild_list.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
         l.atn_init_sampler.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]

@@ -26,6 +26,7 @@
 #include "device/volume.hpp"
 #include "device/lbvh.hpp"
 #include "device/skinning.hpp"
+#include "device/motion.hpp"
 #include "host/scene_upload.hpp"
 #include "host/ibl_precompute.hpp"
 
@@ -480,7 +481,135 @@ public:
         case SB_TRIS: return tris.n * sizeof(atn_triangle_param); default: return objects.n * sizeof(atn_object_param);
         }
     }
-    void log_range(int b, size_t off, size_t bytes) { if (bytes) log_now.push_back(SceneRange{ b, off, bytes }); }
+    void log_range(int b, size_t off, size_t bytes)
+    {
+        if (!bytes) return;
+        log_now.push_back(SceneRange{ b, off, bytes });
+        if (gm_on && (b == SB_VTX_POS || b == SB_MATRICES)) gm_note_range(SceneRange{ b, off, bytes });
+    }
+
+    // Geometry motion vectors (atn_set_geometry_motion, device/motion.hpp, docs/MOTION.md).  The GEOMETRY HISTORY: the scene's vertex
+    // positions and matrices as the last frame rendered with compute_motion = 2 saw them.  One per context -- SVGF and ReSTIR frames
+    // share it, and it belongs to no scene set: every update logs the ranges of SB_VTX_POS / SB_MATRICES it writes (the offsets are
+    // the same in every set), and a mode-2 frame copies exactly those, from the set it reads, behind its motion pass.  Frames are
+    // ordered through gm_ev: a frame's motion pass reads the history only after the previous frame's copies, and writes it only
+    // after the previous frame's reads -- on the device, frame after frame, like the film.
+    bool gm_on = false, gm_pending = false;
+    DevBuf<float4> gm_vtx, gm_mtx;
+    uint32_t gm_mtx_quads = 0;                  // matrices rows the history holds (scene.mtx_quads when it was last made equal)
+    std::vector<SceneRange> gm_dirty;           // written since the last mode-2 frame
+    hipEvent_t gm_ev = nullptr;                 // the last mode-2 frame is done with the history
+    DevBuf<float4> gm_ids[2], gm_rs_ids;        // ids planes: SVGF's per hand-over slot, ReSTIR's
+    float4* gm_capture = nullptr;               // run_paths: where the frame's bounce-0 hit records go (null: not captured)
+    bool gm_sv_ids[2] = { false, false }, gm_rs_has_ids = false;       // the plane holds a frame's ids
+    uint64_t gm_stats[3] = {};                  // motion passes, range copies launched, float4s copied (atn_geometry_motion_stats)
+    float gm_w2c[16] = {}, gm_prev_w2c[16] = {};    // the camera matrices of the last motion pass (atn_geometry_motion_matrices)
+
+    // A range an update wrote, for the next mode-2 frame.  The list stays short whatever the caller renders in between: a range that
+    // an entry already covers is dropped (a tick writes the ranges the tick before it wrote), and a list that still reaches
+    // kGmMaxDirty entries is merged -- overlapping ranges joined, then, if need be, one covering range per buffer.
+    static constexpr size_t kGmMaxDirty = 64;
+    void gm_note_range(const SceneRange& r)
+    {
+        for (const SceneRange& e : gm_dirty)
+            if (e.buf == r.buf && e.off <= r.off && r.off + r.bytes <= e.off + e.bytes) return;
+        gm_dirty.push_back(r);
+        if (gm_dirty.size() < kGmMaxDirty) return;
+        gm_merge_dirty();
+        if (gm_dirty.size() < kGmMaxDirty / 2) return;
+        std::vector<SceneRange> cover;
+        for (const SceneRange& e : gm_dirty) {          // (sorted by buffer and offset)
+            if (cover.empty() || cover.back().buf != e.buf) cover.push_back(e);
+            else cover.back().bytes = e.off + e.bytes - cover.back().off;
+        }
+        gm_dirty.swap(cover);
+    }
+    // sorted by buffer and offset, overlapping and adjoining ranges joined
+    void gm_merge_dirty()
+    {
+        std::sort(gm_dirty.begin(), gm_dirty.end(), [](const SceneRange& a, const SceneRange& b) { return a.buf != b.buf ? a.buf < b.buf : a.off < b.off; });
+        size_t k = 0;
+        for (size_t i = 0; i < gm_dirty.size(); i++) {
+            if (k && gm_dirty[k - 1].buf == gm_dirty[i].buf && gm_dirty[i].off <= gm_dirty[k - 1].off + gm_dirty[k - 1].bytes) {
+                const size_t end = std::max(gm_dirty[k - 1].off + gm_dirty[k - 1].bytes, gm_dirty[i].off + gm_dirty[i].bytes);
+                gm_dirty[k - 1].bytes = end - gm_dirty[k - 1].off;
+            }
+            else gm_dirty[k++] = gm_dirty[i];
+        }
+        gm_dirty.resize(k);
+    }
+
+    // the history := the current scene, behind everything in flight (upload, switching on: not per frame)
+    int gm_reset_history()
+    {
+        ATN_HIP(gm_vtx.resize(vtx_pos.n ? vtx_pos.n : 1));
+        ATN_HIP(gm_mtx.resize(matrices.n ? matrices.n : 1));
+        if (vtx_pos.n) ATN_HIP(hipMemcpyAsync(gm_vtx.p, vtx_pos.p, vtx_pos.n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        if (matrices.n) ATN_HIP(hipMemcpyAsync(gm_mtx.p, matrices.p, matrices.n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        gm_mtx_quads = scene.mtx_quads;
+        gm_dirty.clear();
+        gm_pending = false;
+        return ATN_OK;
+    }
+    int set_geometry_motion(int32_t on)
+    {
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        if (!on) {
+            gm_on = false; gm_dirty.clear(); gm_pending = false;
+            gm_vtx.release(); gm_mtx.release(); gm_ids[0].release(); gm_ids[1].release(); gm_rs_ids.release();
+            gm_sv_ids[0] = gm_sv_ids[1] = gm_rs_has_ids = false;
+            return ATN_OK;
+        }
+        if (scene_in_place) return fail(ATN_ERR_UNSUPPORTED, "geometry motion needs to see every scene update: not once the caller writes the scene arrays itself (atn_scene_device_arrays)");
+        if (gm_on) return ATN_OK;
+        if (!gm_ev) ATN_HIP(hipEventCreateWithFlags(&gm_ev, hipEventDisableTiming));
+        gm_on = true;
+        return has_scene ? gm_reset_history() : ATN_OK;
+    }
+    // A mode-2 frame's motion pass and the history's update, on the frame's stream.  `ma` comes with ids, pos, motion and the camera
+    // matrices filled in; the scene and the history are added here.
+    int gm_motion_pass(MotionArgs ma, int32_t width, int32_t height)
+    {
+        if (frames_in_flight > 1 && gm_pending) ATN_HIP(hipStreamWaitEvent(stream, gm_ev, 0));
+        // another number of matrices (instances added / removed): no previous matrix to pair with -- object motion is zero this frame
+        if (scene.mtx_quads != gm_mtx_quads) {
+            if (matrices.n > gm_mtx.n) {
+                { int q = quiesce(); if (q) return q; }
+                ATN_HIP(gm_mtx.resize(matrices.n));
+            }
+            motion_launch_copy(stream, gm_mtx.p, matrices.p, scene.mtx_quads);
+            gm_stats[1]++; gm_stats[2] += scene.mtx_quads;
+            gm_mtx_quads = scene.mtx_quads;
+            size_t k = 0;
+            for (const SceneRange& r : gm_dirty) if (r.buf != SB_MATRICES) gm_dirty[k++] = r;
+            gm_dirty.resize(k);
+        }
+        ma.objects = objects.p; ma.tris = tris.p; ma.h_vtx = gm_vtx.p; ma.h_mtx = gm_mtx.p;
+        ma.width = width; ma.height = height;
+        ma.n_objects = (uint32_t)objects.n; ma.n_tris = (uint32_t)(n_scene_tris < tris.n ? n_scene_tris : tris.n);
+        ma.n_vtx = (uint32_t)(n_scene_vtx < gm_vtx.n ? n_scene_vtx : gm_vtx.n); ma.h_mtx_quads = (uint32_t)(gm_mtx_quads < gm_mtx.n ? gm_mtx_quads : gm_mtx.n);
+        motion_launch_geometry(motion_launch(width, height), stream, ma);
+        std::memcpy(gm_w2c, ma.w2c, sizeof(gm_w2c)); std::memcpy(gm_prev_w2c, ma.prev_w2c, sizeof(gm_prev_w2c));
+        gm_stats[0]++;
+        // the history := the scene this frame saw: the union of the logged ranges (two ticks between two frames wrote the same ones)
+        gm_merge_dirty();
+        for (const SceneRange& r : gm_dirty) {
+            DevBuf<float4>& h = r.buf == SB_VTX_POS ? gm_vtx : gm_mtx;
+            size_t end = r.off + r.bytes;
+            if (end > h.n * sizeof(float4)) end = h.n * sizeof(float4);
+            if (end > set_bytes(r.buf)) end = set_bytes(r.buf);
+            if (r.off >= end) continue;
+            const uint32_t q0 = (uint32_t)(r.off / sizeof(float4)), nq = (uint32_t)((end - r.off) / sizeof(float4));
+            motion_launch_copy(stream, h.p + q0, reinterpret_cast<const float4*>(set_ptr(r.buf)) + q0, nq);
+            gm_stats[1]++; gm_stats[2] += nq;
+        }
+        gm_dirty.clear();
+        ATN_HIP(hipGetLastError());
+        if (frames_in_flight > 1) { ATN_HIP(hipEventRecord(gm_ev, stream)); gm_pending = true; }
+        return ATN_OK;
+    }
     void drop_alt_set()
     {
         for (int k = 0; k < n_alt; k++) alt[k].release();
@@ -681,6 +810,7 @@ public:
         }
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (rs_ev) (void)hipEventDestroy(rs_ev);
+        if (gm_ev) (void)hipEventDestroy(gm_ev);
         if (ao_ev) (void)hipEventDestroy(ao_ev);
         if (ev_gather) (void)hipEventDestroy(ev_gather);
         for (auto& e : sv_ev_prepare) if (e) (void)hipEventDestroy(e);
@@ -752,6 +882,7 @@ public:
         scene.lights = lights.p; scene.light_plane = light_plane.p; scene.texels = texels.p; scene.texels8 = texels8.p; scene.textures = textures.p;
         scene.mtx_quads = (uint32_t)img.matrices.size();
         has_scene = true;
+        if (gm_on) { gm_sv_ids[0] = gm_sv_ids[1] = gm_rs_has_ids = false; const int grc = gm_reset_history(); if (grc) return grc; }
         { const int nrc = npr_decode(s, img); if (nrc) return nrc; }
         { const int vrc = vol_decode(s, img); if (vrc) return vrc; }
         env_host.clear(); env_w = env_h = 0; ibl_tables_ready = false;
@@ -1577,6 +1708,7 @@ public:
                         prof_begin(prof, ATN_K_TRACE_CLOSEST, st);
                         launch_trace<false>(plan, pb, count, b, st);
                         prof_end(prof);
+                        if (SVGF && b == 0 && gm_capture) motion_launch_capture(g_all, st, pb, fp, gm_capture);
                         prof_begin(prof, ATN_K_SHADE, st);
                         launch_shade<SVGF>(plan, st, pb, fp, b, sv);
                         prof_end(prof);
@@ -1592,6 +1724,7 @@ public:
                         prof_begin(prof, tl.prof_kind, st);
                         launch_trace_fused<false>(tl, st, pb, scene, b - 1, b < d->maxDepth ? b : -1, b);
                         prof_end(prof);
+                        if (SVGF && b == 0 && gm_capture) motion_launch_capture(g_all, st, pb, fp, gm_capture);
                         if (b < d->maxDepth) {
                             prof_begin(prof, ATN_K_SHADE, st);
                             launch_shade<SVGF>(plan, st, pb, fp, b, sv);
@@ -2019,6 +2152,7 @@ public:
         switch (which) {
         case 8: return sv_tmp.p; case 9: return sv_motion.p; case 10: return sv_primary[k].p;
         case 11: return sv_atrous[0].p; case 12: return sv_atrous[1].p; case 13: return sv_out.p; case 14: return sv_contribs[k].p;
+        case 15: return (!for_upload && gm_sv_ids[k]) ? gm_ids[k].p : nullptr;      // the ids plane of the last mode-2 frame (device/motion.hpp)
         }
         return nullptr;
     }
@@ -2029,6 +2163,14 @@ public:
         int rc = check_ready(d);
         if (rc) return rc;
         if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "SVGF needs the whole frame on one GPU (filter footprints cross tiles)");
+        const bool geo_motion = compute_motion == 2;
+        if (geo_motion) {
+            if (!path_pass) return fail(ATN_ERR_UNSUPPORTED, "compute_motion = 2 needs the frame's primary hits: atn_svgf_denoise has no path pass");
+            if (!gm_on) return fail(ATN_ERR_INVALID_ARG, "compute_motion = 2 needs geometry motion tracking: atn_set_geometry_motion(ctx, 1)");
+            // the ids and primary_position must belong to the same sample: every sample's bounce 0 overwrites the position of the pixels
+            // that still sample, so with several samples the two planes would have to be captured per pixel and sample -- refused
+            if (d->sample != 1) return fail(ATN_ERR_UNSUPPORTED, "compute_motion = 2 renders one sample per pixel (destination.sample must be 1)");
+        }
         ATN_HIP(hipSetDevice(device));
         // Frames in flight (atn_set_frames_in_flight > 1): the path pass of frame f + 1 runs on the next bank's stream while
         // frame f is still being traced and filtered.  The path pass writes only its bank and slot (f + 1) % 2 of the
@@ -2071,15 +2213,30 @@ public:
         sf.width = d->width; sf.height = d->height; sf.frame = d->frame; sf.atrous_iter_cnt = sv_atrous_iters;
         // Camera::ComputeScreenDistance (camera.h:216-221): tan of half the fov IN DEGREES, as the reference writes it
         sf.camera_distance = (float)d->height / (2.0f * std::tan(0.5f * camera.vfov));
-        sf.compute_motion = compute_motion;
+        sf.compute_motion = geo_motion ? 0 : compute_motion;       // mode 2: k_motion_geometry writes the plane, the prepare pass leaves it
+        if (geo_motion) ATN_HIP(gm_ids[slot].resize((size_t)d->width * d->height));
+        gm_sv_ids[slot] = geo_motion;
         SvgfShade sv{};
         sv.nd = sv_gnd[slot].p; sv.am = sv_gam[slot].p; sv.primary = sf.primary;
         sv.w2c3[0] = sf.w2c[12]; sv.w2c3[1] = sf.w2c[13]; sv.w2c3[2] = sf.w2c[14]; sv.w2c3[3] = sf.w2c[15];
 
         if (path_pass) {
             if (pipelined && sv_prepare_recorded[slot]) ATN_HIP(hipStreamWaitEvent(stream, sv_ev_prepare[slot], 0));
+            gm_capture = geo_motion ? gm_ids[slot].p : nullptr;
             rc = run_paths<true>(d, fp, false, prof, sv, sf);
+            gm_capture = nullptr;
             if (rc) return rc;
+            if (geo_motion) {
+                // the plane's last reader is the previous frame's temporal pass on the filter stream (the slot event is recorded behind it)
+                if (pipelined && sv_prepare_recorded[1 - slot]) ATN_HIP(hipStreamWaitEvent(stream, sv_ev_prepare[1 - slot], 0));
+                MotionArgs ma{};
+                ma.ids = gm_ids[slot].p; ma.pos = sf.primary; ma.motion = sf.motion;
+                std::memcpy(ma.w2c, sf.w2c, sizeof(ma.w2c)); std::memcpy(ma.prev_w2c, sf.prev_w2c, sizeof(ma.prev_w2c));
+                prof_begin(prof, ATN_K_SVGF_PREPARE);
+                rc = gm_motion_pass(ma, d->width, d->height);
+                prof_end(prof);
+                if (rc) return rc;
+            }
             if (pipelined) {
                 rc = record_scene_read();       // (this bank's "path pass done")
                 if (rc) return rc;
@@ -2222,6 +2379,8 @@ public:
         if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR has no relaxed-math kernels: atn_set_shade_math(0)");
         if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR frames do not count rays (count_stats must be 0)");
         if (scene.material_set >= kMsToon) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR does not shade toon / stylised materials");
+        const bool geo_motion = compute_motion == 2;
+        if (geo_motion && !gm_on) return fail(ATN_ERR_INVALID_ARG, "compute_motion = 2 needs geometry motion tracking: atn_set_geometry_motion(ctx, 1)");
         ATN_HIP(hipSetDevice(device));
         if (frames_in_flight > 1 && (d->width != rs_w || d->height != rs_h)) { rc = quiesce(); if (rc) return rc; }
         rc = begin_frame(*d, frames_in_flight > 1);
@@ -2232,6 +2391,8 @@ public:
         if (!compute_motion && (!rs_motion_set || rs_motion_count < n))
             return fail(ATN_ERR_INVALID_ARG, "no motion/depth buffer: call atn_restir_set_motion_depth or pass compute_motion = 1");
         if (compute_motion) ATN_HIP(rs_motion_own.resize(n));
+        if (geo_motion) ATN_HIP(gm_rs_ids.resize(n));
+        gm_rs_has_ids = geo_motion;
         if (!rs_ev) ATN_HIP(hipEventCreateWithFlags(&rs_ev, hipEventDisableTiming));
         const bool prof = d->profile != 0;
         camera_matrices(camera, rs_W2V, rs_V2C, rs_prevW2V);
@@ -2282,7 +2443,16 @@ public:
                 // the previous frame's reuse passes read the sets, AOVs and visibility plane this frame's bounce 0 overwrites
                 if (rs_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, rs_ev, 0));
                 restir_launch_shade(scene.material_set, plan.shade_grid, stream, pb, scene, fp, camera, ra);
-                if (compute_motion) restir_launch_motion(stream, fp, ra);
+                if (geo_motion) {
+                    // (the hit records of bounce 0 stay in the path state until the next trace launch)
+                    motion_launch_capture(g_all, stream, pb, fp, gm_rs_ids.p);
+                    MotionArgs ma{};
+                    ma.ids = gm_rs_ids.p; ma.pos = ra.cur.info[2]; ma.motion = ra.motion;
+                    std::memcpy(ma.w2c, ra.w2c, sizeof(ma.w2c)); std::memcpy(ma.prev_w2c, ra.prev_w2c, sizeof(ma.prev_w2c));
+                    rc = gm_motion_pass(ma, d->width, d->height);
+                    if (rc) return rc;
+                }
+                else if (compute_motion) restir_launch_motion(stream, fp, ra);
                 restir_launch_vis_prep(grid_for(n_slots), stream, pb, scene, fp, ra);
             }
             else launch_shade<false>(plan, stream, pb, fp, b, SvgfShade{});
@@ -2310,7 +2480,8 @@ public:
 
     // stage buffers of the last frame (tests): 0 / 1 / 2 the reservoirs after the shade, temporal (visibility) and spatial passes as
     // float[n][5] {y, M, W, w_sum, target_pdf_of_y} (atn_restir_capture); 3 the infos float4[4][n]; 4 / 5 the AOVs; 6 motion-depth;
-    // 7 the CMJ dimension of every pixel after bounce 0's passes, uint32[n] (atn_restir_capture)
+    // 7 the CMJ dimension of every pixel after bounce 0's passes, uint32[n] (atn_restir_capture); 8 the ids plane of a frame rendered
+    // with compute_motion = 2 (device/motion.hpp)
     int restir_download(int32_t which, void* out)
     {
         if (!rs_rendered || !out) return fail(ATN_ERR_INVALID_ARG, "no ReSTIR frame has been rendered");
@@ -2337,7 +2508,7 @@ public:
             return ATN_OK;
         }
         const void* src = which == 4 ? (const void*)rs_nd.p : which == 5 ? (const void*)rs_am.p : which == 6 ? (const void*)(rs_last_own_motion ? rs_motion_own.p : rs_motion.p)
-                        : which == 7 ? (const void*)rs_dims.p : nullptr;
+                        : which == 7 ? (const void*)rs_dims.p : (which == 8 && gm_rs_has_ids) ? (const void*)gm_rs_ids.p : nullptr;
         if (!src) return fail(ATN_ERR_INVALID_ARG, "no such ReSTIR buffer");
         if (which == 7) {
             std::vector<float> h(n);
@@ -3068,10 +3239,31 @@ int atn_scene_device_arrays(atn_ctx* ctx, void** vtx_pos, void** vtx_nml, void**
     // the caller writes these arrays itself from now on: one copy of the scene, updates in place behind the frames in flight
     { int q = ctx->r.quiesce(); if (q) return q; }
     ctx->r.drop_alt_set(); ctx->r.scene_in_place = true;
+    if (ctx->r.gm_on) { const int g = ctx->r.set_geometry_motion(0); if (g) return g; }       // (the history cannot follow the caller's writes)
     ctx->r.scene.planar_lights = 0;     // (the caller writes vertices from now on)
     if (vtx_pos) *vtx_pos = ctx->r.vtx_pos.p;
     if (vtx_nml) *vtx_nml = ctx->r.vtx_nml.p;
     if (triangles) *triangles = ctx->r.tris.p;
+    return ATN_OK;
+}
+int atn_set_geometry_motion(atn_ctx* ctx, int32_t on)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.set_geometry_motion(on); });
+}
+int atn_geometry_motion_stats(atn_ctx* ctx, uint64_t* out3)
+{
+    CTX_OR_FAIL(ctx);
+    if (!out3) return ctx->r.fail(ATN_ERR_INVALID_ARG, "null output");
+    for (int k = 0; k < 3; k++) out3[k] = ctx->r.gm_stats[k];
+    return ATN_OK;
+}
+int atn_geometry_motion_matrices(atn_ctx* ctx, float* w2c16, float* prev_w2c16)
+{
+    CTX_OR_FAIL(ctx);
+    if (!w2c16 || !prev_w2c16) return ctx->r.fail(ATN_ERR_INVALID_ARG, "null output");
+    if (!ctx->r.gm_stats[0]) return ctx->r.fail(ATN_ERR_INVALID_ARG, "no frame has been rendered with compute_motion = 2");
+    std::memcpy(w2c16, ctx->r.gm_w2c, sizeof(ctx->r.gm_w2c)); std::memcpy(prev_w2c16, ctx->r.gm_prev_w2c, sizeof(ctx->r.gm_prev_w2c));
     return ATN_OK;
 }
 int atn_init_sampler(atn_ctx* ctx, int32_t w, int32_t h, int32_t seed) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.initSampler(w, h, seed); }); }

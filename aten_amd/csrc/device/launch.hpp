@@ -188,4 +188,17 @@ void skin_launch_triangles(const SkinLaunch& l, hipStream_t st, const SkinTriArg
 void skin_launch_morton(hipStream_t st, const atn_triangle_param* tris, const float4* vtx, int32_t vtx_offset, uint32_t n, const float* box,
                         uint32_t* codes, uint32_t* indices);
 
+// ---- motion.hip (device/motion.hpp) ----
+struct MotionArgs;
+// the motion pass over a frame: svgf_pixel's tiles (8 x 32 pixels per block of 256; x rounded up to a multiple of 8, one strip per XCD)
+struct MotionLaunch { uint32_t grid_x, grid_y; };
+inline MotionLaunch motion_launch(int32_t width, int32_t height)
+{
+    return MotionLaunch{ (uint32_t)((((width + 7) / 8) + 7) / 8 * 8), (uint32_t)((height + 31) / 32) };
+}
+// the primary hit records of slots [fp.slot_begin, fp.slot_end) -> the ids plane; `grid` blocks of 256 over those slots
+void motion_launch_capture(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, float4* ids);
+void motion_launch_geometry(const MotionLaunch& l, hipStream_t st, const MotionArgs& a);
+void motion_launch_copy(hipStream_t st, float4* dst, const float4* src, uint32_t n_quads);
+
 } // namespace atn

@@ -149,6 +149,24 @@ class PathTracing:
         self._check(self._l.atn_skin_destroy(self._ctx, skin))
         self._skin_sizes.pop(skin, None)
 
+    # ---- geometry motion vectors (docs/MOTION.md)
+    def set_geometry_motion(self, on=True):
+        """Keep the geometry history (the scene's vertex positions and matrices as the last compute_motion=2 frame saw them), so that
+        svgf_render / restir_render accept compute_motion=2: motion vectors that follow skinned meshes and moved instances."""
+        self._check(self._l.atn_set_geometry_motion(self._ctx, int(bool(on))))
+
+    def geometry_motion_stats(self):
+        """dict(passes, copies, copied_float4): motion passes run, range copies into the history, float4s they moved."""
+        s = np.zeros(3, np.uint64)
+        self._check(self._l.atn_geometry_motion_stats(self._ctx, s.ctypes.data))
+        return dict(passes=int(s[0]), copies=int(s[1]), copied_float4=int(s[2]))
+
+    def geometry_motion_matrices(self):
+        """(w2c, prev_w2c) float32 [4, 4]: the camera matrices the last compute_motion=2 frame's motion pass used."""
+        a, b = np.zeros((4, 4), np.float32), np.zeros((4, 4), np.float32)
+        self._check(self._l.atn_geometry_motion_matrices(self._ctx, a.ctypes.data, b.ctypes.data))
+        return a, b
+
     def scene_device_arrays(self):
         """(vtx_pos, vtx_nml, triangles) device addresses of the uploaded scene."""
         p = [C.c_void_p() for _ in range(3)]
@@ -305,7 +323,7 @@ class PathTracing:
     SVGF_BUFFERS = dict(normal_depth=0, albedo_meshid=1, color_variance=2, moment_temporalweight=3,
                         prev_normal_depth=4, prev_albedo_meshid=5, prev_color_variance=6, prev_moment_temporalweight=7,
                         temporary_color=8, motion_depth=9, primary_position=10, atrous0=11, atrous1=12, output=13,
-                        contribs=14)
+                        contribs=14, primary_hit=15)
 
     def svgf_render(self, width, height, max_depth=5, rr_depth=3, spp=1, frame=0, compute_motion=False, stages=False,
                     download=True, profile=False):
@@ -313,7 +331,7 @@ class PathTracing:
         d = Destination(width, height, max_depth, rr_depth, spp, frame, 0, 1, 0, int(profile))
         out = np.empty((height, width, 4), np.float32) if download else None
         st = np.empty((3, height, width, 4), np.float32) if stages else None
-        self._check(self._l.atn_svgf_render(self._ctx, C.byref(d), 1 if compute_motion else 0,
+        self._check(self._l.atn_svgf_render(self._ctx, C.byref(d), int(compute_motion),
                                             out.ctypes.data if download else None, st.ctypes.data if stages else None))
         self.width, self.height = width, height
         return (out, st) if stages else out
@@ -331,7 +349,7 @@ class PathTracing:
         """One ReSTIR frame (1 sample per pixel) into the film; returns the film [h, w, 4]."""
         d = Destination(width, height, max_depth, rr_depth, 1, frame, int(progressive), 1, 0, int(profile))
         out = np.empty((height, width, 4), np.float32) if download else None
-        self._check(self._l.atn_restir_render(self._ctx, C.byref(d), 1 if compute_motion else 0, out.ctypes.data if download else None))
+        self._check(self._l.atn_restir_render(self._ctx, C.byref(d), int(compute_motion), out.ctypes.data if download else None))
         self.width, self.height = width, height
         return out
 
@@ -349,7 +367,8 @@ class PathTracing:
     def restir_buffer(self, name):
         """The last ReSTIR frame's stage buffers.  'initial' / 'temporal' / 'spatial': dict of [h, w] arrays y, M (int32), W, w_sum,
         target_pdf (needs restir_capture); 'info': dict nml, wi, p [h, w, 3], u, v, pre_r, mtrl, mesh, hit; 'nd' / 'am' / 'motion':
-        [h, w, 4]; 'dims': uint32 [h, w] (needs restir_capture)."""
+        [h, w, 4]; 'dims': uint32 [h, w] (needs restir_capture); 'primary_hit': the ids plane [h, w, 4] of a frame rendered with
+        compute_motion=2 (unpack_primary_hit)."""
         w, h = self.width, self.height
         if name in self.RESTIR_STAGES:
             out = np.empty((h, w, 5), np.float32)
@@ -366,7 +385,7 @@ class PathTracing:
             out = np.empty((h, w), np.uint32)
             self._check(self._l.atn_restir_download(self._ctx, 7, out.ctypes.data))
             return out
-        which = {"nd": 4, "am": 5, "motion": 6}[name]
+        which = {"nd": 4, "am": 5, "motion": 6, "primary_hit": 8}[name]
         out = np.empty((h, w, 4), np.float32)
         self._check(self._l.atn_restir_download(self._ctx, which, out.ctypes.data))
         return out
@@ -528,7 +547,7 @@ class PathTracing:
         d = Destination(width, height, 1, 1, 1, frame, 0, 1, 0, int(profile))
         out = np.empty((height, width, 4), np.float32) if download else None
         st = np.empty((3, height, width, 4), np.float32) if stages else None
-        self._check(self._l.atn_svgf_denoise(self._ctx, C.byref(d), 1 if compute_motion else 0,
+        self._check(self._l.atn_svgf_denoise(self._ctx, C.byref(d), int(compute_motion),
                                              out.ctypes.data if download else None, st.ctypes.data if stages else None))
         self.width, self.height = width, height
         return (out, st) if stages else out
@@ -553,6 +572,8 @@ class PathTracing:
         self._check(self._l.atn_svgf_set_atrous_iterations(self._ctx, n))
 
     def svgf_buffer(self, name):
+        """A buffer of the last SVGF frame, float32 [h, w, 4] (SVGF_BUFFERS).  'primary_hit' is the ids plane of a frame rendered with
+        compute_motion=2: object id and triangle id as int bits, a, b (unpack_primary_hit)."""
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(self._l.atn_svgf_download(self._ctx, self.SVGF_BUFFERS[name], out.ctypes.data))
         return out
@@ -763,6 +784,12 @@ class MultiGpuPathTracing:
 
 
 VOLUME_STATE_FLAGS = dict(processed=1, hit=2, sampled=4, absorbed=8, scattered=16, passed=32, connection=64, terminated=256)
+
+
+def unpack_primary_hit(plane):
+    """The ids plane ('primary_hit') as dict(objid int32 [h, w] (-1 = miss), tri int32 [h, w], a, b float32 [h, w])."""
+    p = np.ascontiguousarray(plane, np.float32)
+    return dict(objid=p[..., 0].copy().view(np.int32), tri=p[..., 1].copy().view(np.int32), a=p[..., 2].copy(), b=p[..., 3].copy())
 
 
 def unpack_volume_state(raw):

@@ -521,6 +521,44 @@ def skinned_room(nu=48, nv=24, n_bones=8, asset_dir=None, radius=0.13):
     return b, oid, cam, np.ascontiguousarray(sv[idx.reshape(-1)])
 
 
+MOVING_QUAD = dict(centre=(-0.2, 1.55, -0.6), half=(0.3, 0.25))
+
+
+def moving_quad_room(offset=0.0, asset_dir=None, second_offset=None):
+    """The Cornell box with a camera-facing quad in front of its back wall, as a rigid instance translated along camera-right (+x
+    for this camera) by `offset`: the moved-instance case of the geometry motion vectors (docs/MOTION.md).  The quad's material is
+    its own -- SVGF's mesh-id test compares the material id, so history from the wall behind it is rejected.  Every offset gives the
+    same bottom-level lists: renderer.updateBVH(moving_quad_room(x)[0]) moves the instance.  The quad spans
+    MOVING_QUAD["centre"] +- MOVING_QUAD["half"] in x and y (before the translation), above the tall box, in the plane z = centre z.
+    second_offset: a second instance of the same quad, translated by that much and 0.55 downwards (one more object and matrix pair
+    over the same lists, appended behind everything else: the first instance keeps its ids).
+    Returns (FlatScene, camera, dict(instance=object id of the quad's instance, mtx_id=its L2W matrix, mtrl=its material id))."""
+    asset_dir = asset_dir or os.path.join(ASSETS, "cornellbox")
+    b = SceneBuilder()
+    emit = b.add_material("light", L.MTRL_EMISSIVE, (1.0, 1.0, 1.0))
+    objs = b.load_obj(os.path.join(asset_dir, "orig.obj"), create_mtrl=lambda name, mt, clr, a, n: b.add_material(name, mt, clr),
+                      separate_objs=True, normal_on_the_fly=True)
+    light = b.create_instance(objs[0])
+    b.add_area_light(light, b.materials[emit][1]["baseColor"][:3], 200.0)
+    for o in objs[1:]:
+        b.create_instance(o)
+    mtrl = b.add_material("quad", L.MTRL_DIFFUSE, (0.2, 0.6, 0.8))
+    (cx, cy, cz), (hx, hy) = MOVING_QUAD["centre"], MOVING_QUAD["half"]
+    pos = np.array([[cx - hx, cy - hy, cz], [cx + hx, cy - hy, cz], [cx + hx, cy + hy, cz], [cx - hx, cy + hy, cz]], np.float32)
+    nml = np.tile(np.array([0.0, 0.0, 1.0], np.float32), (4, 1))
+    oid = b.add_mesh("quad", pos, np.array([[0, 1, 2], [0, 2, 3]], np.int64), mtrl, normals=nml)
+    M = np.eye(4, dtype=np.float32)
+    M[0, 3] = offset
+    inst = b.create_instance(oid, M)
+    if second_offset is not None:
+        M2 = np.eye(4, dtype=np.float32)
+        M2[0, 3], M2[1, 3] = second_offset, -0.55
+        b.create_instance(oid, M2)
+    b.set_background((0.0, 0.0, 0.0))
+    cam = dict(pos=(0.0, 1.0, 3.0), at=(0.0, 1.0, 0.0), vfov=45.0)
+    return b.build(), cam, dict(instance=inst, mtx_id=b.objects[inst]["mtx_id"], mtrl=mtrl)
+
+
 def toon_ramp(steps=(0.15, 0.45, 0.8, 1.0), width=64, tint=(1.0, 1.0, 1.0)):
     """A 1-D remap texture (ToonParameter::remap_texture): `width` texels in `len(steps)` flat bands."""
     t = np.ones((1, width, 4), np.float32)

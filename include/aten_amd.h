@@ -350,7 +350,8 @@ int atn_mgpu_render_burst(atn_mgpu* mg, const atn_destination* dst, int32_t n_fr
  * values OnRender puts after the path pass, the temporal pass and the variance pass.
  * compute_motion != 0: the motion/depth buffer is computed from the primary hits and the current/previous
  * camera matrices (MatricesForRendering, pt_params.h:150-185) -- the compute pass that stands in for the
- * reference's GL raster pass (src/shader/ssrt_fs.glsl:31-47); 0: use atn_svgf_set_motion_depth's buffer. */
+ * reference's GL raster pass (src/shader/ssrt_fs.glsl:31-47); 0: use atn_svgf_set_motion_depth's buffer;
+ * 2: the same pass with the geometry's own motion (atn_set_geometry_motion, below). */
 int atn_svgf_render(atn_ctx* ctx, const atn_destination* dst, int32_t compute_motion,
                     atn_vec4* out_host, atn_vec4* stages_host);
 /* ≙ SVGFRenderer::SetMotionDepthBuffer (svgf.cpp:441-450): {motion.xy in screen fractions, depth, 1}. */
@@ -369,6 +370,27 @@ int atn_svgf_set_dilate_temporal_weight(atn_ctx* ctx, int32_t on);
  * 4-7 GetPrevAovBuffer() (the set the last frame wrote), 8 temporary colour, 9 motion/depth, 10 primary hit
  * position, 11/12 a-trous ping-pong buffers, 13 output, 14 contributions. */
 int atn_svgf_download(atn_ctx* ctx, int32_t which, atn_vec4* out_host);
+
+/* ---- Geometry motion vectors (docs/MOTION.md) ------------------------------------------------------------------------------
+ * ≙ the G-buffer pass of drawSceneForGBuffer for moving geometry (src/shader/ssrt_deformable_vs.glsl, ssrt_vs.glsl: a previous
+ * position per vertex, a previous local-to-world matrix per object).  The context keeps a GEOMETRY HISTORY: the scene's vertex
+ * positions and matrices as the last frame rendered with compute_motion = 2 saw them (equal to the scene after atn_upload_scene and
+ * when tracking is switched on).  Such a frame projects every primary hit through the current camera from where it is and through
+ * the previous camera from where the history has it; then the history takes over the ranges the updates since wrote.
+ *   atn_set_geometry_motion: on != 0 allocates the history and starts tracking (default off; waits for the frames in flight);
+ *                            0 frees it.  ATN_ERR_UNSUPPORTED after atn_scene_device_arrays (which also switches tracking off).
+ *   compute_motion = 2 (atn_svgf_render, atn_restir_render): ATN_ERR_INVALID_ARG while tracking is off; ATN_ERR_UNSUPPORTED for
+ *                            atn_svgf_denoise (no path pass: no ids) and for atn_svgf_render with destination.sample != 1.
+ *   ids plane: atn_svgf_download which = 15, atn_restir_download which = 8, of the last frame if it was rendered with
+ *                            compute_motion = 2: atn_vec4[w*h] {object id (int bits; -1 = miss), triangle id (int bits), a, b}.
+ * For tests (like atn_skin_download: not part of what an application needs):
+ *   atn_geometry_motion_stats: {motion passes, range copies into the history, float4s copied} since the context was created.
+ *   atn_geometry_motion_matrices: the world-to-clip matrices (row-major) of this frame's and the previous frame's camera that the
+ *                            last motion pass used.
+ * SVGF and ReSTIR frames of a context share the one history.  Additive entry points: atn_abi_version stays 3. */
+int atn_set_geometry_motion(atn_ctx* ctx, int32_t on);
+int atn_geometry_motion_stats(atn_ctx* ctx, uint64_t* out3);
+int atn_geometry_motion_matrices(atn_ctx* ctx, float* w2c16, float* prev_w2c16);
 
 /* ---- ReSTIR (idaten::ReSTIRPathTracing; docs/RESTIR.md) ------------------------------------------------------------------
  * Many-light direct lighting at the primary hit with reservoir resampling (initial candidates, temporal and spatial reuse); the

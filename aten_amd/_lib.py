@@ -33,6 +33,7 @@ SYMBOLS = [
     "atn_skin_create", "atn_skin_update", "atn_skin_compute", "atn_lbvh_rebuild_list_skinned", "atn_skin_download",
     "atn_skin_download_list", "atn_skin_destroy",
     "atn_set_geometry_motion", "atn_geometry_motion_stats", "atn_geometry_motion_matrices",
+    "atn_taa_resolve", "atn_taa_upload", "atn_taa_download", "atn_taa_reset", "atn_taa_output_device", "atn_taa_rgba8_device",
     "atn_mgpu_create", "atn_mgpu_destroy", "atn_mgpu_last_error", "atn_mgpu_shard_count", "atn_mgpu_shard_device",
     "atn_mgpu_upload_scene", "atn_mgpu_update_tlas", "atn_mgpu_update_camera", "atn_mgpu_init_sampler",
     "atn_mgpu_set_random", "atn_mgpu_render", "atn_mgpu_reset", "atn_mgpu_synchronize", "atn_mgpu_film_device",
@@ -131,6 +132,12 @@ def lib():
         l.atn_svgf_upload.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp]
         l.atn_svgf_output_device.argtypes = [vp]
         l.atn_svgf_output_device.restype = vp
+        l.atn_taa_resolve.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, vp]
+        l.atn_taa_upload.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp]
+        l.atn_taa_download.argtypes = [vp, C.c_int32, vp]
+        l.atn_taa_reset.argtypes = [vp]
+        l.atn_taa_output_device.argtypes = [vp]; l.atn_taa_output_device.restype = vp
+        l.atn_taa_rgba8_device.argtypes = [vp]; l.atn_taa_rgba8_device.restype = vp
         l.atn_film_device.argtypes = [vp]; l.atn_film_device.restype = vp
         l.atn_tile_device.argtypes = [vp]; l.atn_tile_device.restype = vp
         l.atn_tile_slots.argtypes = [vp]; l.atn_tile_slots.restype = C.c_uint32

@@ -27,6 +27,7 @@
 #include "device/lbvh.hpp"
 #include "device/skinning.hpp"
 #include "device/motion.hpp"
+#include "device/taa.hpp"
 #include "host/scene_upload.hpp"
 #include "host/ibl_precompute.hpp"
 
@@ -419,6 +420,7 @@ public:
         if (sv_stream) ATN_HIP(hipStreamSynchronize(sv_stream));
         if (scene_stream) ATN_HIP(hipStreamSynchronize(scene_stream));
         film_pending = false;
+        ta_pending = false;     // (the display tail runs on one of the streams above)
         sv_prepare_recorded[0] = sv_prepare_recorded[1] = false;
         return ATN_OK;
     }
@@ -810,6 +812,7 @@ public:
         }
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (rs_ev) (void)hipEventDestroy(rs_ev);
+        if (ta_ev) (void)hipEventDestroy(ta_ev);
         if (gm_ev) (void)hipEventDestroy(gm_ev);
         if (ao_ev) (void)hipEventDestroy(ao_ev);
         if (ev_gather) (void)hipEventDestroy(ev_gather);
@@ -1769,7 +1772,7 @@ public:
     int wait_film()
     {
         if (film_pending) ATN_HIP(hipStreamWaitEvent(stream, ev_film, 0));
-        return ATN_OK;
+        return taa_before_write(stream);        // (a display tail that still reads the film: atn_taa_resolve, source 1)
     }
     int record_film_writer()
     {
@@ -2039,6 +2042,8 @@ public:
     float4* sv_spare = nullptr;
     int32_t sv_w = 0, sv_h = 0, sv_curr = 0, sv_atrous_iters = 5;
     bool sv_motion_set = false;
+    bool sv_frame_done = false;             // a frame has been rendered / denoised into sv_out at sv_w x sv_h (the display tail's source 0)
+    hipStream_t sv_last_fs = nullptr;       // the stream its filter passes ran on
     hipStream_t sv_stream = nullptr;        // filter stream of pipelined SVGF frames (frames in flight > 1)
     bool w_or_h_changed(int32_t w, int32_t h) const { return w != sv_w || h != sv_h || w != film_w || h != film_h; }
     DevBuf<float> sv_weight;        // scalar plane of the optional temporal-weight dilation
@@ -2115,6 +2120,7 @@ public:
             if (!sv_motion_set || sv_motion_count < n) { ATN_HIP(sv_motion.resize(n)); sv_motion_set = false; sv_motion_count = 0; }
             sv_cv[0] = sv_aov[0][2].p; sv_cv[1] = sv_aov[1][2].p; sv_spare = sv_scratch.p;
             sv_w = w; sv_h = h; sv_curr = 0; sv_slot = 0; sv_last_slot = 0;
+            sv_frame_done = false;
         }
         if (stages) ATN_HIP(sv_stages.resize(3 * n));
         return ATN_OK;
@@ -2136,6 +2142,7 @@ public:
     int svgf_reset()
     {
         sv_w = 0; sv_h = 0; sv_curr = 0;        // buffers are re-initialised by the next svgf_render
+        sv_frame_done = false;
         const float id[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
         std::memcpy(sv_W2V, id, sizeof(id)); std::memcpy(sv_V2C, id, sizeof(id)); std::memcpy(sv_prevW2V, id, sizeof(id));
         return ATN_OK;
@@ -2229,6 +2236,8 @@ public:
             if (geo_motion) {
                 // the plane's last reader is the previous frame's temporal pass on the filter stream (the slot event is recorded behind it)
                 if (pipelined && sv_prepare_recorded[1 - slot]) ATN_HIP(hipStreamWaitEvent(stream, sv_ev_prepare[1 - slot], 0));
+                rc = taa_before_write(stream);      // ... or the display tail of that frame (atn_taa_resolve, source 0)
+                if (rc) return rc;
                 MotionArgs ma{};
                 ma.ids = gm_ids[slot].p; ma.pos = sf.primary; ma.motion = sf.motion;
                 std::memcpy(ma.w2c, sf.w2c, sizeof(ma.w2c)); std::memcpy(ma.prev_w2c, sf.prev_w2c, sizeof(ma.prev_w2c));
@@ -2244,6 +2253,8 @@ public:
             }
         }
         const dim3 gp((((d->width + 7) / 8) + 7) / 8 * 8, (d->height + 31) / 32), tp(256);     // x: multiple of 8 (XCD strips)
+        rc = taa_before_write(fs);      // the prepare pass overwrites the output and motion planes a display tail may still read
+        if (rc) return rc;
         prof_begin(prof, ATN_K_SVGF_PREPARE, fs);
         hipLaunchKernelGGL(k_svgf_prepare, gp, tp, 0, fs, sf);
         prof_end(prof);
@@ -2287,6 +2298,7 @@ public:
         prof_end(prof);
         ATN_HIP(hipGetLastError());
         sv_curr = 1 - sv_curr;
+        sv_frame_done = true; sv_last_fs = fs;
 
         const size_t n = (size_t)d->width * d->height;
         if (out_host) ATN_HIP(hipMemcpyAsync(out_host, sv_out.p, n * sizeof(float4), hipMemcpyDeviceToHost, fs));
@@ -2442,6 +2454,8 @@ public:
             if (b == 0) {
                 // the previous frame's reuse passes read the sets, AOVs and visibility plane this frame's bounce 0 overwrites
                 if (rs_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, rs_ev, 0));
+                rc = taa_before_write(stream);      // (the motion plane a display tail may still read: atn_taa_resolve, source 1)
+                if (rc) return rc;
                 restir_launch_shade(scene.material_set, plan.shade_grid, stream, pb, scene, fp, camera, ra);
                 if (geo_motion) {
                     // (the hit records of bounce 0 stay in the path state until the next trace launch)
@@ -2517,6 +2531,148 @@ public:
             return ATN_OK;
         }
         ATN_HIP(hipMemcpy(out, src, n * sizeof(float4), hipMemcpyDeviceToHost));
+        return ATN_OK;
+    }
+
+    // ------------------------------------------------------------------------------------------------
+    // The display tail (aten::TAA + aten::GammaCorrection, device/taa.hpp; docs/TAA.md): frame-persistent state = the history ping-pong
+    // (taa.cpp:33-60).  One launch per frame, enqueued on the stream that produced its source and ordered against the next frame's
+    // writers by ta_ev (taa_before_write).
+    // ------------------------------------------------------------------------------------------------
+    DevBuf<float4> ta_hist[2], ta_gamma, ta_up_color, ta_up_motion;
+    DevBuf<uint32_t> ta_rgba8;
+    int32_t ta_w = 0, ta_h = 0, ta_pos = 0;         // ta_hist[ta_pos]: the last output = the history of the next frame
+    int32_t ta_up_w[2] = { 0, 0 }, ta_up_h[2] = { 0, 0 };       // sizes of the uploaded colour / motion planes (source 2)
+    bool ta_valid = false;          // a history exists (false: the next frame takes the pass-through rule for every pixel)
+    bool ta_resolved = false, ta_has_gamma = false;     // a frame has been resolved at ta_w x ta_h / and it wrote the float gamma plane
+    bool ta_pending = false;
+    hipEvent_t ta_ev = nullptr;     // the last display tail has finished (its reads of the source planes and of the history)
+    hipStream_t ta_last_stream = nullptr;
+    static constexpr int32_t kTaaMaxSide = 16384;
+
+    // in front of a pass that overwrites a plane the last display tail reads
+    int taa_before_write(hipStream_t st)
+    {
+        if (ta_pending) ATN_HIP(hipStreamWaitEvent(st, ta_ev, 0));
+        return ATN_OK;
+    }
+    int taa_idle()
+    {
+        if (ta_pending) { ATN_HIP(hipStreamSynchronize(ta_last_stream)); ta_pending = false; }
+        return ATN_OK;
+    }
+    // a size change forgets the history
+    int taa_ensure(int32_t w, int32_t h)
+    {
+        if (w <= 0 || h <= 0 || w > kTaaMaxSide || h > kTaaMaxSide) return fail(ATN_ERR_INVALID_ARG, "TAA: bad frame size (1 .. 16384 per side)");
+        if (w == ta_w && h == ta_h) return ATN_OK;
+        const int rc = taa_idle();
+        if (rc) return rc;
+        const size_t n = (size_t)w * h;
+        for (auto& b : ta_hist) ATN_HIP(b.resize(n));
+        ATN_HIP(ta_rgba8.resize(n));
+        ta_w = w; ta_h = h; ta_pos = 0;
+        ta_valid = false; ta_resolved = false; ta_has_gamma = false;
+        return ATN_OK;
+    }
+    int taa_reset()
+    {
+        ta_valid = false;
+        return ATN_OK;
+    }
+    // which: 0 the colour, 1 the motion/depth plane (source 2 of taa_resolve), 2 the history
+    int taa_upload(int32_t which, int32_t w, int32_t h, const atn_vec4* host)
+    {
+        if (!host || which < 0 || which > 2) return fail(ATN_ERR_INVALID_ARG, "atn_taa_upload: which = 0 colour, 1 motion/depth, 2 history; host must not be null");
+        if (w <= 0 || h <= 0 || w > kTaaMaxSide || h > kTaaMaxSide) return fail(ATN_ERR_INVALID_ARG, "TAA: bad frame size (1 .. 16384 per side)");
+        ATN_HIP(hipSetDevice(device));
+        int rc = taa_idle();
+        if (rc) return rc;
+        const size_t n = (size_t)w * h;
+        float4* dst;
+        if (which == 2) {
+            rc = taa_ensure(w, h);
+            if (rc) return rc;
+            dst = ta_hist[ta_pos].p;
+        }
+        else {
+            DevBuf<float4>& b = which == 0 ? ta_up_color : ta_up_motion;
+            ATN_HIP(b.resize(n));
+            dst = b.p;
+        }
+        ATN_HIP(hipMemcpyAsync(dst, host, n * sizeof(float4), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        if (which == 2) ta_valid = true;
+        else { ta_up_w[which] = w; ta_up_h[which] = h; }
+        return ATN_OK;
+    }
+    // which: 0 the TAA output (= the new history), 1 the history the last frame read, 2 the gamma plane as float4, 3 as RGBA8
+    int taa_download(int32_t which, void* out)
+    {
+        if (!out || which < 0 || which > 3) return fail(ATN_ERR_INVALID_ARG, "atn_taa_download: which = 0 output, 1 previous history, 2 gamma float, 3 gamma RGBA8; out must not be null");
+        if (!ta_resolved) return fail(ATN_ERR_INVALID_ARG, "atn_taa_download: atn_taa_resolve has not run (at this size)");
+        if (which == 2 && !ta_has_gamma) return fail(ATN_ERR_INVALID_ARG, "atn_taa_download: the last atn_taa_resolve did not ask for the float gamma plane");
+        ATN_HIP(hipSetDevice(device));
+        const int rc = taa_idle();
+        if (rc) return rc;
+        const size_t n = (size_t)ta_w * ta_h;
+        const void* src = which == 0 ? (const void*)ta_hist[ta_pos].p : which == 1 ? (const void*)ta_hist[1 - ta_pos].p
+                        : which == 2 ? (const void*)ta_gamma.p : (const void*)ta_rgba8.p;
+        ATN_HIP(hipMemcpy(out, src, n * (which == 3 ? sizeof(uint32_t) : sizeof(float4)), hipMemcpyDeviceToHost));
+        return ATN_OK;
+    }
+    // ≙ TAA::prePostProc / postPostProc around the fragment shader (taa.cpp:33-60) + GammaCorrection
+    int taa_resolve(int32_t source, int32_t w, int32_t h, int32_t enable, float gamma, atn_vec4* out_f, uint32_t* out_8)
+    {
+        if (!(gamma > 0.0F) || !std::isfinite(gamma)) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: gamma must be finite and > 0");
+        if (w <= 0 || h <= 0 || w > kTaaMaxSide || h > kTaaMaxSide) return fail(ATN_ERR_INVALID_ARG, "TAA: bad frame size (1 .. 16384 per side)");
+        ATN_HIP(hipSetDevice(device));
+        TaaArgs a{};
+        hipStream_t st = stream;
+        switch (source) {
+        case 0:
+            if (!sv_frame_done) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: source 0 needs an atn_svgf_render / atn_svgf_denoise frame");
+            if (w != sv_w || h != sv_h) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: the last SVGF frame has another size");
+            a.cur = sv_out.p; a.motion = sv_motion.p; st = sv_last_fs;
+            break;
+        case 1:
+            if (!rs_rendered) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: source 1 needs an atn_restir_render frame");
+            if (w != rs_w || h != rs_h || w != film_w || h != film_h) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: the last ReSTIR frame has another size");
+            a.cur = film.p; a.motion = rs_last_own_motion ? rs_motion_own.p : rs_motion.p;      // (the frame's film writer ran on `stream`)
+            break;
+        case 2:
+            if (ta_up_w[0] != w || ta_up_h[0] != h || ta_up_w[1] != w || ta_up_h[1] != h)
+                return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: source 2 needs atn_taa_upload of the colour and the motion/depth plane at this size");
+            a.cur = ta_up_color.p; a.motion = ta_up_motion.p;
+            break;
+        default:
+            return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: source 0 (SVGF), 1 (ReSTIR) or 2 (uploaded planes)");
+        }
+        int rc = taa_ensure(w, h);
+        if (rc) return rc;
+        const size_t n = (size_t)w * h;
+        if (out_f && ta_gamma.n < n) {
+            rc = taa_idle();
+            if (rc) return rc;
+            ATN_HIP(ta_gamma.resize(n));
+        }
+        if (!ta_ev) ATN_HIP(hipEventCreateWithFlags(&ta_ev, hipEventDisableTiming));
+        // behind the previous display tail (it wrote this frame's history), whatever stream that ran on
+        if (ta_pending && ta_last_stream != st) ATN_HIP(hipStreamWaitEvent(st, ta_ev, 0));
+        a.hist = ta_hist[ta_pos].p; a.out = ta_hist[1 - ta_pos].p;
+        a.gamma_f = out_f ? ta_gamma.p : nullptr; a.rgba8 = ta_rgba8.p;
+        a.width = w; a.height = h;
+        a.enable = (enable != 0 && ta_valid) ? 1 : 0;       // no history: the frame passes through (docs/TAA.md, first frame)
+        a.inv_gamma = 1.0F / gamma;
+        taa_launch_resolve(taa_launch(w, h), st, a);
+        ATN_HIP(hipGetLastError());
+        ATN_HIP(hipEventRecord(ta_ev, st));
+        ta_pending = true; ta_last_stream = st;
+        ta_pos = 1 - ta_pos;
+        ta_valid = true; ta_resolved = true; ta_has_gamma = out_f != nullptr;
+        if (out_f) ATN_HIP(hipMemcpyAsync(out_f, ta_gamma.p, n * sizeof(float4), hipMemcpyDeviceToHost, st));
+        if (out_8) ATN_HIP(hipMemcpyAsync(out_8, ta_rgba8.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (out_f || out_8) ATN_HIP(hipStreamSynchronize(st));
         return ATN_OK;
     }
 
@@ -3478,6 +3634,18 @@ int atn_svgf_upload(atn_ctx* ctx, int32_t which, int32_t width, int32_t height, 
     return ATN_OK;
 }
 void* atn_svgf_output_device(atn_ctx* ctx) { return ctx ? (void*)ctx->r.sv_out.p : nullptr; }
+
+// the display tail: like atn_svgf_render, atn_taa_resolve does not wait for the frames in flight
+int atn_taa_resolve(atn_ctx* ctx, int32_t source, int32_t width, int32_t height, int32_t enable, float gamma, atn_vec4* out_rgba32f, uint32_t* out_rgba8)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.taa_resolve(source, width, height, enable, gamma, out_rgba32f, out_rgba8); });
+}
+int atn_taa_upload(atn_ctx* ctx, int32_t which, int32_t width, int32_t height, const atn_vec4* host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.taa_upload(which, width, height, host); }); }
+int atn_taa_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.taa_download(which, out_host); }); }
+int atn_taa_reset(atn_ctx* ctx) { CTX_OR_FAIL(ctx); return ctx->r.taa_reset(); }
+void* atn_taa_output_device(atn_ctx* ctx) { return (ctx && ctx->r.ta_resolved) ? (void*)ctx->r.ta_hist[ctx->r.ta_pos].p : nullptr; }
+void* atn_taa_rgba8_device(atn_ctx* ctx) { return (ctx && ctx->r.ta_resolved) ? (void*)ctx->r.ta_rgba8.p : nullptr; }
 
 void* atn_film_device(atn_ctx* ctx) { return ctx ? (void*)ctx->r.film.p : nullptr; }
 void* atn_tile_device(atn_ctx* ctx) { return ctx ? (void*)ctx->r.tile_out.p : nullptr; }

@@ -201,4 +201,15 @@ void motion_launch_capture(uint32_t grid, hipStream_t st, const PathBuffers& pb,
 void motion_launch_geometry(const MotionLaunch& l, hipStream_t st, const MotionArgs& a);
 void motion_launch_copy(hipStream_t st, float4* dst, const float4* src, uint32_t n_quads);
 
+// ---- taa.hip (device/taa.hpp) ----
+struct TaaArgs;
+// the display tail over a frame: svgf_pixel's tiles like the motion pass (8 x 32 pixels per block of 256; x rounded up to a multiple of
+// 8, one strip per XCD); a ragged frame's last tiles are partly outside it
+struct TaaLaunch { uint32_t grid_x, grid_y; };
+inline TaaLaunch taa_launch(int32_t width, int32_t height)
+{
+    return TaaLaunch{ (uint32_t)((((width + 7) / 8) + 7) / 8 * 8), (uint32_t)((height + 31) / 32) };
+}
+void taa_launch_resolve(const TaaLaunch& l, hipStream_t st, const TaaArgs& a);
+
 } // namespace atn

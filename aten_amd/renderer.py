@@ -578,6 +578,42 @@ class PathTracing:
         self._check(self._l.atn_svgf_download(self._ctx, self.SVGF_BUFFERS[name], out.ctypes.data))
         return out
 
+    # ---- the display tail: temporal anti-aliasing + gamma (docs/TAA.md) ----
+    TAA_SOURCES = {"svgf": 0, "restir": 1, "uploaded": 2}
+    TAA_UPLOADS = {"color": 0, "motion_depth": 1, "history": 2}
+    TAA_BUFFERS = {"output": 0, "previous_history": 1, "gamma": 2, "rgba8": 3}
+
+    def taa_resolve(self, width, height, source="svgf", enable=True, gamma=2.2, want_float=False, want_rgba8=False):
+        """aten::TAA + aten::GammaCorrection behind the last frame of `source` ('svgf', 'restir', or 'uploaded': the planes of
+        taa_upload), one kernel launch.  Without want_*: enqueued, no host wait, returns None (the results stay on the device:
+        taa_buffer, atn_taa_output_device).  want_float: the gamma plane float32 [h, w, 4]; want_rgba8: uint8 [h, w, 4] (R, G, B, A)."""
+        gf = np.empty((height, width, 4), np.float32) if want_float else None
+        g8 = np.empty((height, width), np.uint32) if want_rgba8 else None
+        self._check(self._l.atn_taa_resolve(self._ctx, self.TAA_SOURCES[source], width, height, int(bool(enable)), float(gamma),
+                                            gf.ctypes.data if want_float else None, g8.ctypes.data if want_rgba8 else None))
+        self._taa_size = (height, width)
+        if want_rgba8:
+            g8 = g8.view(np.uint8).reshape(height, width, 4)
+        return (gf, g8) if (want_float and want_rgba8) else gf if want_float else g8
+
+    def taa_upload(self, name, data):
+        """'color' / 'motion_depth' (source 'uploaded') or 'history', float32 [h, w, 4], row 0 = bottom."""
+        data = np.ascontiguousarray(data, np.float32)
+        h, w = data.shape[:2]
+        self._check(self._l.atn_taa_upload(self._ctx, self.TAA_UPLOADS[name], w, h, data.ctypes.data))
+
+    def taa_buffer(self, name):
+        """Of the last taa_resolve: 'output' (= the new history), 'previous_history', 'gamma' (float32 [h, w, 4]; needs want_float) or
+        'rgba8' (uint8 [h, w, 4])."""
+        h, w = self._taa_size
+        which = self.TAA_BUFFERS[name]
+        out = np.empty((h, w), np.uint32) if which == 3 else np.empty((h, w, 4), np.float32)
+        self._check(self._l.atn_taa_download(self._ctx, which, out.ctypes.data))
+        return out.view(np.uint8).reshape(h, w, 4) if which == 3 else out
+
+    def taa_reset(self):
+        self._check(self._l.atn_taa_reset(self._ctx))
+
     def kernel_times(self):
         ms = np.zeros(len(K_NAMES), np.float32); n = np.zeros(len(K_NAMES), np.uint32)
         self._check(self._l.atn_get_kernel_times(self._ctx, ms.ctypes.data, n.ctypes.data))

@@ -496,6 +496,37 @@ int atn_svgf_denoise(atn_ctx* ctx, const atn_destination* dst, int32_t compute_m
 int atn_svgf_upload(atn_ctx* ctx, int32_t which, int32_t width, int32_t height, const atn_vec4* host);
 void* atn_svgf_output_device(atn_ctx* ctx);
 
+/* ---- The display tail: temporal anti-aliasing and gamma (aten::TAA + aten::GammaCorrection; docs/TAA.md) ---------------------------
+ * ≙ the two post-processes svgf_renderer and deformation_renderer put behind the renderer (src/libaten/filter/taa.{h,cpp},
+ * src/shader/taa_fs.glsl, src/shader/gamma_fs.glsl), as ONE kernel launch per frame: TAA from the frame's colour, the history and the
+ * motion/depth plane; the history write (the TAA output IS the next frame's history); pow(rgb, 1 / gamma) clamped to [0, 1] as RGBA8
+ * (R in the low byte, round to nearest) and, when asked for, as float4.  The gamma planes are never fed back.
+ *   atn_taa_resolve: source 0 = the output and motion/depth plane of the last atn_svgf_render / atn_svgf_denoise frame, 1 = the film
+ *                    and motion/depth plane of the last atn_restir_render frame, 2 = the planes of atn_taa_upload.  Enqueued behind
+ *                    the frame that produced the source and ordered against the next frame on the device; the host waits only when
+ *                    an output pointer is given (out_rgba32f: atn_vec4[w*h], out_rgba8: uint32[w*h]; either may be NULL; the float
+ *                    gamma plane is written only when out_rgba32f is given).  enable = 0: every pixel passes through (the current
+ *                    texel, alpha 1) and the history still advances.  The first frame after atn_taa_reset, a size change or context
+ *                    creation has no history and passes through as well.  ATN_ERR_INVALID_ARG for gamma <= 0 or not finite, a size
+ *                    outside 1 .. 16384 per side, source 0 / 1 without a frame of that renderer or with another size, source 2 without
+ *                    both planes uploaded at that size.  (A frame without a motion/depth plane cannot exist: atn_svgf_render and
+ *                    atn_restir_render refuse compute_motion = 0 without a caller's plane themselves.)
+ *   atn_taa_upload:  which = 0 the colour, 1 the motion/depth plane {prev - cur in screen fractions, depth (< 0: a miss), 1}, 2 the
+ *                    history (at a new size it starts a new history).  For tests and callers with a renderer of their own.
+ *   atn_taa_download: which = 0 the TAA output (= the new history), 1 the history the last frame read (meaningful when it had one),
+ *                    2 the gamma plane as atn_vec4[w*h] (if the last resolve asked for it), 3 as RGBA8 uint32[w*h].
+ *   atn_taa_reset:   forget the history.  atn_svgf_reset, atn_restir_reset and atn_upload_scene do NOT; a size change does.
+ *   atn_taa_output_device / atn_taa_rgba8_device: the last frame's TAA output (float4[w*h]) / RGBA8 plane in device memory (NULL
+ *                    before the first atn_taa_resolve); the output pointer changes every frame (ping-pong).
+ * One GPU only: atn_mgpu_* has no form of it.  Additive entry points: atn_abi_version stays 3. */
+int atn_taa_resolve(atn_ctx* ctx, int32_t source, int32_t width, int32_t height, int32_t enable, float gamma,
+                    atn_vec4* out_rgba32f, uint32_t* out_rgba8);
+int atn_taa_upload(atn_ctx* ctx, int32_t which, int32_t width, int32_t height, const atn_vec4* host);
+int atn_taa_download(atn_ctx* ctx, int32_t which, void* out_host);
+int atn_taa_reset(atn_ctx* ctx);
+void* atn_taa_output_device(atn_ctx* ctx);
+void* atn_taa_rgba8_device(atn_ctx* ctx);
+
 /* ---- stage entry points (parity tests; each mirrors one reference function) ---------------- */
 /* GeneratePath for every pixel (src/libaten/renderer/pathtracing/pathtracing_impl.h:65-110). */
 int atn_generate_paths(atn_ctx* ctx, int32_t width, int32_t height, int32_t sample, uint32_t frame, atn_ray* out_host);

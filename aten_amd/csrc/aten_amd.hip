@@ -119,6 +119,9 @@ public:
     bool opt_node_layout = true, opt_planar_lights = true;      // ATEN_AMD_NODE_LAYOUT / ATEN_AMD_PLANAR_LIGHTS at creation; atn_set_upload_options
     bool env_atrous4 = true;    // SVGF a-trous levels with four pixels per thread (k_svgf_atrous4); ATEN_AMD_SVGF_ATROUS4=0: one pixel per thread
     int env_shade_waves = 0;    // ATEN_AMD_SHADE_WAVES=4|5 forces the k_shade_wn flavour (default: plan_pass)
+    bool rr_lookahead_twin = true;      // ATEN_AMD_RR_LOOKAHEAD_TWIN=0 (experiments): doomed rays stop at their first hit on the list as given
+    int rr_lookahead = 1;       // ATEN_AMD_RR_LOOKAHEAD / atn_set_rr_lookahead: 0 = off, 1 = render()'s serial passes on scenes that qualify
+                                // (counted frames keep the reference's accounting: off), 2 = counted frames too (atn_rr_lookahead_stats)
     int env_flavour = -1;       // ATEN_AMD_TRACE: 1 = the refill walk, 0 = the plain walk for every launch (default: refill_walk)
 
     // scene (HBM-resident after UpdateSceneData)
@@ -762,7 +765,7 @@ public:
     std::vector<Span> spans;
     size_t ev_used = 0;
     hipStream_t prof_stream = nullptr;
-    uint64_t host_stats[8] = {};
+    uint64_t host_stats[16] = {};
 
     int fail(int code, const std::string& msg) { last_error = msg; return code; }
 
@@ -787,6 +790,8 @@ public:
         if (const char* e = std::getenv("ATEN_AMD_SVGF_ATROUS4")) env_atrous4 = e[0] != '0';     // 0: the one-pixel-per-thread a-trous kernel
         if (const char* e = std::getenv("ATEN_AMD_SHADE_WAVES")) { const int v = std::atoi(e); if (v == 4 || v == 5) env_shade_waves = v; }   // else: plan_pass
         if (const char* e = std::getenv("ATEN_AMD_LDS_NODES")) env_lds_nodes = std::atoi(e) != 0;
+        if (const char* e = std::getenv("ATEN_AMD_RR_LOOKAHEAD")) rr_lookahead = std::max(0, std::min(2, std::atoi(e)));
+        if (const char* e = std::getenv("ATEN_AMD_RR_LOOKAHEAD_TWIN")) rr_lookahead_twin = std::atoi(e) != 0;
         if (const char* e = std::getenv("ATEN_AMD_ANYHIT_TWIN")) env_anyhit_twin = std::max(0, std::min(2, std::atoi(e)));
         if (const char* e = std::getenv("ATEN_AMD_ANYHIT_TWIN_DIRS")) env_anyhit_twin_dirs = std::atoi(e) == 1 ? 1 : 8;
         if (const char* e = std::getenv("ATEN_AMD_NODE_LAYOUT")) opt_node_layout = std::atoi(e) != 0;     // 0: bottom-level records in walk order
@@ -1475,8 +1480,8 @@ public:
             counters_depth = max_depth + 2;
         }
         if (!stats.p) {
-            ATN_HIP(stats.resize(8));
-            ATN_HIP(hipMemsetAsync(stats.p, 0, 64, stream));
+            ATN_HIP(stats.resize(16));
+            ATN_HIP(hipMemsetAsync(stats.p, 0, 128, stream));
         }
         return ATN_OK;
     }
@@ -1613,6 +1618,14 @@ public:
         }, count, p.refill);
     }
 
+    // Does this frame of render() run the roulette look-ahead (kernels.hpp, F_DOOMED)?  The scene has to qualify (DevScene::rr_lookahead);
+    // counted frames stay the reference's own accounting unless mode 2 asks for the look-ahead's; the relaxed-math shade kernel (not
+    // the parity path) has no look-ahead flavour.
+    bool rr_lookahead_frame(bool count) const
+    {
+        return rr_lookahead >= (count ? 2 : 1) && scene.rr_lookahead != 0 && !shade_math_relaxed && scene.material_set <= kMsAnalytic;
+    }
+
     template <bool SVGF>
     void launch_shade(const PassPlan& p, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, int32_t b, const SvgfShade& sv)
     {
@@ -1620,8 +1633,18 @@ public:
             relaxed_launch_shade(scene.material_set, p.shade_waves, p.shade_grid, st, pb, scene, fp, camera, b);
             return;
         }
+        // the look-ahead's flavour from the first launch that can mark a path (bounce + 1 > rr_depth) on; the launches before it are the
+        // kernel as it is without -- and so is every launch of a material set that has no such flavour (none of those qualifies:
+        // rr_lookahead_frame; unmarked, no path is ever doomed)
+        const bool la = !SVGF && pb.doomed_bit != 0u && b >= fp.rr_depth;
         with_shade_flavour(scene.material_set, p.shade_waves, [&](auto k) {
             using K = decltype(k);
+            if constexpr (!SVGF && K::waves != 0) {
+                if (la) {
+                    hipLaunchKernelGGL((k_shade_wn<false, K::ms, K::waves, true>), dim3(p.shade_grid), dim3(256), 0, st, pb, scene, fp, camera, b, sv);
+                    return;
+                }
+            }
             if constexpr (K::waves == 0) hipLaunchKernelGGL((k_shade<SVGF, K::ms>), dim3(p.shade_grid), dim3(256), 0, st, pb, scene, fp, camera, b, sv);
             else hipLaunchKernelGGL((k_shade_wn<SVGF, K::ms, K::waves>), dim3(p.shade_grid), dim3(256), 0, st, pb, scene, fp, camera, b, sv);
         });
@@ -1695,6 +1718,8 @@ public:
             hipStream_t st = nb > 1 ? bstream[k] : stream;
             if (nb > 1) ATN_HIP(hipStreamWaitEvent(st, ev_fork, 0));
             PathBuffers pb = buffers(count, k, begin);
+            pb.doomed_bit = (!SVGF && rr_lookahead_frame(count)) ? F_DOOMED : 0u;
+            pb.doomed_stop = rr_lookahead_twin ? kInf : 1.0e30F;        // (kInf is the largest finite float: any smaller bound beyond every scene's distances stops the walk and is not the twins' key)
             fp.slot_begin = (int32_t)begin; fp.slot_end = (int32_t)end;
             const uint32_t n = end - begin;
             const PassPlan plan = plan_pass(SVGF ? PassKind::Svgf : PassKind::Serial, n);
@@ -1802,7 +1827,7 @@ public:
         if (rc) return rc;
         FrameParams fp = frame_params(*d);
         if (count) {
-            ATN_HIP(hipMemsetAsync(stats.p, 0, 64, stream));
+            ATN_HIP(hipMemsetAsync(stats.p, 0, 128, stream));
             ATN_HIP(cost.resize((size_t)2 * n_slots));
             ATN_HIP(cost_film.resize((size_t)2 * d->width * d->height));
             ATN_HIP(hipMemsetAsync(cost.p, 0, (size_t)2 * n_slots * sizeof(uint32_t), stream));
@@ -1827,12 +1852,16 @@ public:
 
         if (count) {
             hipLaunchKernelGGL(k_cost_to_pixels, dim3(g_all), dim3(256), 0, stream, fp, (const uint32_t*)cost.p, cost_film.p);
-            ATN_HIP(hipMemcpyAsync(host_stats, stats.p, 64, hipMemcpyDeviceToHost, stream));
+            ATN_HIP(hipMemcpyAsync(host_stats, stats.p, 128, hipMemcpyDeviceToHost, stream));
         }
         if (out_host) {
             ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
         }
         if (out_host || count) ATN_HIP(hipStreamSynchronize(stream));
+        if (count) {
+            // the closest-hit kernels count every ray of their queue: the doomed ones (mode 2 only, else zero) are reported on their own
+            host_stats[0] -= host_stats[8]; host_stats[3] -= host_stats[10]; host_stats[4] -= host_stats[11];
+        }
         return ATN_OK;      // profiling spans are resolved lazily in kernel_times() (no sync in the frame loop)
     }
 
@@ -3442,6 +3471,24 @@ int atn_set_regeneration(atn_ctx* ctx, int32_t mode)
     CTX_QUIET_OR_FAIL(ctx);
     if (mode < 0 || mode > 1) return ctx->r.fail(ATN_ERR_INVALID_ARG, "regeneration mode out of range");
     ctx->r.regen_mode = mode;
+    return ATN_OK;
+}
+int atn_set_rr_lookahead(atn_ctx* ctx, int32_t mode)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    if (mode < 0 || mode > 2) return ctx->r.fail(ATN_ERR_INVALID_ARG, "roulette look-ahead mode out of range");
+    ctx->r.rr_lookahead = mode;
+    return ATN_OK;
+}
+int32_t atn_rr_lookahead_active(atn_ctx* ctx)
+{
+    return (ctx && ctx->r.has_scene && ctx->r.rr_lookahead_frame(false)) ? 1 : 0;
+}
+int atn_rr_lookahead_stats(atn_ctx* ctx, uint64_t out[4])
+{
+    CTX_OR_FAIL(ctx);
+    if (!out) return ctx->r.fail(ATN_ERR_INVALID_ARG, "null output");
+    for (int i = 0; i < 4; i++) out[i] = ctx->r.host_stats[8 + i];
     return ATN_OK;
 }
 int atn_set_shade_math(atn_ctx* ctx, int32_t mode)

@@ -65,6 +65,16 @@ constexpr uint32_t kRegenSampleShift = 13u, kRegenSampleMask = 2047u;
 constexpr uint32_t kRegenItemHiShift = 24u;
 constexpr uint32_t kRegenDimMask = 4095u, kRegenItemLoShift = 12u, kRegenItemLoMask = (1u << 20) - 1u;
 constexpr uint32_t kRegenMaxSpp = 1u << 11, kRegenMaxItems = 1u << 28;
+// ---- the roulette look-ahead (render()'s serial passes on scenes that qualify: DevScene::rr_lookahead) ------------
+// Whether a path loses the roulette at its NEXT vertex is known when shade stores it: russian_prob is max3 of the throughput it arrives
+// with, the draw is a pure function of the stored sampler position once nothing the hit decides sits in front of it (no material that
+// draws before the roulette or skips NEE's draws, the light pick independent of the hit).  Such a path is DOOMED: a miss adds the
+// environment as ever, a hit ends it without adding anything (no emissive surface in the scene; HitShadowRay runs only for paths that
+// go on).  So its ray asks "hit anything or not" -- an any-hit walk, exact for the reason the shadow rays' is (until the first accepted
+// hit t_max is the constant the ray came with: whether any triangle is accepted does not depend on the order) -- and its hit is not
+// shaded.  The mark is a bit of ray_d.w above the regenerated pool's five flag bits; the pool and the other renderers never set it
+// and their closest-hit jobs never look for it (ClosestJobT::doomed_bit = 0).
+constexpr uint32_t F_DOOMED = 32u;
 constexpr uint32_t kShadowFinalFlag = 0x20000000u;        // in sh_c.w / sh_d.w: the shadow ray of a path's LAST vertex -- its light goes to `pend`, not `contrib`
 
 struct PathBuffers {
@@ -87,7 +97,9 @@ struct PathBuffers {
     uint32_t* fetch_closest;    // [maxDepth] dynamic job-fetch cursors of the trace kernels
     uint32_t* fetch_shadow;     // [maxDepth]
     uint32_t* cost;     // [2 * slots] node visits / triangle tests of the pixel's walks this sample (count_stats frames; else null)
-    unsigned long long* stats; // [8]: closest rays, shadow rays, hits, closest node visits, closest tri tests, shadow node visits, shadow tri tests
+    unsigned long long* stats; // [16]: closest rays, shadow rays, hits, closest node visits, closest tri tests, shadow node visits, shadow tri tests,
+                               // [7] the traversal probe's fetch cursor; [8..11] doomed rays, doomed hits, their node visits, their tri tests
+                               // (counted look-ahead frames: [0], [3], [4] include the doomed rays on the device, the host takes them out)
     float4* pend;       // regeneration only: contrib.xyz of the pixel's previous sample while its last shadow ray is in flight (F_PENDING)
     // regeneration only: what k_regen_shade writes for k_regen_compact -- chunk c's surviving / regenerated entries and shadow entries
     // in region c (chunk_size entries wide) of q_regions / sh_regions, their numbers in region_counts[2 * c], [2 * c + 1], and the
@@ -98,6 +110,9 @@ struct PathBuffers {
     uint32_t* group_counts;
     const uint32_t* valid_list;     // regeneration only: [n_valid] the shard's pixel slots that lie inside the frame, ascending (items index it)
     uint32_t* next_item;            // regeneration only: the first item no slot has taken yet
+    uint32_t doomed_bit;            // F_DOOMED in the serial passes of a frame that runs the roulette look-ahead, 0 everywhere else
+    float doomed_stop;              // the stop_t a doomed ray is handed out with: kInf = first accepted hit, through the any-hit twins; 1e30
+                                    // = first accepted hit on the list as given (ATEN_AMD_RR_LOOKAHEAD_TWIN=0, experiments)
 };
 
 struct FrameParams {
@@ -443,15 +458,23 @@ ATN_DEV void trace_dispatch(const DevScene& sc, uint32_t count, uint32_t* fetch_
     }
 }
 
-struct ClosestJob {
+// DOOM: the job looks for the roulette look-ahead's mark (F_DOOMED, above) and hands a doomed ray out as an any-hit ray: stop_t =
+// +inf (doomed_stop), so the first accepted hit ends the walk and walk_start / the TLAS-leaf step send it into the list's any-hit twin; finish()
+// writes whichever hit ended it and shade reads only its objid >= 0.  `doomed_bit` is 0 wherever no launch can hold such a ray (the
+// regenerated pool keeps its bounce in those bits of ray_d.w).  DOOM = false keeps stop_t a compile-time constant: the launch of a
+// sample's primary rays (launch.hpp, trace_launch) and the unfused launches, which walk a doomed ray to its closest hit -- as exact.
+template <bool DOOM>
+struct ClosestJobT {
     PathBuffers pb;
     const uint32_t* __restrict__ q;
     float t_min;
+    uint32_t doomed_bit;
+    float doomed_stop;
     ATN_DEV void fetch(uint32_t j, float4& a, float4& b, float& stop_t) const { fetch_slot(q[j], a, b, stop_t); }
     ATN_DEV void fetch_slot(uint32_t slot, float4& a, float4& b, float& stop_t) const
     {
         const float4 ro = pb.ray_o[slot], rd = pb.ray_d[slot];
-        stop_t = -kInf;
+        stop_t = (DOOM && (__float_as_uint(rd.w) & doomed_bit)) ? doomed_stop : -kInf;
         a = make_float4(ro.x, ro.y, ro.z, kInf);
         b = make_float4(rd.x, rd.y, rd.z, __uint_as_float(slot));
     }
@@ -463,14 +486,19 @@ struct ClosestJob {
     ATN_DEV void cost(uint32_t slot, uint32_t nodes, uint32_t tris) const
     {
         if (pb.cost) { atomicAdd(&pb.cost[2u * slot], nodes); atomicAdd(&pb.cost[2u * slot + 1u], tris); }
+        if (DOOM && doomed_bit && pb.stats && (__float_as_uint(pb.ray_d[slot].w) & doomed_bit)) {     // (counted look-ahead frames)
+            atomicAdd(&pb.stats[8], 1ull); atomicAdd(&pb.stats[10], (unsigned long long)nodes); atomicAdd(&pb.stats[11], (unsigned long long)tris);
+        }
     }
 };
+using ClosestJob = ClosestJobT<false>;
 
+// (the counting flavour serves the counted look-ahead frames too: it looks for doomed rays)
 template <bool COUNT, bool REFILL>
 __global__ void __launch_bounds__(kTraceBlock > 256 ? kTraceBlock : 256) k_trace_closest(PathBuffers pb, DevScene sc, int32_t bounce)
 {
     const uint32_t count = pb.q_count[bounce];
-    const ClosestJob job{ pb, pb.queue[bounce & 1], kEps };
+    const ClosestJobT<COUNT> job{ pb, pb.queue[bounce & 1], kEps, pb.doomed_bit, pb.doomed_stop };
     TravCounters tc{};
     trace_dispatch<COUNT, REFILL>(sc, count, &pb.fetch_closest[bounce], job, &tc);
     if (COUNT) {
@@ -507,7 +535,10 @@ struct SvgfShade {
 #ifndef ATN_SHADE_PARTITION
 #define ATN_SHADE_PARTITION 1
 #endif
-struct ShadePartShared { uint32_t perm[kChunk]; uint32_t wcount[kChunkItems][4][2]; };
+// In a launch that can hold doomed paths (LA, below) the classes are three -- live hits, doomed hits, misses: a doomed hit is not
+// shaded at all, and only a wave of nothing but such entries saves the instructions.
+template <int NC> struct ShadePartSharedT { uint32_t perm[kChunk]; uint32_t wcount[kChunkItems][4][NC]; };
+using ShadePartShared = ShadePartSharedT<2>;
 // REGEN: what brings a chunk's results back into the order of its queue entries (inv: where in the chunk an entry of the permutation
 // came from; oflag: per queue entry, bit 0 = goes on to the next stage, bit 1 = has a shadow ray).  The hits-first permutation is for
 // the shading only: a queue written in permuted order is scrambled a little more by every stage, and after some tens of stages a
@@ -517,13 +548,19 @@ template <bool ON> struct ShadeOrderShared { uint16_t inv[ON ? kChunk : 1]; uint
 // REGEN: the path-regeneration flavour (k_regen_shade).  `bounce_arg` is then the STAGE of the pool -- it selects queues and counters --
 // and a path's own bounce, sample and frame come out of its state words; a path that ends runs its sample epilogue here and the
 // pixel's next primary ray takes its place in the next stage's queue.
-template <bool SVGF, int MS, bool REGEN = false>
+// LA: the roulette look-ahead's flavour (F_DOOMED, above), launched by render()'s serial passes from bounce rr_depth on when the scene
+// qualifies: it MARKS the paths it stores that will lose the next vertex's roulette (launches with bounce + 1 > rr_depth) and ENDS
+// the marked ones that hit (launches with bounce > rr_depth) without shading them.  Every other launch runs LA = false: the code as
+// it was.
+template <bool SVGF, int MS, bool REGEN = false, bool LA = false>
 ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const atn_camera_param& cam, int32_t bounce_arg, const SvgfShade& sv,
                         const RegenOut& ro = RegenOut{})
 {
+    static_assert(!LA || (!SVGF && !REGEN && ATN_SHADE_PARTITION), "the look-ahead is the serial path tracer's");
     __shared__ BlockAppendShared sh;
+    const bool la_ends = LA && bounce_arg > fp.rr_depth;       // (wave-uniform) this launch's queue can hold doomed paths
 #if ATN_SHADE_PARTITION
-    __shared__ ShadePartShared part;
+    __shared__ ShadePartSharedT<LA ? 3 : 2> part;
     __shared__ ShadeOrderShared<REGEN> order[1];
 #endif
     const uint32_t count = pb.q_count[bounce_arg];
@@ -539,38 +576,64 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
       uint32_t push_bits = 0;     // bit k: item k goes on to the next bounce; bit 16 + k: it has a shadow ray (one register, not two)
 #if ATN_SHADE_PARTITION
       const uint32_t n_valid = count - chunk < chunk_size ? count - chunk : chunk_size;
+      uint32_t doomed_lo = 0, doomed_hi = 0;      // LA: the chunk's doomed hits are entries [doomed_lo, doomed_hi) of the permutation
       {
           const uint32_t tid = here_v(threadIdx.x);      // (the LDS addresses below are computed per chunk, not carried across it)
           const uint32_t lane = tid & 63u, wave = tid >> 6;
-          uint32_t hitmask = 0;
           __syncthreads();            // the previous chunk's append has read `part.perm`
+          // The classes, stable: hits first, misses last, and in a launch that can hold doomed paths (LA) the doomed hits between
+          // them -- the flag word is read only there.  Two bits per item: its class, 3 = no entry.
+          constexpr uint32_t NC = LA ? 3u : 2u;
+          uint32_t cls_bits = 0;
 #pragma unroll 1
           for (int k = 0; k < items; k++) {
               const uint32_t j = chunk + (uint32_t)k * 256u + threadIdx.x;
-              const bool valid = j < count;
-              const bool hit = valid && __float_as_int(pb.isect[q[j]].x) >= 0;
-              if (hit) hitmask |= 1u << k;
-              const unsigned long long bh = __ballot(hit), bm = __ballot(valid && !hit);
-              if (lane == 0) { part.wcount[k][wave][0] = (uint32_t)__popcll(bh); part.wcount[k][wave][1] = (uint32_t)__popcll(bm); }
-          }
-          if (pb.stats) wave_add_stat(&pb.stats[2], (uint32_t)__popc(hitmask));   // (counted frames only; per chunk, so that no counter lives across the shading)
-          __syncthreads();
-          uint32_t total_hits = 0;
-          for (int k = 0; k < items; k++) for (uint32_t w = 0; w < 4; w++) total_hits += part.wcount[k][w][0];
-          uint32_t before_h = 0, before_m = 0;
-#pragma unroll 1
-          for (int k = 0; k < items; k++) {
-              const uint32_t j = chunk + (uint32_t)k * 256u + threadIdx.x;
-              const bool valid = j < count;
-              const bool hit = (hitmask >> k) & 1u;
-              const unsigned long long bh = __ballot(hit), bm = __ballot(valid && !hit);
-              uint32_t bh_w = before_h, bm_w = before_m;
-              for (uint32_t w = 0; w < 4; w++) {
-                  if (w < wave) { bh_w += part.wcount[k][w][0]; bm_w += part.wcount[k][w][1]; }
-                  before_h += part.wcount[k][w][0]; before_m += part.wcount[k][w][1];
+              uint32_t cls = 3u;
+              if (j < count) {
+                  const uint32_t s = q[j];
+                  cls = __float_as_int(pb.isect[s].x) >= 0 ? 0u : NC - 1u;
+                  if constexpr (LA) { if (la_ends && cls == 0u && (__float_as_uint(pb.ray_d[s].w) & F_DOOMED)) cls = 1u; }
               }
-              if (valid) {
-                  const uint32_t pos = hit ? bh_w + bits_below_lane(bh) : total_hits + bm_w + bits_below_lane(bm);
+              cls_bits |= cls << (2 * k);
+#pragma unroll
+              for (uint32_t c = 0; c < NC; c++) {
+                  const uint32_t n = (uint32_t)__popcll(__ballot(cls == c));
+                  if (lane == 0) part.wcount[k][wave][c] = n;
+              }
+          }
+          if (pb.stats) {     // (counted frames only; per chunk, so that no counter lives across the shading): hits that are shaded, hits the look-ahead ended
+              uint32_t n0 = 0, n1 = 0;
+              for (int k = 0; k < items; k++) { const uint32_t c = (cls_bits >> (2 * k)) & 3u; n0 += c == 0u; n1 += c == 1u; }
+              wave_add_stat(&pb.stats[2], n0);
+              if constexpr (LA) wave_add_stat(&pb.stats[9], n1);
+          }
+          __syncthreads();
+          uint32_t base[NC];      // where a class begins in the permutation, then: ... where item k's entries of it begin
+          base[0] = 0u;
+#pragma unroll
+          for (uint32_t c = 1; c < NC; c++) {
+              uint32_t t = 0;
+              for (int k = 0; k < items; k++) for (uint32_t w = 0; w < 4; w++) t += part.wcount[k][w][c - 1u];
+              base[c] = base[c - 1u] + t;
+          }
+          if constexpr (LA) { doomed_lo = base[1]; doomed_hi = base[2]; }
+#pragma unroll 1
+          for (int k = 0; k < items; k++) {
+              const uint32_t j = chunk + (uint32_t)k * 256u + threadIdx.x;
+              const uint32_t cls = (cls_bits >> (2 * k)) & 3u;
+              uint32_t pos = 0;
+#pragma unroll
+              for (uint32_t c = 0; c < NC; c++) {
+                  const unsigned long long bc = __ballot(cls == c);
+                  uint32_t mine = base[c];
+                  for (uint32_t w = 0; w < 4; w++) {
+                      const uint32_t n = part.wcount[k][w][c];
+                      if (w < wave) mine += n;
+                      base[c] += n;
+                  }
+                  if (cls == c) pos = mine + bits_below_lane(bc);
+              }
+              if (cls != 3u) {
                   part.perm[pos] = q[j];
                   if constexpr (REGEN) order[0].inv[pos] = (uint16_t)(j - chunk);
               }
@@ -591,16 +654,31 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
         uint32_t rg_need_bits = 0u;     // REGEN: bit 2 = the slot needs a new item, bit 3 = ... and its last path's epilogue is pending
         uint32_t slot = 0;
 
-        if (valid) {
+        bool live = valid;
 #if ATN_SHADE_PARTITION
-            slot = part.perm[e];
+        if (valid) slot = part.perm[e];
 #else
-            slot = q[j];
+        if (valid) slot = q[j];
 #endif
+#if ATN_SHADE_PARTITION
+        if constexpr (LA) {
+            // a doomed path that hit: the flags the full path would have ended with -- the roulette of this vertex terminates it, and
+            // what PathTracing::shade computes behind that (the BSDF sample, the throughput) nobody reads -- and nothing else: no hit
+            // evaluation, no texture, no draw.  A doomed path that missed takes ShadeMiss below like any other.
+            if (e >= doomed_lo && e < doomed_hi) {        // (the pre-pass classified it: one word read, one word written)
+                const uint32_t f = __float_as_uint(pb.ray_d[slot].w);
+                pb.ray_d[slot].w = __uint_as_float((f & ~F_DOOMED) | F_HIT | F_TERMINATED);
+                live = false;
+            }
+        }
+#endif
+
+        if (live) {
             const float4 ro4 = pb.ray_o[slot], rd4 = pb.ray_d[slot];
             const f3 ray_org = mk3(ro4), ray_dir = mk3(rd4);
             float pdfb = ro4.w;
             uint32_t flags = __float_as_uint(rd4.w);
+            if constexpr (LA) flags &= ~F_DOOMED;       // (a doomed miss: the mark has done its work)
             uint32_t rg_sample = 0u, rg_item = 0u;      // REGEN: the path's sample of its item, the item (frame of the burst, pixel)
             int32_t bounce = bounce_arg;
             if constexpr (REGEN) {
@@ -885,8 +963,31 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                         }
                         const f3 no = ray_offset(rec.p, ray_along_normal);
                         const f3 nd = normalize(next_dir);     // ray(o, d, n) constructor re-normalises (ray.h:17-24)
+                        uint32_t mark = 0u;
+                        if constexpr (LA) {
+                            // The roulette of the path's NEXT vertex (the block "ComputeRussianProbability" above, one bounce later), from
+                            // what is final here: the sampler position just stored, advanced over NEE's draws as that vertex will advance it
+                            // (every material of a qualifying scene takes NEE and draws nothing in front of it), and the stored throughput.
+                            // Same functions on the same bits; a zero or NaN throughput takes no draw and is not doomed.
+                            if (bounce + 1 > fp.rr_depth && bounce + 1 < fp.max_depth) {
+                                Cmj la; la.idx = smp.idx; la.dim = smp.dim; la.scramble = smp.scramble;
+                                if (sc.n_lights > 0) {
+                                    int32_t pick = 0;
+                                    if (here(sc.n_lights) > 1) {
+                                        pick = (int32_t)(cmj_next(la) * (float)here(sc.n_lights));
+                                        pick = pick < sc.n_lights - 1 ? pick : sc.n_lights - 1;
+                                    }
+                                    else la.dim++;
+                                    la.dim += light_sample_draws(sc.lights[pick], sc);
+                                }
+                                if (dot(throughput, throughput) > 0) {
+                                    const float p = cmj_next(la);
+                                    if (p >= max3(throughput)) mark = F_DOOMED;
+                                }
+                            }
+                        }
                         pb.ray_o[slot] = make_float4(no.x, no.y, no.z, pdfb);
-                        pb.ray_d[slot] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(flags));
+                        pb.ray_d[slot] = make_float4(nd.x, nd.y, nd.z, __uint_as_float(flags | mark));
                         wrote_ray = true;
                         push_next = (bounce + 1 < fp.max_depth);
                     }
@@ -1010,10 +1111,10 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
 #endif
 }
 
-template <bool SVGF, int MS>
+template <bool SVGF, int MS, bool LA = false>
 __global__ void ATN_SHADE_ATTR __launch_bounds__(256) k_shade(PathBuffers pb, DevScene sc, FrameParams fp, atn_camera_param cam, int32_t bounce, SvgfShade sv)
 {
-    shade_body<SVGF, MS>(pb, sc, fp, cam, bounce, sv);
+    shade_body<SVGF, MS, false, LA>(pb, sc, fp, cam, bounce, sv);
 }
 // The three smaller material sets need 124 / 125 / 131 VGPRs (built without the SLP vectoriser, build.py): held to 128 they run
 // 4 waves per SIMD without a spill.  WAVES = 5 holds them to 96 registers with 16-18 spilled ones: alone that launch is 3-6 %
@@ -1022,10 +1123,10 @@ __global__ void ATN_SHADE_ATTR __launch_bounds__(256) k_shade(PathBuffers pb, De
 // the Cornell box, -0.2 % on sponza_lod; latency +1-3 % (profiles/r04_variants_shade_waves.txt).  So the host launches WAVES = 5
 // when frames overlap and 4 when a caller waits for every frame.  6 waves (80 registers, 36-47 spilled) lose everywhere.
 // The larger sets (139 .. 205 VGPRs) would spill too much: they keep the compiler's own allocation (k_shade).
-template <bool SVGF, int MS, int WAVES>
+template <bool SVGF, int MS, int WAVES, bool LA = false>
 __global__ void __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) __launch_bounds__(256) k_shade_wn(PathBuffers pb, DevScene sc, FrameParams fp, atn_camera_param cam, int32_t bounce, SvgfShade sv)
 {
-    shade_body<SVGF, MS>(pb, sc, fp, cam, bounce, sv);
+    shade_body<SVGF, MS, false, LA>(pb, sc, fp, cam, bounce, sv);
 }
 
 // HitShadowRay -> HitTestToTargetLight -> scene::hitLight
@@ -1176,7 +1277,7 @@ __global__ void __launch_bounds__(kTraceBlock > 256 ? kTraceBlock : 256) k_trace
 template <bool ALPHA, bool REGEN = false>
 struct FusedJob {
     ShadowJob<ALPHA, REGEN> s;
-    ClosestJob c;
+    ClosestJobT<!REGEN> c;
     uint32_t n_shadow;
     float t_min;
     ATN_DEV void fetch(uint32_t j, float4& a, float4& b, float& stop_t) const
@@ -1210,7 +1311,7 @@ __global__ void ATN_TRACE_ATTR __launch_bounds__(kTraceBlock > 256 ? kTraceBlock
 {
     const uint32_t n_shadow = bs >= 0 ? pb.sh_count[bs] : 0u;
     const uint32_t n_closest = bc >= 0 ? pb.q_count[bc] : 0u;
-    const FusedJob<ALPHA, REGEN> job{ ShadowJob<ALPHA, REGEN>{ pb, sc, kEps }, ClosestJob{ pb, pb.queue[(bc >= 0 ? bc : 0) & 1], kEps }, n_shadow, kEps };
+    const FusedJob<ALPHA, REGEN> job{ ShadowJob<ALPHA, REGEN>{ pb, sc, kEps }, ClosestJobT<!REGEN>{ pb, pb.queue[(bc >= 0 ? bc : 0) & 1], kEps, REGEN ? 0u : pb.doomed_bit, pb.doomed_stop }, n_shadow, kEps };
     TravCounters tc{};
     trace_dispatch<false, REFILL, FusedJob<ALPHA, REGEN>, LDSN>(sc, n_shadow + n_closest, &pb.fetch_closest[launch], job, &tc);
 }

@@ -143,6 +143,7 @@ struct DevScene {
     int32_t ibl_w, ibl_h;
     int32_t ibl_importance;             // 1 = sample the IBL light from those tables (ImageBasedLight::sample, ibl.cpp:180-230)
     int32_t tex_bilinear;               // 1 = texture::AtWithBilinear (image/texture.cpp:77-125) instead of texture::at
+    int32_t rr_lookahead;               // 1 = the roulette look-ahead is valid on this scene (host/scene_upload.hpp: rr_lookahead_valid; kernels.hpp, F_DOOMED)
 };
 
 } // namespace atn

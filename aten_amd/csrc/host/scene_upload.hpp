@@ -374,6 +374,32 @@ constexpr double kTwinPays = 0.95;
 // from an LDS copy (kLdsNodesMaxBytes of records) gets no twin that would push it out of that path.  (The 31-bit offset limit of the
 // links is a separate, later check.)
 constexpr uint64_t kTwinBudgetBytes = 512ull << 20;
+// The roulette look-ahead (device/kernels.hpp, F_DOOMED) decides at vertex b whether the path loses the roulette of vertex b + 1.  That
+// is exact only if, whatever vertex b + 1 hits, (1) the sampler dimension of its roulette draw is the same and (2) a terminated hit adds
+// nothing.  shade_body draws in front of the roulette: toon_bsdf (Toon / StylizedBrdf at a first hit; deeper they turn into their base
+// material, which may be singular), apply_normal (CarPaint's shared random number), and NEE's light pick + light_sample_draws -- taken
+// iff the material is neither SINGULAR nor TRANSLUCENT, the picked light a function of the draw alone.  A hit adds light only on an
+// emissive surface (HitImplicitLight), which an any-hit walk could not tell from whatever lies in front of it.  So EVERY uploaded
+// material, the appended white-diffuse fallback included, has to be one of the types below without those attributes; any other type
+// (and any unknown one) switches the look-ahead off.  The scene has no call that changes materials or lights in place: they arrive
+// with atn_upload_scene only, which decides this again; a caller that writes the triangle array itself (atn_scene_device_arrays) can
+// only point a triangle at another checked material or at the fallback.
+inline bool rr_lookahead_valid(const std::vector<DevMaterial>& materials)
+{
+    for (const DevMaterial& dm : materials) {
+        if (dm.attrib & (ATN_MTRL_ATTR_SINGULAR | ATN_MTRL_ATTR_TRANSLUCENT | ATN_MTRL_ATTR_EMISSIVE)) return false;
+        switch (dm.type) {
+        case ATN_MTRL_DIFFUSE: case ATN_MTRL_OREN_NAYAR: case ATN_MTRL_GGX: case ATN_MTRL_BECKMAN: case ATN_MTRL_VELVET:
+        case ATN_MTRL_RETROREFLECTIVE: case ATN_MTRL_DISNEY:
+        case ATN_MTRL_SPECULAR: case ATN_MTRL_REFRACTION: case ATN_MTRL_MICROFACET_REFRACTION:      // (only without the attributes above)
+            break;
+        default:        // Emissive, CarPaint, Toon, StylizedBrdf, media, anything unknown
+            return false;
+        }
+    }
+    return true;
+}
+
 inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::string& err, int anyhit_twins = 0, int twin_dirs = 8,
                              int node_layout_top_levels = kLayoutTopLevels, bool planar_lights = true, uint64_t twin_budget_bytes = kTwinBudgetBytes)
 {
@@ -604,6 +630,7 @@ inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::
         img.screen_shadow.resize(n);
         for (size_t i = 0; i < n; i++) img.screen_shadow[i] = s->screen_space_texture.texels[i].x;
     }
+    p.rr_lookahead = rr_lookahead_valid(img.materials) ? 1 : 0;
     p.material_set = kMsCore;
     for (const DevMaterial& dm : img.materials) {
         const int32_t t = dm.type;

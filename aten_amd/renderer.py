@@ -210,6 +210,21 @@ class PathTracing:
         """False (default): the parity path; True: the shade kernel under the reference GPU build's --use_fast_math rules (opt-in)."""
         self._check(self._l.atn_set_shade_math(self._ctx, int(relaxed)))
 
+    def set_rr_lookahead(self, mode):
+        """The roulette look-ahead of render() (include/aten_amd.h): 0 off, 1 on where the scene qualifies (default; counted frames
+        keep the reference's accounting), 2 counted frames too (rr_lookahead_stats).  Films are byte-equal in every mode."""
+        self._check(self._l.atn_set_rr_lookahead(self._ctx, int(mode)))
+
+    def rr_lookahead_active(self):
+        """Whether frames of the current scene run the look-ahead (no emissive, singular, translucent, CarPaint or toon material)."""
+        return bool(self._l.atn_rr_lookahead_active(self._ctx))
+
+    def rr_lookahead_stats(self):
+        """Of the last counted frame in mode 2: the rays traced as any-hit rays, their hits (ended unshaded), their visits."""
+        s = np.zeros(4, np.uint64)
+        self._check(self._l.atn_rr_lookahead_stats(self._ctx, s.ctypes.data))
+        return dict(doomed_rays=int(s[0]), doomed_hits=int(s[1]), doomed_nodes=int(s[2]), doomed_tris=int(s[3]))
+
     def set_regeneration(self, on):
         """Path regeneration (include/aten_amd.h): the samples of a frame / the frames of a burst share one pool of path slots.
         Off by default.  Measured guidance: switch it on for render_burst of >= 2 multi-sample frames in the

@@ -200,6 +200,20 @@ int atn_regen_stage_counts(atn_ctx* ctx, uint32_t* closest, uint32_t* shadow, ui
  * CPU renderer's beyond the parity tolerance (measured: DESIGN.md section 7f); serial loop only (not the regenerated pool, not SVGF). */
 int atn_set_shade_math(atn_ctx* ctx, int32_t mode);
 
+/* The roulette look-ahead of atn_render's serial sample loop.  Where Russian roulette applies (bounce > russianRouletteDepth), whether a
+ * path survives its NEXT vertex is known one bounce earlier: the probability is max3 of the throughput it arrives with and the draw a
+ * pure function of the stored sampler position.  A path that will lose is traced as an any-hit ray -- a miss adds the environment as
+ * ever, a hit only ends it -- and its hit is not shaded.  Films are byte-equal with and without.
+ * Valid only on scenes in which no material draws in front of the roulette, skips NEE's draws or emits (no Emissive, singular,
+ * translucent, CarPaint, Toon / StylizedBrdf material): decided at atn_upload_scene; atn_rr_lookahead_active tells (1 / 0) whether
+ * frames of the current scene run it.  mode 0 = off; 1 (default; ATEN_AMD_RR_LOOKAHEAD at atn_create) = on, frames with count_stats = 1
+ * keep the reference's accounting (off); 2 = counted frames too: atn_get_stats then counts the rays walked to their closest hit and
+ * the hits that are shaded, and atn_rr_lookahead_stats the rest: {doomed rays, doomed hits (not shaded), node visits and triangle
+ * tests of the doomed rays}.  Not applied by the regenerated pool, SVGF, ReSTIR, NPR, AO, volume frames or atn_set_shade_math(1). */
+int atn_set_rr_lookahead(atn_ctx* ctx, int32_t mode);
+int32_t atn_rr_lookahead_active(atn_ctx* ctx);
+int atn_rr_lookahead_stats(atn_ctx* ctx, uint64_t out[4]);
+
 /* ≙ idaten::Renderer::reset (renderer.h:40-43): clears the progressive film. */
 int atn_reset(atn_ctx* ctx);
 

@@ -41,6 +41,7 @@ SYMBOLS = [
     "atn_set_regeneration", "atn_get_regeneration", "atn_render_burst", "atn_regen_stage_counts",
     "atn_mgpu_set_regeneration", "atn_mgpu_render_burst", "atn_set_upload_options", "atn_libm_probe", "atn_set_shade_math",
     "atn_set_rr_lookahead", "atn_rr_lookahead_active", "atn_rr_lookahead_stats",
+    "atn_set_nee_deferral", "atn_nee_deferral_active", "atn_nee_deferral_stats",
 ]
 
 
@@ -97,6 +98,9 @@ def lib():
         l.atn_set_rr_lookahead.argtypes = [vp, C.c_int32]
         l.atn_rr_lookahead_active.argtypes = [vp]; l.atn_rr_lookahead_active.restype = C.c_int32
         l.atn_rr_lookahead_stats.argtypes = [vp, vp]
+        l.atn_set_nee_deferral.argtypes = [vp, C.c_int32]
+        l.atn_nee_deferral_active.argtypes = [vp]; l.atn_nee_deferral_active.restype = C.c_int32
+        l.atn_nee_deferral_stats.argtypes = [vp, vp]
         l.atn_get_regeneration.argtypes = [vp]; l.atn_get_regeneration.restype = C.c_int32
         l.atn_render_burst.argtypes = [vp, C.POINTER(Destination), C.c_int32, vp]
         l.atn_regen_stage_counts.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]

@@ -122,6 +122,8 @@ public:
     bool rr_lookahead_twin = true;      // ATEN_AMD_RR_LOOKAHEAD_TWIN=0 (experiments): doomed rays stop at their first hit on the list as given
     int rr_lookahead = 1;       // ATEN_AMD_RR_LOOKAHEAD / atn_set_rr_lookahead: 0 = off, 1 = render()'s serial passes on scenes that qualify
                                 // (counted frames keep the reference's accounting: off), 2 = counted frames too (atn_rr_lookahead_stats)
+    int nee_deferral = 0;       // ATEN_AMD_NEE_DEFERRAL / atn_set_nee_deferral: 0 = off (the initial mode: docs/NEE_DEFERRAL.md has the measurement), 1 = every
+                                // scene that qualifies, 2 = the policy: scenes that qualify and have infinite lights only (scene_upload.hpp, nee_deferral_class)
     int env_flavour = -1;       // ATEN_AMD_TRACE: 1 = the refill walk, 0 = the plain walk for every launch (default: refill_walk)
 
     // scene (HBM-resident after UpdateSceneData)
@@ -233,6 +235,10 @@ public:
 
     // path state
     DevBuf<float4> ray_o, ray_d, thr, contrib, isect, sh_o, sh_d, sh_c, accum, film, tile_out;
+    DevBuf<float4> sh_w;                    // deferred NEE: {incoming direction, sampler dimension} of the vertex behind a slot's shadow ray
+    DevBuf<uint32_t> nee_reached;           // deferred NEE: per slot, the shadow ray reached its light (isect then holds two planes of hit records); these
+                                            // and isect's second plane exist only in a bank that has run a deferred frame (run_paths)
+    DevBuf<unsigned long long> nee_stats;   // deferred NEE: {shadow rays cast, rays that reached the light} of the deferred frames since the last reset
     DevBuf<float4> pend;                    // path regeneration: a pixel's previous sample while its last shadow ray is in flight
     DevBuf<float4> rg_frames;               // path regeneration: [frames of the burst][slots] pixel values on their way to the film (k_regen_end)
     DevBuf<uint32_t> done, queue0, queue1, shadow_q, counters;
@@ -254,8 +260,8 @@ public:
     // Only the film orders consecutive frames: a frame's k_gather waits for the previous frame's.
     static constexpr int kMaxInFlight = 4;      // (5 / 6 / 8 banks with 8 hardware queues: no gain, profiles/r04_variants_shade_waves.txt)
     struct Bank {
-        DevBuf<float4> ray_o, ray_d, thr, contrib, isect, sh_o, sh_d, sh_c, accum, tile_out, pend, rg_frames;
-        DevBuf<uint32_t> done, queue0, queue1, shadow_q, counters, rg_counters, rg_regions;
+        DevBuf<float4> ray_o, ray_d, thr, contrib, isect, sh_o, sh_d, sh_c, sh_w, accum, tile_out, pend, rg_frames;
+        DevBuf<uint32_t> done, queue0, queue1, shadow_q, nee_reached, counters, rg_counters, rg_regions;
         int32_t rg_stages = 0;
         uint32_t n_slots = 0;
         int32_t counters_depth = 0;
@@ -279,7 +285,7 @@ public:
     void swap_bank(Bank& b)
     {
         ray_o.swap(b.ray_o); ray_d.swap(b.ray_d); thr.swap(b.thr); contrib.swap(b.contrib); isect.swap(b.isect);
-        sh_o.swap(b.sh_o); sh_d.swap(b.sh_d); sh_c.swap(b.sh_c); accum.swap(b.accum); tile_out.swap(b.tile_out);
+        sh_o.swap(b.sh_o); sh_d.swap(b.sh_d); sh_c.swap(b.sh_c); sh_w.swap(b.sh_w); nee_reached.swap(b.nee_reached); accum.swap(b.accum); tile_out.swap(b.tile_out);
         done.swap(b.done); queue0.swap(b.queue0); queue1.swap(b.queue1); shadow_q.swap(b.shadow_q);
         counters.swap(b.counters); pend.swap(b.pend); rg_frames.swap(b.rg_frames); rg_counters.swap(b.rg_counters); rg_regions.swap(b.rg_regions); std::swap(rg_stages, b.rg_stages);
         std::swap(n_slots, b.n_slots); std::swap(counters_depth, b.counters_depth); std::swap(bank_epoch, b.bank_epoch); std::swap(bank_scene_set, b.scene_set);
@@ -791,6 +797,7 @@ public:
         if (const char* e = std::getenv("ATEN_AMD_SHADE_WAVES")) { const int v = std::atoi(e); if (v == 4 || v == 5) env_shade_waves = v; }   // else: plan_pass
         if (const char* e = std::getenv("ATEN_AMD_LDS_NODES")) env_lds_nodes = std::atoi(e) != 0;
         if (const char* e = std::getenv("ATEN_AMD_RR_LOOKAHEAD")) rr_lookahead = std::max(0, std::min(2, std::atoi(e)));
+        if (const char* e = std::getenv("ATEN_AMD_NEE_DEFERRAL")) nee_deferral = std::max(0, std::min(2, std::atoi(e)));
         if (const char* e = std::getenv("ATEN_AMD_RR_LOOKAHEAD_TWIN")) rr_lookahead_twin = std::atoi(e) != 0;
         if (const char* e = std::getenv("ATEN_AMD_ANYHIT_TWIN")) env_anyhit_twin = std::max(0, std::min(2, std::atoi(e)));
         if (const char* e = std::getenv("ATEN_AMD_ANYHIT_TWIN_DIRS")) env_anyhit_twin_dirs = std::atoi(e) == 1 ? 1 : 8;
@@ -1483,6 +1490,11 @@ public:
             ATN_HIP(stats.resize(16));
             ATN_HIP(hipMemsetAsync(stats.p, 0, 128, stream));
         }
+        if (!nee_stats.p) {
+            ATN_HIP(nee_stats.resize(2));
+            ATN_HIP(hipMemsetAsync(nee_stats.p, 0, 16, stream));
+            ATN_HIP(hipStreamSynchronize(stream));      // (once per context: every bank's stream adds to it)
+        }
         return ATN_OK;
     }
 
@@ -1625,6 +1637,22 @@ public:
     {
         return rr_lookahead >= (count ? 2 : 1) && scene.rr_lookahead != 0 && !shade_math_relaxed && scene.material_set <= kMsAnalytic;
     }
+    // Does this frame of render() defer its NEE evaluation (kernels.hpp, PathBuffers::nee_reached)?  The scene has to qualify, and under
+    // the default policy (mode 2) every light has to be infinite (DevScene::nee_deferral); counted frames stay eager -- their shadow-ray
+    // counter is the reference's, which casts no ray for a sample whose BSDF pdf is 0 -- and the relaxed-math kernel has no such flavour.
+    bool nee_deferral_frame(bool count) const
+    {
+        const int32_t need = nee_deferral == 1 ? 1 : 3;
+        return nee_deferral != 0 && !count && (scene.nee_deferral & need) == need && !shade_math_relaxed && scene.material_set <= kMsAnalytic;
+    }
+    // k_nee_eval for bounce b of a deferred frame: behind the trace launch that carried b's shadow rays
+    void launch_nee_eval(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, int32_t b)
+    {
+        with_shade_flavour(scene.material_set, 4, [&](auto k) {
+            using K = decltype(k);
+            if constexpr (K::waves != 0) hipLaunchKernelGGL((k_nee_eval<K::ms>), dim3(grid), dim3(256), 0, st, pb, scene, fp, b, nee_stats.p);
+        });
+    }
 
     template <bool SVGF>
     void launch_shade(const PassPlan& p, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, int32_t b, const SvgfShade& sv)
@@ -1637,11 +1665,16 @@ public:
         // kernel as it is without -- and so is every launch of a material set that has no such flavour (none of those qualifies:
         // rr_lookahead_frame; unmarked, no path is ever doomed)
         const bool la = !SVGF && pb.doomed_bit != 0u && b >= fp.rr_depth;
+        // the deferred-NEE flavour for every launch of a deferred frame (nee_deferral_frame: run_paths hands such a frame the flag plane)
+        const bool dn = !SVGF && pb.nee_reached != nullptr;
         with_shade_flavour(scene.material_set, p.shade_waves, [&](auto k) {
             using K = decltype(k);
             if constexpr (!SVGF && K::waves != 0) {
-                if (la) {
-                    hipLaunchKernelGGL((k_shade_wn<false, K::ms, K::waves, true>), dim3(p.shade_grid), dim3(256), 0, st, pb, scene, fp, camera, b, sv);
+                if (la || dn) {
+                    with_flags([&](auto f_la, auto f_dn) {
+                        hipLaunchKernelGGL((k_shade_wn<false, K::ms, K::waves, decltype(f_la)::value, decltype(f_dn)::value>), dim3(p.shade_grid), dim3(256), 0, st,
+                                           pb, scene, fp, camera, b, sv);
+                    }, la, dn);
                     return;
                 }
             }
@@ -1709,6 +1742,13 @@ public:
         if (nb > batch_streams_checked && nb > 1 && env_probe_streams) { int rc = separate_batch_streams(nb); if (rc) return rc; }
         uint32_t per = (n_slots + (uint32_t)nb - 1u) / (uint32_t)nb;
         per = (per + kChunk - 1u) / kChunk * kChunk;        // whole 1024-slot chunks (16 screen tiles)
+        // A deferred-NEE frame's extra state -- the second plane of hit records, sh_w, the flag words: 36 B per slot -- is allocated
+        // when a bank first runs such a frame (DevBuf::resize frees behind the device's work and never shrinks); a context that
+        // stays in mode 0, and every other renderer, never pays for it.
+        const bool deferred = !SVGF && nee_deferral_frame(count);
+        if (deferred) {
+            ATN_HIP(isect.resize((size_t)2 * n_slots)); ATN_HIP(sh_w.resize(n_slots)); ATN_HIP(nee_reached.resize(n_slots));
+        }
         ATN_HIP(hipMemsetAsync(counters.p, 0, (size_t)nb * 4 * counters_depth * 4, stream));
         ATN_HIP(hipEventRecord(ev_fork, stream));
         for (int k = 0; k < nb; k++) {
@@ -1720,11 +1760,15 @@ public:
             PathBuffers pb = buffers(count, k, begin);
             pb.doomed_bit = (!SVGF && rr_lookahead_frame(count)) ? F_DOOMED : 0u;
             pb.doomed_stop = rr_lookahead_twin ? kInf : 1.0e30F;        // (kInf is the largest finite float: any smaller bound beyond every scene's distances stops the walk and is not the twins' key)
+            if (deferred) { pb.isect_odd = n_slots; pb.nee_reached = nee_reached.p; pb.sh_w = sh_w.p; }
             fp.slot_begin = (int32_t)begin; fp.slot_end = (int32_t)end;
             const uint32_t n = end - begin;
             const PassPlan plan = plan_pass(SVGF ? PassKind::Svgf : PassKind::Serial, n);
             fp.chunk_items = plan.shade_items;
             const uint32_t g_slots = grid_for(n), g_all = (n + 255u) / 256u;
+            // k_nee_eval: a block per four 1024-entry chunks of a full shadow queue (never 0) -- enough flagged entries per block for
+            // full replay waves where a few per cent of the rays reach the light, enough blocks to cover the chip on a 1080p frame
+            const uint32_t g_nee = grid_for((n + 4u * kChunk - 1u) / (4u * kChunk) * 256u);
             for (int32_t s = 0; s < d->sample; s++) {
                 fp.sample = s;
                 if (s > 0) ATN_HIP(hipMemsetAsync(pb.q_count, 0, (size_t)4 * counters_depth * 4, st));
@@ -1743,6 +1787,11 @@ public:
                         prof_begin(prof, ATN_K_TRACE_SHADOW, st);
                         launch_trace<true>(plan, pb, count, b, st);
                         prof_end(prof);
+                        if (deferred) {
+                            prof_begin(prof, ATN_K_TRACE_SHADOW, st);       // (with the shadow launch whose rays it evaluates, as in the fused loop)
+                            launch_nee_eval(g_nee, st, pb, fp, b);
+                            prof_end(prof);
+                        }
                     }
                 }
                 else {
@@ -1753,6 +1802,13 @@ public:
                         launch_trace_fused<false>(tl, st, pb, scene, b - 1, b < d->maxDepth ? b : -1, b);
                         prof_end(prof);
                         if (SVGF && b == 0 && gm_capture) motion_launch_capture(g_all, st, pb, fp, gm_capture);
+                        // deferred NEE: the launch above carried the shadow rays of bounce b - 1; their evaluation goes in front of
+                        // whatever vertex b adds to `contrib` (and, behind the last launch, in front of the sample's epilogue)
+                        if (deferred && b > 0) {
+                            prof_begin(prof, ATN_K_TRACE_SHADOW, st);       // (HitShadowRay's addition: timed apart from the shade launches)
+                            launch_nee_eval(g_nee, st, pb, fp, b - 1);
+                            prof_end(prof);
+                        }
                         if (b < d->maxDepth) {
                             prof_begin(prof, ATN_K_SHADE, st);
                             launch_shade<SVGF>(plan, st, pb, fp, b, sv);
@@ -3265,8 +3321,27 @@ public:
     }
 
     // ≙ idaten::Renderer::reset, renderer.h:40-43
+    // {shadow rays cast, rays that reached the light} of the deferred frames since the last reset
+    int nee_deferral_stats(uint64_t out[2])
+    {
+        out[0] = out[1] = 0;
+        if (!nee_stats.p) return ATN_OK;
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        unsigned long long h[2] = {};
+        ATN_HIP(hipMemcpyAsync(h, nee_stats.p, 16, hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        out[0] = h[0]; out[1] = h[1];
+        return ATN_OK;
+    }
+
     int reset()
     {
+        if (nee_stats.p) {
+            ATN_HIP(hipSetDevice(device));
+            { int q = quiesce(); if (q) return q; }
+            ATN_HIP(hipMemsetAsync(nee_stats.p, 0, 16, stream));
+        }
         if (film.p) {
             ATN_HIP(hipSetDevice(device));
             { int q = quiesce(); if (q) return q; }
@@ -3490,6 +3565,23 @@ int atn_rr_lookahead_stats(atn_ctx* ctx, uint64_t out[4])
     if (!out) return ctx->r.fail(ATN_ERR_INVALID_ARG, "null output");
     for (int i = 0; i < 4; i++) out[i] = ctx->r.host_stats[8 + i];
     return ATN_OK;
+}
+int atn_set_nee_deferral(atn_ctx* ctx, int32_t mode)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    if (mode < 0 || mode > 2) return ctx->r.fail(ATN_ERR_INVALID_ARG, "NEE deferral mode out of range");
+    ctx->r.nee_deferral = mode;
+    return ATN_OK;
+}
+int32_t atn_nee_deferral_active(atn_ctx* ctx)
+{
+    return (ctx && ctx->r.has_scene && ctx->r.nee_deferral_frame(false)) ? 1 : 0;
+}
+int atn_nee_deferral_stats(atn_ctx* ctx, uint64_t out[2])
+{
+    CTX_OR_FAIL(ctx);
+    if (!out) return ctx->r.fail(ATN_ERR_INVALID_ARG, "null output");
+    return guarded(ctx, [&] { return ctx->r.nee_deferral_stats(out); });
 }
 int atn_set_shade_math(atn_ctx* ctx, int32_t mode)
 {

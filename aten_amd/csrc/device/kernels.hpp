@@ -32,6 +32,7 @@ namespace atn {
 
 constexpr uint32_t F_TERMINATED = 1u, F_SINGULAR = 2u, F_HIT = 4u;
 constexpr uint32_t kShadowSlotMask = (1u << 26) - 1u;      // shadow-job payload: slot bits (ShadowJob)
+constexpr uint32_t kShadowLightMask = 0xffffffu;          // in sh_c.w / sh_d.w: the target light's index (the flags below sit above it)
 constexpr uint32_t kShadowStencilFlag = 0x40000000u;      // in sh_d.w next to the light index: the shaded surface's material is StencilType::ALWAYS
 constexpr uint32_t F_LAST_SPECULAR = 8u;     // SVGF shade only: paths.attrib.last_hit_mtrl_idx names a Specular material
 
@@ -75,6 +76,16 @@ constexpr uint32_t kRegenMaxSpp = 1u << 11, kRegenMaxItems = 1u << 28;
 // shaded.  The mark is a bit of ray_d.w above the regenerated pool's five flag bits; the pool and the other renderers never set it
 // and their closest-hit jobs never look for it (ClosestJobT::doomed_bit = 0).
 constexpr uint32_t F_DOOMED = 32u;
+// ---- the deferred NEE (render()'s serial passes on scenes that qualify: DevScene::nee_deferral, DESIGN.md section 5, docs/NEE_DEFERRAL.md) ----
+// HitShadowRay adds a vertex's light sample only when its shadow ray reaches the light, so everything of the sample but the ray is
+// needed for those vertices alone.  In a deferred frame shade (shade_body<..., DN>) casts the ray from the light sample's GEOMETRY
+// (sample_light<true>, nee_geometry) and stores what the evaluation cannot recompute: the throughput the vertex arrived with (sh_c.xyz,
+// in place of the light's contribution) and {incoming direction, sampler dimension} (sh_w).  The shadow job's finish() sets a flag
+// word instead of adding to `contrib`, and k_nee_eval(b) -- behind the trace launch that carried bounce b's shadow rays, in front of
+// shade(b + 1): the order of additions into `contrib` stays -- REPLAYS the vertex for the flagged slots from its hit record with the
+// functions shade runs (vertex_surface, vertex_albedo, vertex_frame, nee_evaluate) and adds the contribution.  The hit record of
+// bounce b has to outlive closest(b + 1), which shares a launch with shadow(b): the records alternate between two planes by bounce
+// parity (isect_odd).  All three fields are 0 / null in every other frame, pass and renderer: their code is the code as it was.
 constexpr uint32_t kShadowFinalFlag = 0x20000000u;        // in sh_c.w / sh_d.w: the shadow ray of a path's LAST vertex -- its light goes to `pend`, not `contrib`
 
 struct PathBuffers {
@@ -87,7 +98,8 @@ struct PathBuffers {
     float4* isect;      // instance object id (bit pattern; < 0 = miss), a, b, triangle id (bit pattern): what shade reads of the hit
     float4* sh_o;       // shadow org.xyz, distToLight
     float4* sh_d;       // shadow dir.xyz, target light id (bit pattern)
-    float4* sh_c;       // lightcontrib.xyz, -
+    float4* sh_c;       // lightcontrib.xyz, light bits (sh_d.w again).  In a DEFERRED-NEE frame (nee_reached != null) xyz is NOT a contribution
+                        // but the throughput the vertex arrived with: only k_nee_eval may read it there (ShadowJob::finish sets the flag and returns)
     float4* accum;      // sum of valid sample contribs.xyz, count
     uint32_t* done;     // pixel stopped sampling (pathtracing.cpp:350-352)
     uint32_t* queue[2]; // live path slots, ping-pong per bounce
@@ -113,6 +125,12 @@ struct PathBuffers {
     uint32_t doomed_bit;            // F_DOOMED in the serial passes of a frame that runs the roulette look-ahead, 0 everywhere else
     float doomed_stop;              // the stop_t a doomed ray is handed out with: kInf = first accepted hit, through the any-hit twins; 1e30
                                     // = first accepted hit on the list as given (ATEN_AMD_RR_LOOKAHEAD_TWIN=0, experiments)
+    uint32_t isect_odd;             // deferred-NEE frames: the hit records of odd bounces live this many entries behind those of even bounces
+                                    // (isect + (bounce & 1) * isect_odd); 0 everywhere else
+    uint32_t* nee_reached;          // deferred-NEE frames: per slot, "the shadow ray stored by the last shade reached its light" (cleared by
+                                    // shade, set by ShadowJob::finish, read by k_nee_eval); null everywhere else
+    float4* sh_w;                   // deferred-NEE frames: incoming direction.xyz of the vertex that cast the shadow ray, its sampler dimension in
+                                    // front of the light pick (bit pattern)
 };
 
 struct FrameParams {
@@ -470,6 +488,7 @@ struct ClosestJobT {
     float t_min;
     uint32_t doomed_bit;
     float doomed_stop;
+    uint32_t isect_off;     // (deferred-NEE frames: the plane of this bounce's hit records, PathBuffers::isect_odd; else 0)
     ATN_DEV void fetch(uint32_t j, float4& a, float4& b, float& stop_t) const { fetch_slot(q[j], a, b, stop_t); }
     ATN_DEV void fetch_slot(uint32_t slot, float4& a, float4& b, float& stop_t) const
     {
@@ -480,7 +499,7 @@ struct ClosestJobT {
     }
     ATN_DEV bool finish(uint32_t slot, const Hit& h, bool, float4&, float4&, float&) const
     {
-        pb.isect[slot] = make_float4(__int_as_float(h.objid), h.a, h.b, __int_as_float(h.tri));
+        pb.isect[slot + isect_off] = make_float4(__int_as_float(h.objid), h.a, h.b, __int_as_float(h.tri));
         return false;
     }
     ATN_DEV void cost(uint32_t slot, uint32_t nodes, uint32_t tris) const
@@ -498,7 +517,7 @@ template <bool COUNT, bool REFILL>
 __global__ void __launch_bounds__(kTraceBlock > 256 ? kTraceBlock : 256) k_trace_closest(PathBuffers pb, DevScene sc, int32_t bounce)
 {
     const uint32_t count = pb.q_count[bounce];
-    const ClosestJobT<COUNT> job{ pb, pb.queue[bounce & 1], kEps, pb.doomed_bit, pb.doomed_stop };
+    const ClosestJobT<COUNT> job{ pb, pb.queue[bounce & 1], kEps, pb.doomed_bit, pb.doomed_stop, (uint32_t)(bounce & 1) * pb.isect_odd };
     TravCounters tc{};
     trace_dispatch<COUNT, REFILL>(sc, count, &pb.fetch_closest[bounce], job, &tc);
     if (COUNT) {
@@ -545,6 +564,75 @@ using ShadePartShared = ShadePartSharedT<2>;
 // wave's 64 entries are 64 slots from all over the chunk's neighbourhood -- every state read one cache line per lane.
 template <bool ON> struct ShadeOrderShared { uint16_t inv[ON ? kChunk : 1]; uint8_t oflag[ON ? kChunk : 1]; };
 
+// ---- the front half of a vertex and its NEE evaluation: what shade_body runs at a hit and k_nee_eval replays (deferred NEE) ----------
+// One routine each, called from both places: the replay computes a vertex's values with the functions that computed them in shade.
+// GeneratePath's sampler of a path (pathtracing_impl.h:75-81) from the pixel's seed: s4.w = the pixel, s4.x = the CMJ index, s4.z = the
+// scramble (s4.y, the dimension, is the caller's); fs = frame + sample.
+ATN_DEV void path_sampler(uint4& s4, const PathBuffers& pb, const FrameParams& fp, uint32_t pixel_slot, uint32_t fs)
+{
+    int32_t px = 0, py = 0;
+    slot_to_pixel(fp, pixel_slot, px, py);
+    s4.w = (uint32_t)(py * fp.width + px);
+    const uint32_t rnd = pb.seeds[s4.w < fp.n_seeds ? s4.w : s4.w % here(fp.n_seeds)];    // (one seed per pixel is the rule)
+    s4.x = fs % 256u;
+    s4.z = rnd * 0x1fe3434fu * ((fs + 133u * rnd) / 256u);
+}
+// the hit record -> the surface point, its material id and which side the ray arrived on
+ATN_DEV void vertex_surface(HitRec& rec, int32_t& mtrlid, bool& isBackfacing, const DevScene& sc, const float4& is4, const f3& ray_dir)
+{
+    const int32_t tri_id = __float_as_int(is4.w);
+    evaluate_hit(rec, sc, __float_as_int(is4.x), tri_id, is4.y, is4.z);
+    mtrlid = triangle_mtrlid(sc, tri_id);
+    isBackfacing = dot(rec.normal, -ray_dir) < 0.0F;
+}
+// the albedo the path tracer's shade multiplies with (AT_NAME::sampleTexture + ApplyAlphaBlend's identity blend)
+ATN_DEV float4 vertex_albedo(const DevScene& sc, const DevMaterial& m, const HitRec& rec)
+{
+    float4 albedo4 = sample_texture(sc, m.albedoMap, rec.u, rec.v, m.baseColor);
+    albedo4 = add4(mul4(1.0F, albedo4), make_float4(0, 0, 0, 0));
+    return albedo4;
+}
+// the shading frame: the back-face rule, material::applyNormal (the normal map -- or, for CarPaint, the flake normal and the random
+// number it shares: the return value) and what the BSDF sample, the NEE evaluation and the light sample share (shading.hpp, HitPre).
+// `orienting_normal` comes in as the hit's normal.
+template <int MS>
+ATN_DEV float vertex_frame(const DevScene& sc, const DevMaterial& m, int32_t mtrl_slot, const HitRec& rec, bool isBackfacing, const f3& ray_dir,
+                           Cmj& smp, f3& orienting_normal, HitPre& hp)
+{
+    if (!(m.attrib & ATN_MTRL_ATTR_TRANSLUCENT) && isBackfacing) orienting_normal = -orienting_normal;
+    const float pre_r = apply_normal<MS>(sc, m, mtrl_slot, orienting_normal, rec.u, rec.v, ray_dir, smp);
+    tangent_coordinate(orienting_normal, hp.t, hp.b);
+    hp.rough = ggx_roughness(sc, m, rec.u, rec.v);
+    hp.lambda_v = m.type == ATN_MTRL_GGX ? ggx_lambda(hp.rough, -ray_dir, orienting_normal) : 0.0F;
+    return pre_r;
+}
+// SampleLight + ComputeRadianceNEE for light `li` from the sampler position `at` (behind the light pick's dimension), and the
+// contribution HitShadowRay adds if the ray reaches the light: then(lightcontrib, ls) runs where the sample is valid.
+template <int MS, class Then>
+ATN_DEV bool nee_evaluate(const DevScene& sc, const DevMaterial& m, int32_t mtrl_slot, const HitRec& rec, const f3& orienting_normal, const HitPre& hp,
+                          float pre_r, const f3& ray_dir, const Cmj& at, int32_t li, const f3& thr_in, const f3& albedo, Then&& then)
+{
+    Cmj sl = at;
+    const float lightSelectPdf = sc.inv_n_lights;       // 1.0f / (float)n_lights, divided once at upload
+    LightSample ls;
+    sample_light(ls, sc.lights[li], sc, rec.p, orienting_normal, sl, &hp);
+    return radiance_nee_then<MS>(sc, ray_dir, orienting_normal, m, rec.u, rec.v, lightSelectPdf, ls, mtrl_slot, pre_r, nullptr,
+                                 [&](const f3& radiance) {
+        // the contribution first: `radiance` is dead before the caller works out the shadow ray's geometry
+        const f3 lightcontrib = (thr_in * radiance) * albedo;
+        then(lightcontrib, ls);
+    }, &hp);
+}
+// FillShadowRay's ray (pathtracing_impl.h:236-262) for a light sample, into the slot's shadow record; lbits goes next to the direction
+ATN_DEV void store_shadow_ray(const PathBuffers& pb, uint32_t slot, const HitRec& rec, const f3& orienting_normal, const LightSample& ls, float lbits)
+{
+    const f3 dirToLight = normalize(ls.dir);
+    const float distToLight = length(ls.pos - rec.p);
+    const f3 so = ray_offset(rec.p, orienting_normal);
+    pb.sh_o[slot] = make_float4(so.x, so.y, so.z, distToLight);
+    pb.sh_d[slot] = make_float4(dirToLight.x, dirToLight.y, dirToLight.z, lbits);
+}
+
 // REGEN: the path-regeneration flavour (k_regen_shade).  `bounce_arg` is then the STAGE of the pool -- it selects queues and counters --
 // and a path's own bounce, sample and frame come out of its state words; a path that ends runs its sample epilogue here and the
 // pixel's next primary ray takes its place in the next stage's queue.
@@ -552,11 +640,16 @@ template <bool ON> struct ShadeOrderShared { uint16_t inv[ON ? kChunk : 1]; uint
 // qualifies: it MARKS the paths it stores that will lose the next vertex's roulette (launches with bounce + 1 > rr_depth) and ENDS
 // the marked ones that hit (launches with bounce > rr_depth) without shading them.  Every other launch runs LA = false: the code as
 // it was.
-template <bool SVGF, int MS, bool REGEN = false, bool LA = false>
+// DN: the deferred-NEE flavour (PathBuffers::nee_reached, above), every shade launch of a deferred frame: at the NEE block it casts the
+// shadow ray from the light sample's geometry and leaves the evaluation to k_nee_eval; hit records are read from the bounce's plane.
+template <bool SVGF, int MS, bool REGEN = false, bool LA = false, bool DN = false>
 ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const atn_camera_param& cam, int32_t bounce_arg, const SvgfShade& sv,
                         const RegenOut& ro = RegenOut{})
 {
     static_assert(!LA || (!SVGF && !REGEN && ATN_SHADE_PARTITION), "the look-ahead is the serial path tracer's");
+    static_assert(!DN || (!SVGF && !REGEN && MS <= kMsAnalytic), "the deferred NEE is the serial path tracer's, without CarPaint and toon");
+    const float4* __restrict__ isect_b = pb.isect;
+    if constexpr (DN) isect_b += (size_t)((uint32_t)bounce_arg & 1u) * pb.isect_odd;
     __shared__ BlockAppendShared sh;
     const bool la_ends = LA && bounce_arg > fp.rr_depth;       // (wave-uniform) this launch's queue can hold doomed paths
 #if ATN_SHADE_PARTITION
@@ -591,7 +684,7 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
               uint32_t cls = 3u;
               if (j < count) {
                   const uint32_t s = q[j];
-                  cls = __float_as_int(pb.isect[s].x) >= 0 ? 0u : NC - 1u;
+                  cls = __float_as_int(isect_b[s].x) >= 0 ? 0u : NC - 1u;
                   if constexpr (LA) { if (la_ends && cls == 0u && (__float_as_uint(pb.ray_d[s].w) & F_DOOMED)) cls = 1u; }
               }
               cls_bits |= cls << (2 * k);
@@ -687,7 +780,7 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                 bounce = (int32_t)((flags >> kRegenBounceShift) & kRegenBounceMask);
                 flags &= kRegenFlagMask;
             }
-            const float4 is4 = pb.isect[slot];
+            const float4 is4 = isect_b[slot];
             const int32_t hit_objid = __float_as_int(is4.x);
             const float4 thr4 = pb.thr[slot];
             f3 throughput = mk3(thr4);
@@ -707,12 +800,7 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                     regen_item(pb, fp, rg_item, rg_frame, pixel_slot);
                     fs = fp.frame + rg_frame + rg_sample;
                 }
-                int32_t px = 0, py = 0;
-                slot_to_pixel(fp, pixel_slot, px, py);
-                s4.w = (uint32_t)(py * fp.width + px);
-                const uint32_t rnd = pb.seeds[s4.w < fp.n_seeds ? s4.w : s4.w % here(fp.n_seeds)];    // (one seed per pixel is the rule)
-                s4.x = fs % 256u;
-                s4.z = rnd * 0x1fe3434fu * ((fs + 133u * rnd) / 256u);
+                path_sampler(s4, pb, fp, pixel_slot, fs);
             }
             Cmj smp; smp.idx = s4.x; smp.dim = s4.y; smp.scramble = s4.z;
             if constexpr (REGEN) {
@@ -790,12 +878,10 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                 nhits++;
 #endif
                 // ---------------- shade
-                const int32_t tri_id = __float_as_int(is4.w);
                 HitRec rec;
-                evaluate_hit(rec, sc, hit_objid, tri_id, is4.y, is4.z);
-                const int32_t mtrlid = triangle_mtrlid(sc, tri_id);
-
-                const bool isBackfacing = dot(rec.normal, -ray_dir) < 0.0F;
+                int32_t mtrlid;
+                bool isBackfacing;
+                vertex_surface(rec, mtrlid, isBackfacing, sc, is4, ray_dir);
                 f3 orienting_normal = rec.normal;
 
                 // FillMaterial (material_impl.h:232-262): a negative id selects the white-diffuse fallback, which
@@ -829,8 +915,7 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                     albedo4 = sample_texture(sc, albedo_map, rec.u, rec.v, make_float4(1.0F, 1.0F, 1.0F, 1.0F));
                 }
                 else {
-                    albedo4 = sample_texture(sc, m.albedoMap, rec.u, rec.v, m.baseColor);
-                    albedo4 = add4(mul4(1.0F, albedo4), make_float4(0, 0, 0, 0));
+                    albedo4 = vertex_albedo(sc, m, rec);
                 }
                 const f3 albedo = mk3(albedo4);
 
@@ -869,10 +954,11 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                 }
 
                 if (!shaded_out) {
-                    if (!(m.attrib & ATN_MTRL_ATTR_TRANSLUCENT) && isBackfacing) orienting_normal = -orienting_normal;
-                    // material::applyNormal: the normal map -- or, for CarPaint, the flake normal and the random number it shares
+                    // the back-face rule, material::applyNormal and what the BSDF sample, the NEE evaluation and the light sample share at
+                    // this vertex (vertex_frame, above)
                     const int32_t mtrl_slot = mtrlid >= 0 ? mtrlid : sc.n_materials;
-                    const float pre_r = apply_normal<MS>(sc, m, mtrl_slot, orienting_normal, rec.u, rec.v, ray_dir, smp);
+                    HitPre hp;
+                    const float pre_r = vertex_frame<MS>(sc, m, mtrl_slot, rec, isBackfacing, ray_dir, smp, orienting_normal, hp);
 
                     // ---- FillShadowRay / SampleLight, pathtracing_impl.h:178-264
                     // The reference evaluates NEE HERE, before Russian roulette and the BSDF sample, and HitShadowRay later drops
@@ -886,11 +972,6 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                     const bool nee = sc.n_lights > 0 && !invalid_mtrl;
                     const uint32_t nee_dim = smp.dim;
                     const f3 thr_in = throughput;
-                    // what the BSDF sample, the NEE evaluation and the light sample share at this vertex (shading.hpp, HitPre)
-                    HitPre hp;
-                    tangent_coordinate(orienting_normal, hp.t, hp.b);
-                    hp.rough = ggx_roughness(sc, m, rec.u, rec.v);
-                    hp.lambda_v = m.type == ATN_MTRL_GGX ? ggx_lambda(hp.rough, -ray_dir, orienting_normal) : 0.0F;
                     int32_t nee_light = 0;      // the light NEE picked (kept: the draw that picked it is not repeated)
                     if (nee) {
                         // with ONE light the pick is 0 whatever the draw says ((int)(r * 1) with r < 1): the draw is skipped, its
@@ -901,6 +982,27 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                         }
                         else smp.dim++;
                         smp.dim += light_sample_draws(sc.lights[nee_light], sc);
+                    }
+                    // Deferred NEE: the shadow ray is cast HERE, from the light sample's geometry and the part of the validity test that needs
+                    // no BSDF, and its record stored at once -- the throughput the vertex arrived with and {incoming direction, sampler
+                    // dimension} are what k_nee_eval cannot recompute -- so nothing of it stays live across the BSDF block.  Whether the
+                    // path goes on (and the ray is queued) is known below; a record stored for a path that ends is never read.
+                    bool nee_cast = false;
+                    if constexpr (DN) {
+                        if (nee) {
+                            Cmj sl; sl.idx = smp.idx; sl.dim = nee_dim + 1u; sl.scramble = smp.scramble;
+                            const float lbits = __uint_as_float((uint32_t)nee_light | ((m.attrib & kAttrStencilAlways) ? kShadowStencilFlag : 0u));
+                            LightSample ls;
+                            sample_light<true>(ls, sc.lights[nee_light], sc, rec.p, orienting_normal, sl, &hp);
+                            NeeGeom ng;
+                            if (nee_geometry(ng, orienting_normal, ls)) {
+                                pb.sh_c[slot] = make_float4(thr_in.x, thr_in.y, thr_in.z, lbits);
+                                pb.sh_w[slot] = make_float4(ray_dir.x, ray_dir.y, ray_dir.z, __uint_as_float(nee_dim));
+                                pb.nee_reached[slot] = 0u;
+                                store_shadow_ray(pb, slot, rec, orienting_normal, ls, lbits);
+                                nee_cast = true;
+                            }
+                        }
                     }
 
                     // ---- ComputeRussianProbability, pathtracing_impl.h:680-698
@@ -996,23 +1098,18 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                     if (nee && !(flags & F_TERMINATED)) {
                         Cmj sl; sl.idx = smp.idx; sl.dim = nee_dim + 1u; sl.scramble = smp.scramble;     // (behind the light pick's dimension)
                         const int32_t li = nee_light;
-                        const float lightSelectPdf = sc.inv_n_lights;       // 1.0f / (float)n_lights, divided once at upload
-                        LightSample ls;
-                        sample_light(ls, sc.lights[li], sc, rec.p, orienting_normal, sl, &hp);
-                        push_shadow = radiance_nee_then<MS>(sc, ray_dir, orienting_normal, m, rec.u, rec.v, lightSelectPdf, ls, mtrl_slot, pre_r, nullptr,
-                                                            [&](const f3& radiance) {
-                            // (next to the light index: HitShadowRay's surface_mtrl.stencil_type == ALWAYS, pathtracing.cpp:59-66)
-                            const float lbits = __uint_as_float((uint32_t)li | ((m.attrib & kAttrStencilAlways) ? kShadowStencilFlag : 0u)
-                                                                | (nee_final ? kShadowFinalFlag : 0u));
-                            // the contribution first: `radiance` is dead before the shadow ray's geometry is worked out
-                            const f3 lightcontrib = (thr_in * radiance) * albedo;
+                        // (next to the light index: HitShadowRay's surface_mtrl.stencil_type == ALWAYS, pathtracing.cpp:59-66)
+                        const float lbits = __uint_as_float((uint32_t)li | ((m.attrib & kAttrStencilAlways) ? kShadowStencilFlag : 0u)
+                                                            | (nee_final ? kShadowFinalFlag : 0u));
+                        if constexpr (DN) push_shadow = nee_cast;      // (deferred: cast above, evaluated by k_nee_eval)
+                        else
+                        {
+                        push_shadow = nee_evaluate<MS>(sc, m, mtrl_slot, rec, orienting_normal, hp, pre_r, ray_dir, sl, li, thr_in, albedo,
+                                                       [&](const f3& lightcontrib, const LightSample& ls) {
                             pb.sh_c[slot] = make_float4(lightcontrib.x, lightcontrib.y, lightcontrib.z, lbits);     // (the light bits again: all finish() needs)
-                            const f3 dirToLight = normalize(ls.dir);
-                            const float distToLight = length(ls.pos - rec.p);
-                            const f3 so = ray_offset(rec.p, orienting_normal);
-                            pb.sh_o[slot] = make_float4(so.x, so.y, so.z, distToLight);
-                            pb.sh_d[slot] = make_float4(dirToLight.x, dirToLight.y, dirToLight.z, lbits);
-                        }, &hp);
+                            store_shadow_ray(pb, slot, rec, orienting_normal, ls, lbits);
+                        });
+                        }
                     }
                 }
             }
@@ -1123,10 +1220,104 @@ __global__ void ATN_SHADE_ATTR __launch_bounds__(256) k_shade(PathBuffers pb, De
 // the Cornell box, -0.2 % on sponza_lod; latency +1-3 % (profiles/r04_variants_shade_waves.txt).  So the host launches WAVES = 5
 // when frames overlap and 4 when a caller waits for every frame.  6 waves (80 registers, 36-47 spilled) lose everywhere.
 // The larger sets (139 .. 205 VGPRs) would spill too much: they keep the compiler's own allocation (k_shade).
-template <bool SVGF, int MS, int WAVES, bool LA = false>
+template <bool SVGF, int MS, int WAVES, bool LA = false, bool DN = false>
 __global__ void __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) __launch_bounds__(256) k_shade_wn(PathBuffers pb, DevScene sc, FrameParams fp, atn_camera_param cam, int32_t bounce, SvgfShade sv)
 {
-    shade_body<SVGF, MS, false, LA>(pb, sc, fp, cam, bounce, sv);
+    shade_body<SVGF, MS, false, LA, DN>(pb, sc, fp, cam, bounce, sv);
+}
+
+// The deferred NEE's evaluation of one slot (k_nee_eval): the vertex REPLAYED from its primary inputs -- the hit record of the bounce's
+// plane, the stored incoming direction, throughput, light and sampler dimension, the pixel's seed.  Its values come out of the functions
+// shade_body computed them with, compiled in this unit under its flags; the contribution is added to `contrib` as ShadowJob::finish
+// adds it.
+template <int MS>
+ATN_DEV void nee_replay(const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const float4* __restrict__ isect_b, uint32_t slot)
+{
+    const float4 w4 = pb.sh_w[slot], c4 = pb.sh_c[slot], is4 = isect_b[slot];
+    const f3 ray_dir = mk3(w4), thr_in = mk3(c4);
+    const uint32_t nee_dim = __float_as_uint(w4.w);
+    const int32_t li = (int32_t)(__float_as_uint(c4.w) & kShadowLightMask);
+    uint4 s4;
+    path_sampler(s4, pb, fp, slot, fp.frame + (uint32_t)fp.sample);
+    HitRec rec;
+    int32_t mtrlid;
+    bool isBackfacing;
+    vertex_surface(rec, mtrlid, isBackfacing, sc, is4, ray_dir);
+    const int32_t mtrl_slot = mtrlid >= 0 ? mtrlid : sc.n_materials;
+    const DevMaterial& m = sc.materials[mtrl_slot];
+    const f3 albedo = mk3(vertex_albedo(sc, m, rec));
+    f3 orienting_normal = rec.normal;
+    HitPre hp;
+    Cmj smp; smp.idx = s4.x; smp.dim = nee_dim; smp.scramble = s4.z;        // (no material of a qualifying scene draws in applyNormal)
+    const float pre_r = vertex_frame<MS>(sc, m, mtrl_slot, rec, isBackfacing, ray_dir, smp, orienting_normal, hp);
+    Cmj sl; sl.idx = s4.x; sl.dim = nee_dim + 1u; sl.scramble = s4.z;       // (behind the light pick's dimension)
+    nee_evaluate<MS>(sc, m, mtrl_slot, rec, orienting_normal, hp, pre_r, ray_dir, sl, li, thr_in, albedo,
+                     [&](const f3& lc, const LightSample&) {
+        const float4 c = pb.contrib[slot];
+        pb.contrib[slot] = make_float4(c.x + lc.x, c.y + lc.y, c.z + lc.z, 0.0F);
+    });
+}
+
+// The deferred NEE's evaluation pass for bounce `bounce` (PathBuffers::nee_reached, above), over the bounce's shadow queue -- the count
+// is read here, the grid is the host's and grid-strides.  A block gathers the entries of its 1024-entry chunks whose ray reached the
+// light into one LDS list (ballot + popcount prefix, as the queue appends do) and replays them with all its lanes, when the list could
+// not take another chunk and at the end: where a few per cent of the rays reach the light -- the case deferral is for -- a chunk alone
+// would leave a block one sparse wave to replay.  stats (may be null): [0] shadow rays cast, [1] rays that reached the light.
+constexpr uint32_t kNeeList = 2u * kChunk;
+template <int MS>
+__global__ void __launch_bounds__(256) k_nee_eval(PathBuffers pb, DevScene sc, FrameParams fp, int32_t bounce, unsigned long long* stats)
+{
+    __shared__ uint32_t list[kNeeList];
+    __shared__ uint32_t wtot[kChunkItems][4];
+    const uint32_t count = pb.sh_count[bounce];
+    const float4* __restrict__ isect_b = pb.isect + (size_t)((uint32_t)bounce & 1u) * pb.isect_odd;
+    const uint32_t tid = here_v(threadIdx.x);
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    uint32_t n_cast = 0, n_reached = 0, n_list = 0;        // (the same in every thread of the block)
+    for (uint32_t chunk = blockIdx.x * kChunk; chunk < count; chunk += gridDim.x * kChunk) {
+        uint32_t mine[kChunkItems], below[kChunkItems];
+        uint32_t set_bits = 0;
+#pragma unroll
+        for (int k = 0; k < kChunkItems; k++) {
+            const uint32_t j = chunk + (uint32_t)k * 256u + threadIdx.x;
+            bool set = false;
+            mine[k] = 0u;
+            if (j < count) {
+                mine[k] = pb.shadow_q[j];
+                set = pb.nee_reached[mine[k]] != 0u;
+            }
+            const unsigned long long m = __ballot(set);
+            below[k] = bits_below_lane(m);
+            if (set) set_bits |= 1u << k;
+            if (lane == 0) wtot[k][wave] = (uint32_t)__popcll(m);
+        }
+        __syncthreads();
+        uint32_t n_set = 0;
+#pragma unroll
+        for (int k = 0; k < kChunkItems; k++) {
+            uint32_t before = n_set;
+            for (uint32_t w = 0; w < 4; w++) {
+                const uint32_t n = wtot[k][w];
+                if (w < wave) before += n;
+                n_set += n;
+            }
+            if ((set_bits >> k) & 1u) list[n_list + before + below[k]] = mine[k];       // (n_list <= kChunk here, before + below < n_set <= kChunk)
+        }
+        n_list += n_set;
+        n_cast += count - chunk < kChunk ? count - chunk : kChunk;
+        n_reached += n_set;
+        __syncthreads();        // the list is written, wtot has been read
+        if (n_list > kNeeList - kChunk) {       // no room for another chunk's entries: replay what is there
+            for (uint32_t e = threadIdx.x; e < n_list; e += 256u) nee_replay<MS>(pb, sc, fp, isect_b, list[e]);
+            n_list = 0;
+            __syncthreads();    // the list has been read
+        }
+    }
+    for (uint32_t e = threadIdx.x; e < n_list; e += 256u) nee_replay<MS>(pb, sc, fp, isect_b, list[e]);
+    if (stats && threadIdx.x == 0u && n_cast) {      // (one atomic per block and counter)
+        atomicAdd(&stats[0], (unsigned long long)n_cast);
+        atomicAdd(&stats[1], (unsigned long long)n_reached);
+    }
 }
 
 // HitShadowRay -> HitTestToTargetLight -> scene::hitLight
@@ -1160,7 +1351,7 @@ struct ShadowJob {
         // can be accepted first (triangle hits are accepted against isect.t = inf, threaded_bvh_traverser.h:236-262)
         // while the closest hit is a nearer blocker -- only an accepted hit with t <= distToLight settles it early.
         const uint32_t lbits = __float_as_uint(sd.w);
-        const atn_light_param* lp = &sc.lights[lbits & 0xffffffu];
+        const atn_light_param* lp = &sc.lights[lbits & kShadowLightMask];
         const bool has_obj = lp->type == ATN_LIGHT_AREA && lp->arealight_objid >= 0;
         // (a light with neither object nor attribute is visible iff nothing is hit, like an infinite one)
         const bool near_only = (lp->attrib & ATN_LIGHT_ATTR_SINGULAR) && !(lp->attrib & ATN_LIGHT_ATTR_INFINITE);
@@ -1169,7 +1360,7 @@ struct ShadowJob {
         // (scene_upload.hpp, planar_area_light, has the argument and the two conditions below).
         bool planar = false;
         if (has_obj && sc.planar_lights != 0) {
-            const float4 pl = sc.light_plane[lbits & 0xffffffu];
+            const float4 pl = sc.light_plane[lbits & kShadowLightMask];
             const float cos_l = fabsf(dot(mk3(pl), dir));
             // the origin is ray::Offset(p, n): at most 256 ulps (or 2^-16) per coordinate from p
             const float big = fmaxf(fmaxf(fabsf(so.x), fabsf(so.y)), fabsf(so.z));
@@ -1195,7 +1386,7 @@ struct ShadowJob {
         // the ray itself are read only by the branches that need them
         const float4 lc = pb.sh_c[slot];
         const uint32_t lbits = __float_as_uint(lc.w);
-        const atn_light_param* lp = &sc.lights[lbits & 0xffffffu];
+        const atn_light_param* lp = &sc.lights[lbits & kShadowLightMask];
         const int32_t ltype = lp->type, lobj = lp->arealight_objid;
         const uint32_t lattr = lp->attrib;
         const int32_t lightobj = (ltype == ATN_LIGHT_AREA && lobj >= 0) ? lobj : -1;
@@ -1246,6 +1437,10 @@ struct ShadowJob {
             }
         }
         if (visible) {
+            if constexpr (!REGEN) {
+                // a deferred-NEE frame: sh_c holds no contribution yet -- k_nee_eval evaluates and adds it for the slots flagged here
+                if (pb.nee_reached) { pb.nee_reached[slot] = 1u; return false; }
+            }
             float4* dst = pb.contrib;
             if constexpr (REGEN) { if (lbits & kShadowFinalFlag) dst = pb.pend; }
             const float4 c = dst[slot];
@@ -1311,7 +1506,8 @@ __global__ void ATN_TRACE_ATTR __launch_bounds__(kTraceBlock > 256 ? kTraceBlock
 {
     const uint32_t n_shadow = bs >= 0 ? pb.sh_count[bs] : 0u;
     const uint32_t n_closest = bc >= 0 ? pb.q_count[bc] : 0u;
-    const FusedJob<ALPHA, REGEN> job{ ShadowJob<ALPHA, REGEN>{ pb, sc, kEps }, ClosestJobT<!REGEN>{ pb, pb.queue[(bc >= 0 ? bc : 0) & 1], kEps, REGEN ? 0u : pb.doomed_bit, pb.doomed_stop }, n_shadow, kEps };
+    const FusedJob<ALPHA, REGEN> job{ ShadowJob<ALPHA, REGEN>{ pb, sc, kEps }, ClosestJobT<!REGEN>{ pb, pb.queue[(bc >= 0 ? bc : 0) & 1], kEps, REGEN ? 0u : pb.doomed_bit, pb.doomed_stop,
+                                                                                                   REGEN ? 0u : (uint32_t)((bc >= 0 ? bc : 0) & 1) * pb.isect_odd }, n_shadow, kEps };
     TravCounters tc{};
     trace_dispatch<false, REFILL, FusedJob<ALPHA, REGEN>, LDSN>(sc, n_shadow + n_closest, &pb.fetch_closest[launch], job, &tc);
 }

@@ -144,6 +144,8 @@ struct DevScene {
     int32_t ibl_importance;             // 1 = sample the IBL light from those tables (ImageBasedLight::sample, ibl.cpp:180-230)
     int32_t tex_bilinear;               // 1 = texture::AtWithBilinear (image/texture.cpp:77-125) instead of texture::at
     int32_t rr_lookahead;               // 1 = the roulette look-ahead is valid on this scene (host/scene_upload.hpp: rr_lookahead_valid; kernels.hpp, F_DOOMED)
+    int32_t nee_deferral;               // the deferred NEE (host/scene_upload.hpp: nee_deferral_class; kernels.hpp, PathBuffers::nee_reached): bit 0 = the
+                                        // scene qualifies, bit 1 = ... and every light is infinite (the default policy defers)
 };
 
 } // namespace atn

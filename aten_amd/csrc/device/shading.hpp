@@ -1309,6 +1309,10 @@ ATN_DEV float ibl_direction_pdf(const DevScene& sc, const f3& dir)
 }
 
 // Light::sample (light/light_impl.h:12-43) and the per-type samplers it dispatches to
+// GEOM: the geometry-only entry point of the deferred NEE (kernels.hpp, shade_body<..., DN>): position, direction, normal, distance,
+// pdf and attributes as ever -- the same code -- and no colour: the image-based light's direction_to_uv and environment texel stay out
+// (res.color is left at 0 and must not be read).
+template <bool GEOM = false>
 ATN_DEV void sample_light(LightSample& res, const atn_light_param& lp, const DevScene& sc, const f3& org, const f3& nml, Cmj& smp,
                           const HitPre* pre = nullptr)
 {
@@ -1399,22 +1403,26 @@ ATN_DEV void sample_light(LightSample& res, const atn_light_param& lp, const Dev
             const float v = (float)((double)y + 0.5) / (float)ih;
             res.pdf = ibl_texel_pdf(sc, pdf_u, pdf_v, y);
             res.dir = uv_to_direction(u, v);
-            const float4 lum = mul4(sc.multiplyer, sample_texture(sc, lp.envmapidx, u, v, make_float4(1, 1, 1, 1)));
-            res.color = mk3(mul4(lp.scale, lum));
+            if constexpr (!GEOM) {
+                const float4 lum = mul4(sc.multiplyer, sample_texture(sc, lp.envmapidx, u, v, make_float4(1, 1, 1, 1)));
+                res.color = mk3(mul4(lp.scale, lum));
+            }
             res.pos = org + sc.ibl_scene_radius * res.dir;      // (the reference leaves pos unset there: "currently not used")
             res.nml = -normalize(res.dir);
             res.dist = 1.0F;
             break;
         }
         res.dir = diffuse_dir(nml, r1, r2, pre);
-        float u, v;
-        direction_to_uv(res.dir, u, v);
         res.pos = org + sc.ibl_scene_radius * res.dir;
         res.nml = -normalize(res.dir);
         res.pdf = 1.0f / (2.0f * kPi);
         res.dist = 1.0F;
-        const float4 lum = sample_texture(sc, lp.envmapidx, u, v, make_float4(1, 1, 1, 1));
-        res.color = mk3(mul4(lp.scale, lum));
+        if constexpr (!GEOM) {
+            float u, v;
+            direction_to_uv(res.dir, u, v);
+            const float4 lum = sample_texture(sc, lp.envmapidx, u, v, make_float4(1, 1, 1, 1));
+            res.color = mk3(mul4(lp.scale, lum));
+        }
         break;
     }
     case ATN_LIGHT_POINT: {     // light/pointlight.h:40-58
@@ -1485,22 +1493,35 @@ ATN_DEV uint32_t light_sample_draws(const atn_light_param& lp, const DevScene& s
 
 // ComputeRadianceNEE, renderer/pathtracing/pathtracing_nee_impl.h:23-95.  `then(radiance)` runs where the reference returns a
 // value (k_shade stores the shadow job right there: the three floats never cross the join behind the validity test).
+// The part of ComputeRadianceNEE's validity test that needs no BSDF (pathtracing_nee_impl.h:60-71): the two cosines, the squared
+// distance as the test and the geometry term use it, the light's kind.  radiance_nee_then and the deferred NEE's shadow-ray cast
+// (kernels.hpp, shade_body<..., DN>) both decide with this one routine; `path_pdf > 0` is radiance_nee_then's alone.
+struct NeeGeom { float cosShadow, cosLight, dist2; bool isInfinite, is_singular; };
+ATN_DEV bool nee_geometry(NeeGeom& g, const f3& nml, const LightSample& ls)
+{
+    g.cosShadow = dot(nml, ls.dir);
+    g.cosLight = dot(ls.nml, -ls.dir);
+    g.dist2 = sqr(ls.dist);
+    g.isInfinite = (ls.attrib & ATN_LIGHT_ATTR_INFINITE) != 0;
+    g.is_singular = (ls.attrib & ATN_LIGHT_ATTR_SINGULAR) != 0;
+    g.dist2 = (g.isInfinite || g.is_singular) ? 1.0F : g.dist2;
+    return g.cosShadow >= 0 && g.cosLight >= 0 && g.dist2 > 0 && ls.pdf > 0.0F;
+}
+
 template <int MS = kMsCarPaint, class Then>
 ATN_DEV bool radiance_nee_then(const DevScene& sc, const f3& wi, const f3& nml, const DevMaterial& m,
                                float hu, float hv, float light_select_prob, const LightSample& ls, int32_t mtrl_id, float pre_r,
                                float* weight_ptr, Then&& then, const HitPre* pre = nullptr)
 {
     if (weight_ptr) *weight_ptr = 0.0F;
-    const float cosShadow = dot(nml, ls.dir);
     float path_pdf = material_pdf<MS>(sc, m, nml, wi, ls.dir, hu, hv, mtrl_id, pre);
     const MtrlSample ev = material_bsdf<MS>(sc, m, nml, wi, ls.dir, hu, hv, mtrl_id, pre_r, pre);
     if (ev.pdf > 0) path_pdf = ev.pdf;
-    const float cosLight = dot(ls.nml, -ls.dir);
-    float dist2 = sqr(ls.dist);
-    const bool isInfinite = (ls.attrib & ATN_LIGHT_ATTR_INFINITE) != 0;
-    const bool is_singular = (ls.attrib & ATN_LIGHT_ATTR_SINGULAR) != 0;
-    dist2 = (isInfinite || is_singular) ? 1.0F : dist2;
-    if (cosShadow >= 0 && cosLight >= 0 && dist2 > 0 && path_pdf > 0.0F && ls.pdf > 0.0F) {
+    NeeGeom g;
+    const bool geom_ok = nee_geometry(g, nml, ls);
+    const float cosShadow = g.cosShadow, cosLight = g.cosLight, dist2 = g.dist2;
+    const bool isInfinite = g.isInfinite, is_singular = g.is_singular;
+    if (geom_ok && path_pdf > 0.0F) {
         if (!isInfinite) path_pdf = (path_pdf * cosLight) / dist2;
         const float f = ls.pdf * light_select_prob;
         const float misW = is_singular ? 1.0f : f / (f + path_pdf);

@@ -400,6 +400,20 @@ inline bool rr_lookahead_valid(const std::vector<DevMaterial>& materials)
     return true;
 }
 
+// The deferred NEE (device/kernels.hpp, PathBuffers::nee_reached) replays a vertex from its hit record, so nothing of the vertex may depend
+// on a draw the replay does not repeat or end the path at the hit: material sets Core, Disney and Analytic qualify (bit 0); CarPaint
+// draws in applyNormal and a toon surface ends the path at a first hit -- those sets keep the eager kernels.  Without a light there is no
+// NEE to defer.  Whether deferral PAYS depends on how many shadow rays reach their light: a few per cent under an environment or a
+// directional light inside a building, most of them under an area lamp in a room (docs/NEE_DEFERRAL.md).  Bit 1 -- every light is
+// infinite -- is what the default policy asks for on top.
+inline int32_t nee_deferral_class(int32_t material_set, const atn_light_param* lights, uint32_t n_lights)
+{
+    if (material_set > kMsAnalytic || n_lights == 0 || !lights) return 0;
+    bool all_infinite = true;
+    for (uint32_t i = 0; i < n_lights; i++) if (!(lights[i].attrib & ATN_LIGHT_ATTR_INFINITE)) all_infinite = false;
+    return all_infinite ? 3 : 1;
+}
+
 inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::string& err, int anyhit_twins = 0, int twin_dirs = 8,
                              int node_layout_top_levels = kLayoutTopLevels, bool planar_lights = true, uint64_t twin_budget_bytes = kTwinBudgetBytes)
 {
@@ -639,6 +653,7 @@ inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::
                            : t == ATN_MTRL_CARPAINT ? kMsCarPaint : t == ATN_MTRL_DISNEY ? kMsDisney : core ? kMsCore : kMsAnalytic;
         if (need > p.material_set) p.material_set = need;
     }
+    p.nee_deferral = nee_deferral_class(p.material_set, s->lights, s->n_lights);
     // ImageBasedLight::sample's scene_radius (light/ibl.h:106-111; aabb::IsValid / getCenter /
     // ComputeDistanceToCoverBoundingSphere, math/aabb.h:176-180,231-234,346-362), evaluated once on the host.
     {

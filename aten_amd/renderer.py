@@ -225,6 +225,21 @@ class PathTracing:
         self._check(self._l.atn_rr_lookahead_stats(self._ctx, s.ctypes.data))
         return dict(doomed_rays=int(s[0]), doomed_hits=int(s[1]), doomed_nodes=int(s[2]), doomed_tris=int(s[3]))
 
+    def set_nee_deferral(self, mode):
+        """The deferred NEE of render() (include/aten_amd.h): 0 off (the mode a context starts in), 1 on wherever the scene qualifies, 2 (the
+        policy) where it qualifies and every light is infinite.  Films are byte-equal in every mode."""
+        self._check(self._l.atn_set_nee_deferral(self._ctx, int(mode)))
+
+    def nee_deferral_active(self):
+        """Whether frames of the current scene defer their NEE evaluation under the current mode."""
+        return bool(self._l.atn_nee_deferral_active(self._ctx))
+
+    def nee_deferral_stats(self):
+        """Over the deferred frames since the last reset(): shadow rays cast and the ones that reached their light."""
+        s = np.zeros(2, np.uint64)
+        self._check(self._l.atn_nee_deferral_stats(self._ctx, s.ctypes.data))
+        return dict(cast=int(s[0]), reached=int(s[1]))
+
     def set_regeneration(self, on):
         """Path regeneration (include/aten_amd.h): the samples of a frame / the frames of a burst share one pool of path slots.
         Off by default.  Measured guidance: switch it on for render_burst of >= 2 multi-sample frames in the

@@ -214,6 +214,24 @@ int atn_set_rr_lookahead(atn_ctx* ctx, int32_t mode);
 int32_t atn_rr_lookahead_active(atn_ctx* ctx);
 int atn_rr_lookahead_stats(atn_ctx* ctx, uint64_t out[4]);
 
+/* The deferred NEE of atn_render's serial sample loop.  HitShadowRay adds a vertex's light sample only if its shadow ray reaches the
+ * light, so in a deferred frame shade casts the ray from the sample's geometry alone and the rest of the sample -- the environment
+ * texel, the second BSDF evaluation, the MIS weight -- is evaluated after the ray has been traced, for the rays that reached their
+ * light: one small launch per bounce replays those vertices with shade's own functions.  Films are byte-equal in every mode
+ * (docs/NEE_DEFERRAL.md).  A scene qualifies when its material set is Core, Disney or Analytic (no CarPaint, Toon / StylizedBrdf
+ * material) and it has a light; decided at atn_upload_scene.  mode 0 = off: the mode a context starts in (ATEN_AMD_NEE_DEFERRAL at
+ * atn_create selects another) -- measured, the headline frame does not gain (docs/NEE_DEFERRAL.md); 1 = every scene that qualifies;
+ * 2 = the policy: scenes that qualify AND whose lights are all infinite (environment, directional): under an area lamp most shadow
+ * rays reach the light and the replay costs more than it saves.  A bank allocates the mode's extra state (36 bytes per path slot)
+ * when it first runs a deferred frame.  atn_nee_deferral_active tells (1 / 0) whether
+ * frames of the current scene run it.  Frames with count_stats = 1 stay eager (the reference's ray accounting).
+ * atn_nee_deferral_stats: {shadow rays cast, rays that reached the light} over the deferred frames since the last atn_reset -- a caller
+ * whose scene lets most rays through can see it and switch the mode off.  ATN_K_TRACE_SHADOW times the evaluation launches.  Not
+ * applied by the regenerated pool, SVGF, ReSTIR, NPR, AO, volume frames or atn_set_shade_math(1). */
+int atn_set_nee_deferral(atn_ctx* ctx, int32_t mode);
+int32_t atn_nee_deferral_active(atn_ctx* ctx);
+int atn_nee_deferral_stats(atn_ctx* ctx, uint64_t out[2]);
+
 /* ≙ idaten::Renderer::reset (renderer.h:40-43): clears the progressive film. */
 int atn_reset(atn_ctx* ctx);
 

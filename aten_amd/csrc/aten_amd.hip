@@ -23,6 +23,7 @@
 #include "device/restir.hpp"
 #include "device/npr.hpp"
 #include "device/ao.hpp"
+#include "device/npr_shadow.hpp"
 #include "device/volume.hpp"
 #include "device/lbvh.hpp"
 #include "device/skinning.hpp"
@@ -262,6 +263,9 @@ public:
     struct Bank {
         DevBuf<float4> ray_o, ray_d, thr, contrib, isect, sh_o, sh_d, sh_c, sh_w, accum, tile_out, pend, rg_frames;
         DevBuf<uint32_t> done, queue0, queue1, shadow_q, nee_reached, counters, rg_counters, rg_regions;
+        DevBuf<float> ns_depth_s, ns_lit, ns_depth, ns_plane;      // the NPR shadow pre-pass's planes of the bank's last mode-1 frame
+        uint32_t ns_slots = 0;
+        int32_t ns_w = 0, ns_h = 0;
         int32_t rg_stages = 0;
         uint32_t n_slots = 0;
         int32_t counters_depth = 0;
@@ -293,6 +297,8 @@ public:
         std::swap(stream, b.stream); std::swap(ev_fork, b.ev_fork); std::swap(ev_gather, b.ev_gather);
         for (int k = 0; k < kMaxBatches; k++) { std::swap(bstream[k], b.bstream[k]); std::swap(ev_join[k], b.ev_join[k]); }
         std::swap(batch_streams_checked, b.batch_streams_checked);
+        ns_depth_s.swap(b.ns_depth_s); ns_lit.swap(b.ns_lit); ns_depth.swap(b.ns_depth); ns_plane.swap(b.ns_plane);
+        std::swap(ns_slots, b.ns_slots); std::swap(ns_w, b.ns_w); std::swap(ns_h, b.ns_h);
     }
 
     int set_frames_in_flight(int n)
@@ -1875,6 +1881,8 @@ public:
     {
         int rc = check_ready(d);
         if (rc) return rc;
+        rc = ns_check(d);
+        if (rc) return rc;
         ATN_HIP(hipSetDevice(device));
         if (d->sample > 1 && regen_applies(*d, 1)) return render_regen(d, 1, out_host);
         const bool count = d->count_stats != 0, prof = d->profile != 0;
@@ -1893,7 +1901,10 @@ public:
         PathBuffers pb = buffers(count);
 
         const uint32_t g_all = (n_slots + 255u) / 256u;
+        // atn_npr_shadow_set_mode(1): this frame's Toon shading reads the plane the pre-pass makes now
+        if (ns_frame()) { rc = ns_prepass(d); if (rc) return rc; }
         rc = run_paths<false>(d, fp, count, prof, SvgfShade{}, SvgfFrame{});
+        { const int e = ns_end_frame(); if (!rc) rc = e; }
         if (rc) return rc;
         fp.slot_begin = 0; fp.slot_end = (int32_t)n_slots;
         rc = wait_film();
@@ -1967,6 +1978,7 @@ public:
     {
         if (!d) return fail(ATN_ERR_INVALID_ARG, "null destination");
         if (n_frames <= 0) return fail(ATN_ERR_INVALID_ARG, "bad burst length");
+        if (ns_mode == 1) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: bursts are not supported: render the frames with atn_render, or atn_npr_shadow_set_mode(0)");
         if (regen_applies(*d, n_frames)) {
             { const int rc = check_ready(d); if (rc) return rc; }
             ATN_HIP(hipSetDevice(device));
@@ -2782,14 +2794,16 @@ public:
         std::memcpy(&np_cfg, s->config.feature_line, sizeof(np_cfg));
         np_mflags_host.assign((size_t)s->n_materials + 1, 0u);        // (+ the white-diffuse fallback: no lines)
         np_stencil = false; np_carpaint = false;
-        bool maybe_alpha = false;
+        bool maybe_alpha = false, any_shadow = false;
         for (uint32_t i = 0; i < s->n_materials; i++) {
             atn_feature_line_mtrl fl;
             std::memcpy(&fl, s->materials[i].feature_line, sizeof(fl));
             np_mflags_host[i] = (fl.enable ? 1u : 0u) | ((uint32_t)fl.metric_flag << 8);
             if (s->materials[i].stencil_type == 2) np_stencil = true;         // StencilType::STENCIL
             if (s->materials[i].type == ATN_MTRL_CARPAINT) np_carpaint = true;
+            if ((s->materials[i].type == ATN_MTRL_TOON || s->materials[i].type == ATN_MTRL_STYLIZED_BRDF) && s->materials[i].toon.stylized_shadow.enable) any_shadow = true;
         }
+        ns_any = any_shadow;
         for (const DevMaterial& dm : img.materials) if (dm.attrib & kAttrMaybeAlpha) maybe_alpha = true;
         np_alpha = s->config.enable_alpha_blending != 0 && maybe_alpha;
         ATN_HIP(np_mflags.upload(np_mflags_host, stream));
@@ -2848,6 +2862,8 @@ public:
         if (rc) return rc;
         rc = npr_ensure(d->width, d->height, d->maxDepth);
         if (rc) return rc;
+        // atn_npr_shadow_set_mode(1): the same pre-pass as with lines off (docs/NPR_SHADOW.md)
+        if (ns_frame()) { rc = ns_prepass(d); if (rc) return rc; }
         if (!np_ev) ATN_HIP(hipEventCreateWithFlags(&np_ev, hipEventDisableTiming));
         const bool prof = d->profile != 0;
         FrameParams fp = frame_params(*d);
@@ -2908,6 +2924,8 @@ public:
         ATN_HIP(hipEventRecord(np_ev, stream));
         np_pending = true;
         np_captured = np_capture != 0;
+        rc = ns_end_frame();
+        if (rc) return rc;
         rc = wait_film();
         if (rc) return rc;
         prof_begin(prof, ATN_K_GATHER);
@@ -3318,6 +3336,140 @@ public:
         case 5: ATN_HIP(hipMemcpy(out, ao_st_ans.p, n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
         }
         return fail(ATN_ERR_INVALID_ARG, "no such AO buffer");
+    }
+
+    // ------------------------------------------------------------------------------------------------
+    // The NPR shadow pre-pass (aten::NprPathTracer::OnRender's first pass / idaten's onShadeByShadowRay, device/npr_shadow.hpp;
+    // docs/NPR_SHADOW.md).  The planes belong to the BANK (they rotate with it, swap_bank): a frame in flight keeps its own plane, so
+    // the next frame's pre-pass -- on another bank's stream -- overwrites nothing this frame's shade launches still read, and nothing
+    // orders the two.
+    // ------------------------------------------------------------------------------------------------
+    DevBuf<float> ns_depth_s, ns_lit, ns_depth, ns_plane;       // (the current bank's)
+    DevBuf<float> ns_f_lit, ns_f_depth, ns_f_out;               // atn_npr_shadow_filter's own
+    // the planes of the last frame that ran the pre-pass, whichever bank is current now (atn_npr_shadow_download): they stay valid until
+    // that bank runs its next pre-pass, which becomes the last one
+    const float* ns_last[3] = {};
+    int32_t ns_last_w = 0, ns_last_h = 0;
+    int32_t ns_mode = 0;            // atn_npr_shadow_set_mode
+    bool ns_any = false;            // an uploaded Toon / StylizedBrdf material has stylized_shadow.enable (upload)
+    uint32_t ns_slots = 0;
+    int32_t ns_w = 0, ns_h = 0;
+    bool ns_rendered = false;
+
+    int ns_set_mode(int32_t mode)
+    {
+        if (mode != 0 && mode != 1) return fail(ATN_ERR_INVALID_ARG, "NPR shadow: mode is 0 (the uploaded texture) or 1 (the shadow-ray pre-pass)");
+        ns_mode = mode;
+        return ATN_OK;
+    }
+
+    // does this frame run the pre-pass?
+    bool ns_frame() const { return ns_mode == 1 && ns_any; }
+
+    // what mode 1 cannot do in atn_render (atn_npr_render refuses the same configurations itself, mode 1 or not)
+    int ns_check(const atn_destination* d)
+    {
+        if (ns_mode != 1) return ATN_OK;
+        if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: the row filter crosses tiles, the whole frame has to be on one GPU (atn_set_screen_shard world 1)");
+        if (regen_mode != 0) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: frames run the serial sample loop: switch path regeneration off (atn_set_regeneration(0))");
+        if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: there are no relaxed-math kernels: atn_set_shade_math(0)");
+        if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: its rays are not counted (count_stats must be 0)");
+        if (np_carpaint) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: applyNormal's CarPaint flake samples are not drawn: CarPaint materials are refused");
+        return ATN_OK;
+    }
+
+    int ns_ensure(int32_t w, int32_t h)
+    {
+        if (n_slots != ns_slots) { ATN_HIP(ns_depth_s.resize(n_slots)); ns_slots = n_slots; }
+        if (w != ns_w || h != ns_h) {
+            const size_t n = (size_t)w * h;
+            ATN_HIP(ns_lit.resize(n)); ATN_HIP(ns_depth.resize(n)); ATN_HIP(ns_plane.resize(n));
+            ns_w = w; ns_h = h;
+        }
+        return ATN_OK;
+    }
+
+    // The pre-pass of a frame, on the frame's stream and bank, in front of its sample loop (begin_frame has run): sample 0's paths, their
+    // closest hits, the bounce-0 shadow rays, the row filter.  Leaves `scene` pointing at the plane: ns_end_frame() puts the uploaded
+    // texture back once the frame's launches are enqueued (kernel arguments are copied at the launch).
+    const float* ns_saved_tex = nullptr;
+    int32_t ns_saved_w = 0, ns_saved_h = 0;
+    bool ns_swapped = false;
+    int ns_prepass(const atn_destination* d)
+    {
+        if (frames_in_flight > 1 && (d->width != ns_w || d->height != ns_h || n_slots != ns_slots)) { const int q = quiesce(); if (q) return q; }
+        int rc = ns_ensure(d->width, d->height);
+        if (rc) return rc;
+        const bool prof = d->profile != 0;
+        FrameParams fp = frame_params(*d);
+        PathBuffers pb = buffers(false);
+        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
+        fp.chunk_items = plan.shade_items;
+        NsArgs na{};
+        na.depth_s = ns_depth_s.p; na.lit = ns_lit.p; na.depth = ns_depth.p; na.plane = ns_plane.p;
+        NsLaunch nl{};
+        nl.grid = grid_for(n_slots);
+        nl.refill = plan.refill; nl.lds_bytes = plan.lds_bytes;
+        nl.trace_block = plan.refill ? (uint32_t)kTraceBlock : plan.block;
+        nl.trace_grid = plan.refill ? trace_grid(n_slots, true) : grid_for(n_slots) * (256u / plan.block);
+        ATN_HIP(hipMemsetAsync(counters.p, 0, (size_t)4 * counters_depth * 4, stream));
+        prof_begin(prof, ATN_K_GEN);
+        hipLaunchKernelGGL(k_gen_path, dim3(grid_for(n_slots)), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
+        prof_end(prof);
+        prof_begin(prof, ATN_K_TRACE_CLOSEST);
+        ns_launch_primary(trace_launch(plan, 0), stream, pb, scene, na);
+        prof_end(prof);
+        prof_begin(prof, ATN_K_SHADE);
+        ns_launch_rays(nl, stream, pb, scene, fp, na);
+        ns_launch_filter(stream, ns_lit.p, ns_depth.p, ns_plane.p, d->width, d->height);
+        prof_end(prof);
+        ATN_HIP(hipGetLastError());
+        ns_saved_tex = scene.screen_shadow; ns_saved_w = scene.ss_w; ns_saved_h = scene.ss_h;
+        scene.screen_shadow = ns_plane.p; scene.ss_w = d->width; scene.ss_h = d->height;
+        ns_swapped = true;
+        ns_rendered = true;
+        ns_last[0] = ns_plane.p; ns_last[1] = ns_lit.p; ns_last[2] = ns_depth.p;
+        ns_last_w = d->width; ns_last_h = d->height;
+        return ATN_OK;
+    }
+    // behind the frame's last shade launch (on `stream`, the batches joined): the uploaded texture is the scene's again
+    int ns_end_frame()
+    {
+        if (!ns_swapped) return ATN_OK;
+        scene.screen_shadow = ns_saved_tex; scene.ss_w = ns_saved_w; scene.ss_h = ns_saved_h;
+        ns_swapped = false;
+        return ATN_OK;
+    }
+
+    int ns_download(int32_t which, float* out, uint32_t n)
+    {
+        if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
+        if (!ns_rendered) return fail(ATN_ERR_INVALID_ARG, "no frame has run the NPR shadow pre-pass");
+        if (which < 0 || which > 2) return fail(ATN_ERR_INVALID_ARG, "no such NPR shadow plane");
+        if ((size_t)n != (size_t)ns_last_w * ns_last_h) return fail(ATN_ERR_INVALID_ARG, "NPR shadow planes have width x height floats");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        ATN_HIP(hipStreamSynchronize(stream));
+        ATN_HIP(hipMemcpy(out, ns_last[which], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        return ATN_OK;
+    }
+
+    // the row filter alone over uploaded planes (a stage entry for tests)
+    int ns_filter(const float* lit, const float* depth, int32_t w, int32_t h, float* out)
+    {
+        if (!lit || !depth || !out) return fail(ATN_ERR_INVALID_ARG, "null plane");
+        if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(ATN_ERR_INVALID_ARG, "NPR shadow filter: sizes are 1..16384 per side");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        const size_t n = (size_t)w * h;
+        ATN_HIP(ns_f_lit.resize(n)); ATN_HIP(ns_f_depth.resize(n)); ATN_HIP(ns_f_out.resize(n));
+        ATN_HIP(hipMemcpyAsync(ns_f_lit.p, lit, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipMemcpyAsync(ns_f_depth.p, depth, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        ns_launch_filter(stream, ns_f_lit.p, ns_f_depth.p, ns_f_out.p, w, h);
+        ATN_HIP(hipGetLastError());
+        ATN_HIP(hipMemcpyAsync(out, ns_f_out.p, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        return ATN_OK;
     }
 
     // ≙ idaten::Renderer::reset, renderer.h:40-43
@@ -3752,6 +3904,13 @@ int atn_ao_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host)
 int atn_ao_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.ao_reset(); }); }
 int atn_ao_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.ao_capture = on != 0; return ATN_OK; }
 int atn_ao_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.ao_download(which, out_host); }); }
+int atn_npr_shadow_set_mode(atn_ctx* ctx, int32_t mode) { CTX_QUIET_OR_FAIL(ctx); return ctx->r.ns_set_mode(mode); }
+int atn_npr_shadow_download(atn_ctx* ctx, int32_t which, float* out_host, uint32_t n) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.ns_download(which, out_host, n); }); }
+int atn_npr_shadow_filter(atn_ctx* ctx, const float* lit, const float* depth, int32_t w, int32_t h, float* out_host)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.ns_filter(lit, depth, w, h, out_host); });
+}
 int atn_svgf_denoise(atn_ctx* ctx, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host)
 {
     CTX_QUIET_OR_FAIL(ctx);

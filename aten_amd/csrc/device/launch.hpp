@@ -138,6 +138,19 @@ void ao_launch_primary(const TraceLaunch& l, hipStream_t st, const PathBuffers& 
 void ao_launch_rays(const AoLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const AoArgs& aa);
 void ao_launch_resolve(const AoLaunch& l, hipStream_t st, const FrameParams& fp, const AoArgs& aa, float4* film, float4* tile_out);
 
+// ---- npr_shadow.hip (device/npr_shadow.hpp) ----
+struct NsArgs;
+// the shadow pre-pass's launches after k_gen_path: the primary rays (the pass's first trace launch, with a job that keeps t), shade over
+// the queue, the shadow rays through the frame's walk (the plan's walk, LDS copy and block), the row filter over w x h pixels
+struct NsLaunch {
+    uint32_t grid;              // shade blocks of 256 (grid-stride over the queue)
+    bool refill;
+    uint32_t trace_grid, trace_block, lds_bytes;
+};
+void ns_launch_primary(const TraceLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const NsArgs& na);
+void ns_launch_rays(const NsLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const NsArgs& na);
+void ns_launch_filter(hipStream_t st, const float* lit, const float* depth, float* out, int32_t width, int32_t height);
+
 // ---- volume.hip (device/volume.hpp) ----
 struct VolArgs;
 // one iteration's volume launches: the closest-hit walk and the connection walk through the frame's walk (the plan's walk, LDS copy and

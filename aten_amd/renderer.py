@@ -572,6 +572,30 @@ class PathTracing:
             return dict(kind=out[..., 0].astype(np.int32), t=out[..., 1].copy(), c=out[..., 2].copy(), skips=out[..., 3].astype(np.int32))
         raise ValueError("no AO buffer %r" % (name,))
 
+    # ---- the NPR shadow pre-pass (NprPathTracer::OnRender's first pass / idaten's onShadeByShadowRay; docs/NPR_SHADOW.md)
+    def set_npr_shadow(self, mode):
+        """0 (default): Toon shading reads the screen-space shadow texture uploaded with the scene; 1: render() and npr_render() first
+        make it from the frame's own bounce-0 shadow rays (the depth-aware row filter over "the ray reached its light")."""
+        self._check(self._l.atn_npr_shadow_set_mode(self._ctx, int(mode)))
+
+    def npr_shadow_buffer(self, which):
+        """The planes of the last frame that ran the pre-pass, float32 [h, w]: 'plane' / 0 the filtered plane, 'lit' / 1 the bit as
+        0.0 / 1.0, 'depth' / 2 the primary hit's t (inf: a miss)."""
+        k = ("plane", "lit", "depth").index(which) if isinstance(which, str) else int(which)
+        out = np.empty((self.height, self.width), np.float32)
+        self._check(self._l.atn_npr_shadow_download(self._ctx, k, out.ctypes.data, out.size))
+        return out
+
+    def npr_shadow_filter(self, lit, depth):
+        """The pre-pass's row filter alone over host planes [h, w] (11 taps, ApplyBilateralFilter<ShadowRay, float, true, 5>)."""
+        l = np.ascontiguousarray(lit, np.float32)
+        d = np.ascontiguousarray(depth, np.float32)
+        if l.shape != d.shape or l.ndim != 2:
+            raise ValueError("lit and depth are [h, w] planes of one shape")
+        out = np.empty_like(l)
+        self._check(self._l.atn_npr_shadow_filter(self._ctx, l.ctypes.data, d.ctypes.data, l.shape[1], l.shape[0], out.ctypes.data))
+        return out
+
     def svgf_denoise(self, width, height, frame=0, compute_motion=False, stages=False, download=True, profile=False):
         """The filter passes of OnRender on the buffers as they stand (svgf_upload / a previous path pass)."""
         d = Destination(width, height, 1, 1, 1, frame, 0, 1, 0, int(profile))

@@ -85,6 +85,8 @@ def sponza_lod(asset_dir=None, mtype=L.MTRL_GGX, ibl=True, use_sbvh=True, textur
     def create_mtrl(name, mt, clr, albedo, nml):
         alb = b.load_image(os.path.join(asset_dir, albedo)) if (albedo and textures) else -1
         nm = b.load_image(os.path.join(asset_dir, nml)) if (nml and textures) else -1
+        if callable(mtype):         # mtype(builder, name, colour, albedo map, normal map) -> material id
+            return mtype(b, name, clr, alb, nm)
         if mtype == L.MTRL_GGX:
             return b.add_material(name, L.MTRL_GGX, clr, albedo_map=alb, normal_map=nm, roughness=0.3, ior=0.01)
         if mtype == L.MTRL_DISNEY:
@@ -568,21 +570,30 @@ def toon_ramp(steps=(0.15, 0.45, 0.8, 1.0), width=64, tint=(1.0, 1.0, 1.0)):
     return t
 
 
-def toon_room(asset_dir=None, target="point", screen_shadow=None, alpha_blocker=False):
+def toon_room(asset_dir=None, target="point", screen_shadow=None, alpha_blocker=False, stylized_shadow=(), without=()):
     """The Cornell box with NPR materials (material/toon.cpp): the tall box is a Toon material of diffuse type, the short
     box a StylizedBrdf of specular type with a stylised highlight and a rim light, the floor a Toon material of specular type;
     all aim at ONE NPR target light (context::AddNprTargetLight) -- a point light, or the room's area light -- and the
     area light still lights the rest of the room.  `screen_shadow` [h, w]: the screen-space shadow texture of the
-    stylized-shadow feature (enabled on the tall box when given)."""
+    stylized-shadow feature (enabled on the tall box when given).  `stylized_shadow`: names of toon materials ("tallBox", "floor")
+    that enable the feature whether or not a texture is given; `without`: material names whose objects are left out of the room."""
     asset_dir = asset_dir or os.path.join(ASSETS, "cornellbox")
     b = SceneBuilder()
+    shadow_term = dict(shadow_enable=1, shadow_threshold=0.9, shadow_offset=0.05, shadow_scale=1.0)
+    left_out = []
     emit = b.add_material("light", L.MTRL_EMISSIVE, (1.0, 1.0, 1.0))
     ramp = b.add_texture("ramp4", toon_ramp())
     ramp_warm = b.add_texture("ramp3warm", toon_ramp((0.2, 0.6, 1.0), tint=(1.0, 0.85, 0.6)))
 
     def create_mtrl(name, mtype, clr, albedo, nml):
+        mid = create_mtrl_named(name, mtype, clr)
+        if name in without:
+            left_out.append(mid)
+        return mid
+
+    def create_mtrl_named(name, mtype, clr):
         if name == "tallBox":
-            extra = dict(shadow_enable=1, shadow_threshold=0.9, shadow_offset=0.05, shadow_scale=1.0) if screen_shadow is not None else {}
+            extra = shadow_term if (screen_shadow is not None or name in stylized_shadow) else {}
             return b.add_toon_material(name, (0.9, 0.5, 0.4), target_light_idx=0, remap_texture=ramp, **extra)
         if name == "shortBox":
             return b.add_toon_material(name, (0.4, 0.6, 0.9), stylized=True, toon_type=L.MTRL_SPECULAR, target_light_idx=0,
@@ -592,14 +603,15 @@ def toon_room(asset_dir=None, target="point", screen_shadow=None, alpha_blocker=
                                        rim_enable=1, rim_width=0.4, rim_softness=0.3, rim_color=(0.3, 0.5, 1.0), rim_spread=1.0)
         if name == "floor":
             return b.add_toon_material(name, (0.7, 0.7, 0.6), toon_type=L.MTRL_SPECULAR, target_light_idx=0, remap_texture=-1,
-                                       roughness=0.4, ior=1.4, will_receive_shadow=1)
+                                       roughness=0.4, ior=1.4, will_receive_shadow=1, **(shadow_term if name in stylized_shadow else {}))
         return b.add_material(name, mtype, clr)
 
     objs = b.load_obj(os.path.join(asset_dir, "orig.obj"), create_mtrl=create_mtrl, separate_objs=True, normal_on_the_fly=True)
     light = b.create_instance(objs[0])
     lid = b.add_area_light(light, b.materials[emit][1]["baseColor"][:3], 200.0)
     for o in objs[1:]:
-        b.create_instance(o)
+        if not (left_out and all(m["mtrl"] in left_out for m in b.objects[o]["meshes"])):
+            b.create_instance(o)
     if alpha_blocker:
         glass = b.add_material("pane", L.MTRL_DIFFUSE, (0.9, 0.9, 0.9, 0.5))
         b.config.enable_alpha_blending = 1
@@ -637,6 +649,42 @@ def with_feature_lines(scene, enabled=True, color=(0.0, 0.0, 0.0), width=1.5, al
         on = materials is None or i in materials
         write_feature_line_mtrl(mats[i], 1 if on else 0, metric_flag if on else 0)
     return fs, cam
+
+
+def stylized_shadow_room(asset_dir=None, target="point", alpha_blocker=False, short_box=True):
+    """toon_room with the stylized shadow term (ToonParameter::stylized_shadow) enabled on the tall box AND the floor, and no
+    uploaded screen-space texture: the scene of the NPR shadow pre-pass (PathTracing.set_npr_shadow(1); docs/NPR_SHADOW.md), which
+    makes the texture per frame.  Toon pixels lit and in the boxes' shadows, non-toon walls, the lamp, background pixels (the camera is
+    toon_room's with a wider field of view).
+    `short_box=False` leaves the short box out (what its shadow on the floor is measured against)."""
+    fs, cam = toon_room(asset_dir, target=target, alpha_blocker=alpha_blocker, stylized_shadow=("tallBox", "floor"),
+                        without=() if short_box else ("shortBox",))
+    # (a wider view than toon_room's: the background shows around the box's open front at every aspect ratio)
+    return fs, dict(cam, vfov=56.0)
+
+
+def stylized_shadow_sponza(asset_dir=None):
+    """sponza_lod with every second material a Toon material of diffuse type that enables the stylized shadow term, aiming at a point
+    NPR target light under the roof; the others keep their GGX parameters and the synthetic sky lights the scene: the benchmark scene
+    of the NPR shadow pre-pass (tools/npr_shadow_bench.py)."""
+    def mtrl(b, name, clr, alb, nm):
+        if len(b.materials) % 2:
+            return b.add_material(name, L.MTRL_GGX, clr, albedo_map=alb, normal_map=nm, roughness=0.3, ior=0.01)
+        ramp = b.add_texture("ramp4", toon_ramp())
+        return b.add_toon_material(name, clr, target_light_idx=0, remap_texture=ramp, albedo_map=alb, normal_map=nm,
+                                   shadow_enable=1, shadow_threshold=0.9, shadow_offset=0.05, shadow_scale=1.0)
+
+    def target_light(b, bmin, bmax, cam):
+        l = np.zeros((), L.LIGHT_PARAM)
+        l["type"] = L.LIGHT_POINT; l["attrib"] = L.LATTR_SINGULAR
+        l["pos"] = [0.5 * (bmin[0] + bmax[0]), bmin[1] + 0.8 * (bmax[1] - bmin[1]), 0.5 * (bmin[2] + bmax[2]), 1.0]
+        l["light_color"] = (1.0, 1.0, 1.0)
+        l["innerAngle"] = l["outerAngle"] = np.pi
+        l["scale"], l["intensity"] = 1.0, 40.0
+        l["arealight_objid"] = -1; l["envmapidx"] = -1
+        b.add_npr_target_light(l)
+
+    return sponza_lod(asset_dir, mtype=mtrl, add_lights=target_light)
 
 
 def npr_room(asset_dir=None, **lines):

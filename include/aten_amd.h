@@ -519,6 +519,28 @@ int atn_ao_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host);
 int atn_ao_reset(atn_ctx* ctx);
 int atn_ao_capture(atn_ctx* ctx, int32_t on);
 int atn_ao_download(atn_ctx* ctx, int32_t which, void* out_host);
+/* ---- The NPR shadow pre-pass (aten::NprPathTracer::OnRender's first pass, src/libaten/renderer/npr/npr.cpp:284-349,399-447;
+ * idaten::NPRPathTracing::onShadeByShadowRay, src/libidaten/npr/npr_pathtracing.cu:211-281,446-476,521-605; docs/NPR_SHADOW.md) ----
+ * The screen-space shadow texture Toon / StylizedBrdf materials multiply their band with (ToonParameter::stylized_shadow,
+ * material/toon.cpp:148-160), made per frame from the frame's own rays: per pixel the bounce-0 NEE shadow ray of sample 0 (the ray
+ * PathTracing::shade casts, pathtracing.cpp:91-236, with the path's termination flag forced off, npr.cpp:305-307), whether it reached
+ * its light (HitTestToTargetLight, pathtracing_impl.h:266-393), and that bit filtered along the row by
+ * ApplyBilateralFilter<ShadowRay, float, true, 5> with coefficients (2, 2) (aorenderer_impl.h:138-191; 11 taps, the depth the
+ * primary hit's t).
+ *   atn_npr_shadow_set_mode: 0 (default) Toon shading reads the texture uploaded with the scene (atn_scene_desc::screen_space_texture);
+ *                    1 atn_render and atn_npr_render first run the pre-pass for the frame's camera and the frame's Toon shading reads
+ *                    its plane.  A scene without a material that enables the term skips the pre-pass.  Other values:
+ *                    ATN_ERR_INVALID_ARG.  While the mode is 1: ATN_ERR_UNSUPPORTED for a screen shard with world > 1, path
+ *                    regeneration, atn_render_burst, relaxed shade math, count_stats and CarPaint materials.  The SVGF, ReSTIR, volume
+ *                    and AO frames ignore the mode.
+ *   atn_npr_shadow_download: the planes of the last frame that ran the pre-pass, n = width * height floats, row-major: which = 0 the
+ *                    filtered plane; 1 the bit as 0.0 / 1.0; 2 the primary hit's t (inf: a miss).  Waits for that frame.
+ *                    ATN_ERR_INVALID_ARG before such a frame and for another n.
+ *   atn_npr_shadow_filter: the row filter alone over host planes lit / depth [h][w] -> out_host [h][w]; w, h 1..16384.
+ * Additive entry points: atn_abi_version stays 3. */
+int atn_npr_shadow_set_mode(atn_ctx* ctx, int32_t mode);
+int atn_npr_shadow_download(atn_ctx* ctx, int32_t which, float* out_host, uint32_t n);
+int atn_npr_shadow_filter(atn_ctx* ctx, const float* lit, const float* depth, int32_t w, int32_t h, float* out_host);
 /* The filter passes alone (everything of OnRender after the sample loop, svgf.cpp:515-637) on whatever the
  * path pass -- or atn_svgf_upload -- left in the buffers: contributions (which = 14: contrib.xyz, sample count),
  * the current AOVs (0, 1), primary hit positions (10), motion/depth (9).  This is how a caller that already has a

@@ -361,64 +361,57 @@ int orc_svgf_get_buffer(void* h, int32_t which, atn_vec4* out)
     return (int)b->size();
 }
 
-// SVGFRenderer::OnRender (svgf.cpp:452-637).  `film` receives what dst.buffer holds when OnRender returns (Film::put,
-// film.cpp:33-45): the last a-trous iteration's albedo-multiplied colour.  `stage_out` (may be null): 3 x vec4[w*h] =
-// the values put after the path pass, after the temporal pass and after the variance pass.
-// compute_motion != 0: fill motion_depth_buffer from the primary hits (ComputeMotionDepth) instead of an external buffer.
-void orc_svgf_render(void* h, const atn_scene_desc* scene, const atn_camera_param* camera,
-    const uint32_t* seeds, uint32_t n_seeds, const orc_destination* dst, int32_t compute_motion,
-    atn_vec4* film, atn_vec4* stage_out)
+// The inverse of orc_svgf_get_buffer (same `which`): gives the oracle the history, or any other plane, a test wants both sides
+// to start from.  Creates the buffers of a w x h frame first where they do not exist yet (SVGFParams::InitBuffers).
+int orc_svgf_set_buffer(void* h, int32_t which, int32_t width, int32_t height, const atn_vec4* in)
 {
-    auto& P = *static_cast<svgf::Params*>(h);
-    Scene ctxt(scene);
+    auto* p = static_cast<svgf::Params*>(h);
+    if (p->width > 0 && (p->width != width || p->height != height)) return -1;      // a renderer keeps one frame size
+    p->InitBuffers(width, height);
+    const size_t n = (size_t)width * height;
+    std::vector<v4>* b = nullptr;
+    if (which >= 0 && which < 4) b = &p->cur(which);
+    else if (which < 8) b = &p->prev(which - 4);
+    else if (which == 8) b = &p->temporary_color_buffer;
+    else if (which == 9) { p->motion_depth_buffer.resize(n); b = &p->motion_depth_buffer; }
+    else if (which == 10) b = &p->primary_position;
+    else if (which == 11 || which == 12) b = &p->atrous_clr_variance[which - 11];
+    if (!b || b->size() != n) return -1;
+    for (size_t i = 0; i < n; i++) (*b)[i] = v4(in[i].x, in[i].y, in[i].z, in[i].w);
+    return (int)n;
+}
+
+// The filter half of SVGFRenderer::OnRender (svgf.cpp:515-637) on the planes as they stand in P: PrepareForDenoise, the motion
+// pass, temporal reprojection, the optional weight dilation, variance estimation, the a-trous levels and the copy-back.
+// `contribs`: Path.contrib as vec4 (contrib.xyz, samples) per pixel.  Shared by orc_svgf_render (behind its path pass) and
+// orc_svgf_denoise (on a caller's planes).
+static void svgf_filter_passes(svgf::Params& P, const atn_camera_param* camera, const orc_destination* dst, int32_t compute_motion,
+    const std::vector<v4>& contribs, atn_vec4* film, atn_vec4* stage_out)
+{
     const int32_t width = dst->width, height = dst->height;
-    const uint32_t samples = (uint32_t)dst->sample;
-    int32_t maxDepth = dst->maxDepth;
-    int32_t rrDepth = dst->russianRouletteDepth;
-    if (rrDepth > maxDepth) rrDepth = maxDepth - 1;         // svgf.cpp:423-425
-    P.InitBuffers(width, height);
-    P.mtxs.Reset(*camera);
+    const size_t n = (size_t)width * height;
     const m4 W2C = P.mtxs.GetW2C();
     const m4 prevW2C = svgf::mul(P.mtxs.V2C, P.mtxs.PrevW2V);
-    const size_t n = (size_t)width * height;
-    std::vector<v4> contribs(n);
     auto put = [&](int stage, int32_t idx, const v4& v) {
         if (stage_out && stage < 3) { atn_vec4& o = stage_out[(size_t)stage * n + idx]; o.x = v.x; o.y = v.y; o.z = v.z; o.w = v.w; }
         atn_vec4& o = film[idx]; o.x = v.x; o.y = v.y; o.z = v.z; o.w = v.w;
     };
-    if (dst->nthreads > 0) omp_set_num_threads(dst->nthreads);
 
 #pragma omp parallel for
-    for (int32_t y = 0; y < height; y++) {
-        for (int32_t x = 0; x < width; x++) {
-            int32_t idx = y * width + x;
-            PathState path;             // path_host_.Clear(): contrib/attrib/throughput zeroed every frame
-            path.samples = 0;
-            Ray ray; ShadowRay shadow_ray;
-            for (uint32_t i = 0; i < samples; i++) {
-                const uint32_t rnd = seeds[idx % n_seeds];
-                GeneratePath(ray, x, y, (int32_t)i, dst->frame, path, *camera, rnd);
-                path.contrib = v3(0);
-                svgf::ExecRendering(path, ray, shadow_ray, x, y, width, height, ctxt, *camera, maxDepth, rrDepth, W2C,
-                    P.cur(svgf::NormalDepth)[idx], P.cur(svgf::AlbedoMeshId)[idx], P.primary_position[idx], nullptr);
-                if (isInvalidColor(path.contrib)) continue;
-                if (path.is_terminated) break;
-            }
-            // PrepareForDenoise (svgf_impl.h:119-144)
-            const v4 c(path.contrib, path.samples);
-            v4 contrib = c;
-            svgf::operator/=(contrib, c.w);
-            if (dst->frame == 0) {
-                float lum = luminance(contrib.x, contrib.y, contrib.z);
-                v4& mt = P.cur(svgf::MomentTemporalWeight)[idx];
-                mt.x += lum * lum; mt.y += lum; mt.z += 1;
-                v4& cv = P.cur(svgf::ColorVariance)[idx];
-                cv = v4(contrib.x, contrib.y, contrib.z, cv.w);
-            }
-            P.temporary_color_buffer[idx] = c;
-            contribs[idx] = c;
-            put(0, idx, v4(path.contrib, 1));       // Film::put(x, y, vec3) -> vec4(v, 1)
+    for (int32_t idx = 0; idx < (int32_t)n; idx++) {
+        // PrepareForDenoise (svgf_impl.h:119-144)
+        const v4 c = contribs[idx];
+        v4 contrib = c;
+        svgf::operator/=(contrib, c.w);
+        if (dst->frame == 0) {
+            float lum = luminance(contrib.x, contrib.y, contrib.z);
+            v4& mt = P.cur(svgf::MomentTemporalWeight)[idx];
+            mt.x += lum * lum; mt.y += lum; mt.z += 1;
+            v4& cv = P.cur(svgf::ColorVariance)[idx];
+            cv = v4(contrib.x, contrib.y, contrib.z, cv.w);
         }
+        P.temporary_color_buffer[idx] = c;
+        put(0, idx, v4(c.x, c.y, c.z, 1));      // Film::put(x, y, vec3) -> vec4(v, 1)
     }
 
     if (compute_motion) {
@@ -478,6 +471,74 @@ void orc_svgf_render(void* h, const atn_scene_desc* scene, const atn_camera_para
         for (size_t i = 0; i < n; i++) { cv[i].z = P.temporary_color_buffer[i].z; cv[i].y = P.temporary_color_buffer[i].y; cv[i].x = P.temporary_color_buffer[i].x; }
     }
     P.curr_aov_pos = 1 - P.curr_aov_pos;
+}
+
+// SVGFRenderer::OnRender (svgf.cpp:452-637).  `film` receives what dst.buffer holds when OnRender returns (Film::put,
+// film.cpp:33-45): the last a-trous iteration's albedo-multiplied colour.  `stage_out` (may be null): 3 x vec4[w*h] =
+// the values put after the path pass, after the temporal pass and after the variance pass.
+// compute_motion != 0: fill motion_depth_buffer from the primary hits (ComputeMotionDepth) instead of an external buffer.
+void orc_svgf_render(void* h, const atn_scene_desc* scene, const atn_camera_param* camera,
+    const uint32_t* seeds, uint32_t n_seeds, const orc_destination* dst, int32_t compute_motion,
+    atn_vec4* film, atn_vec4* stage_out)
+{
+    auto& P = *static_cast<svgf::Params*>(h);
+    Scene ctxt(scene);
+    const int32_t width = dst->width, height = dst->height;
+    const uint32_t samples = (uint32_t)dst->sample;
+    int32_t maxDepth = dst->maxDepth;
+    int32_t rrDepth = dst->russianRouletteDepth;
+    if (rrDepth > maxDepth) rrDepth = maxDepth - 1;         // svgf.cpp:423-425
+    P.InitBuffers(width, height);
+    P.mtxs.Reset(*camera);
+    const m4 W2C = P.mtxs.GetW2C();
+    const size_t n = (size_t)width * height;
+    std::vector<v4> contribs(n);
+    if (dst->nthreads > 0) omp_set_num_threads(dst->nthreads);
+
+#pragma omp parallel for
+    for (int32_t y = 0; y < height; y++) {
+        for (int32_t x = 0; x < width; x++) {
+            int32_t idx = y * width + x;
+            PathState path;             // path_host_.Clear(): contrib/attrib/throughput zeroed every frame
+            path.samples = 0;
+            Ray ray; ShadowRay shadow_ray;
+            for (uint32_t i = 0; i < samples; i++) {
+                const uint32_t rnd = seeds[idx % n_seeds];
+                GeneratePath(ray, x, y, (int32_t)i, dst->frame, path, *camera, rnd);
+                path.contrib = v3(0);
+                svgf::ExecRendering(path, ray, shadow_ray, x, y, width, height, ctxt, *camera, maxDepth, rrDepth, W2C,
+                    P.cur(svgf::NormalDepth)[idx], P.cur(svgf::AlbedoMeshId)[idx], P.primary_position[idx], nullptr);
+                if (isInvalidColor(path.contrib)) continue;
+                if (path.is_terminated) break;
+            }
+            contribs[idx] = v4(path.contrib, path.samples);
+        }
+    }
+    svgf_filter_passes(P, camera, dst, compute_motion, contribs, film, stage_out);
+}
+
+// The filter half alone on planes the caller passes: the twin of atn_svgf_upload (contribs, normal_depth, albedo_meshid,
+// primary_position into the current set) followed by atn_svgf_denoise -- buffers initialised like a fresh renderer's where they
+// do not exist yet, the camera matrices advanced, then every pass of svgf_filter_passes (frame 0: PrepareForDenoise accumulates
+// into the initial (0, 0, 0, 1) texels).  Outputs as orc_svgf_render's.
+void orc_svgf_denoise(void* h, const atn_camera_param* camera, const orc_destination* dst, int32_t compute_motion,
+    const atn_vec4* contribs_in, const atn_vec4* normal_depth, const atn_vec4* albedo_meshid, const atn_vec4* primary_position,
+    atn_vec4* film, atn_vec4* stage_out)
+{
+    auto& P = *static_cast<svgf::Params*>(h);
+    P.InitBuffers(dst->width, dst->height);
+    P.mtxs.Reset(*camera);
+    const size_t n = (size_t)dst->width * dst->height;
+    std::vector<v4> contribs(n);
+    auto& nd = P.cur(svgf::NormalDepth); auto& am = P.cur(svgf::AlbedoMeshId);
+    for (size_t i = 0; i < n; i++) {
+        contribs[i] = v4(contribs_in[i].x, contribs_in[i].y, contribs_in[i].z, contribs_in[i].w);
+        nd[i] = v4(normal_depth[i].x, normal_depth[i].y, normal_depth[i].z, normal_depth[i].w);
+        am[i] = v4(albedo_meshid[i].x, albedo_meshid[i].y, albedo_meshid[i].z, albedo_meshid[i].w);
+        P.primary_position[i] = v4(primary_position[i].x, primary_position[i].y, primary_position[i].z, primary_position[i].w);
+    }
+    if (dst->nthreads > 0) omp_set_num_threads(dst->nthreads);
+    svgf_filter_passes(P, camera, dst, compute_motion, contribs, film, stage_out);
 }
 
 // idaten::LBVHBuilder::build with threadedBvhNodes (LBVHBuilder.cu:812-833): the node array in the reference's order

@@ -258,6 +258,38 @@ class Svgf:
         self.shape = (height, width, 4)
         return (film, st) if stages else film
 
+    def denoise(self, cam, contribs, normal_depth, albedo_meshid, primary_position, frame=0, compute_motion=False, stages=False,
+                nthreads=0):
+        """The filter passes alone on the caller's planes, float32 [h, w, 4] each: the twin of the product's svgf_upload of these
+        four planes followed by svgf_denoise.  Returns what render returns."""
+        planes = [np.ascontiguousarray(p, np.float32) for p in (contribs, normal_depth, albedo_meshid, primary_position)]
+        height, width = planes[0].shape[:2]
+        if any(p.shape != (height, width, 4) for p in planes):
+            raise ValueError("denoise: four [h, w, 4] planes of one size")
+        film = np.zeros((height, width, 4), np.float32)
+        st = np.zeros((3, height, width, 4), np.float32) if stages else None
+        d = Destination(width, height, 1, 1, 1, frame, 0, nthreads)
+        lib().orc_svgf_denoise(self._h, C.c_void_p(cam.ctypes.data), C.byref(d), C.c_int32(1 if compute_motion else 0),
+                               *[C.c_void_p(p.ctypes.data) for p in planes],
+                               C.c_void_p(film.ctypes.data), C.c_void_p(st.ctypes.data) if stages else None)
+        self.n = width * height
+        self.shape = (height, width, 4)
+        return (film, st) if stages else film
+
+    def set_buffer(self, name, data):
+        """The inverse of buffer(): overwrite one plane (BUFFERS) with float32 [h, w, 4], e.g. the history both sides start from."""
+        data = np.ascontiguousarray(data, np.float32)
+        height, width = data.shape[:2]
+        if data.shape != (height, width, 4):
+            raise ValueError("set_buffer: a [h, w, 4] plane")
+        lib().orc_svgf_set_buffer.restype = C.c_int
+        r = lib().orc_svgf_set_buffer(self._h, C.c_int32(self.BUFFERS[name]), C.c_int32(width), C.c_int32(height),
+                                      C.c_void_p(data.ctypes.data))
+        if r < 0:
+            raise ValueError(name)
+        self.n = width * height
+        self.shape = (height, width, 4)
+
     def buffer(self, name):
         out = np.zeros(self.shape, np.float32)
         r = lib().orc_svgf_get_buffer(self._h, C.c_int32(self.BUFFERS[name]), C.c_void_p(out.ctypes.data))

@@ -48,12 +48,13 @@ def _same_hit(gi, oi):
     return (gi["mtrl"] == oi["mtrl"]) & (gi["mesh"] == oi["mesh"]) & np.all(gi["p"] == oi["p"], axis=-1) & (gi["hit"] == oi["hit"])
 
 
-@pytest.mark.parametrize("which", ["cornell", "sponza"])
+@pytest.mark.parametrize("which", ["cornell", "sponza", "cornell-37x21", "cornell-100x52"])
 def test_stage_parity(gpu, rs, orc, ml_cornell, ml_sponza, which):
     """Reservoir y and M exact, W within 1e-4 relative after the initial, temporal and spatial passes, and the CMJ dimension after
-    bounce 0, on pixels whose primary hit agrees -- four consecutive frames of mode 1 (frames 2 and 3 run the temporal pass)."""
-    scene = ml_cornell if which == "cornell" else ml_sponza
-    w, h = (64, 48) if which == "cornell" else (96, 54)
+    bounce 0, on pixels whose primary hit agrees -- four consecutive frames of mode 1 (frames 2 and 3 run the temporal pass).
+    37 x 21 and 100 x 52: frames whose edges line up with no tile of the reuse passes."""
+    scene = ml_sponza if which == "sponza" else ml_cornell
+    w, h = tuple(int(v) for v in which.split("-")[1].split("x")) if "-" in which else (64, 48) if which == "cornell" else (96, 54)
     r, o, c, seeds = _pair(gpu, rs, orc, scene, w, h)
     r.restir_capture(True)
     r.restir_set_options(1, 8)

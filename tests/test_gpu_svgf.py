@@ -30,13 +30,14 @@ def _setup(gpu, orc, scene, cam, w, h):
     return c, orc.init_sampler(w, h, 0)
 
 
-@pytest.mark.parametrize("which", ["sponza", "cornell"])
+@pytest.mark.parametrize("which", ["sponza", "cornell", "cornell-37x21", "cornell-100x52"])
 def test_svgf_filter_passes_on_equal_inputs(gpu, orc, sponza, cornell, which):
     """The filter passes proper: both sides get the SAME noisy frame and G-buffer (the oracle's path pass, uploaded
     through atn_svgf_upload), frame after frame, each side keeping its own history.  What differs is then only
-    powf/expf/sqrt rounding inside the passes."""
+    powf/expf/sqrt rounding inside the passes.  The two ragged Cornell sizes: scene-driven planes on frames whose edges line up
+    with no tile and no a-trous pixel group (tests/test_gpu_svgf_edges.py holds every pixel of synthetic planes)."""
     fs, cam = sponza if which == "sponza" else cornell
-    w, h = 192, 108
+    w, h = tuple(int(v) for v in which.split("-")[1].split("x")) if "-" in which else (192, 108)
     c, seeds = _setup(gpu, orc, fs, cam, w, h)
     sv = orc.Svgf()
     try:
@@ -342,6 +343,16 @@ def test_film_order_survives_svgf_frames_between_renders(sponza):
 
 
 def test_atrous_four_pixel_kernel_against_the_one_pixel_kernel(sponza):
+    _atrous_four_pixel_kernel_against_the_one_pixel_kernel(sponza, 192, 108)
+
+
+def test_atrous_four_pixel_kernel_against_the_one_pixel_kernel_ragged_frame(sponza):
+    """The same comparison at 100 x 52: neither dimension is a multiple of 8 or of the pixel-group width 2 * 2^i of levels 3 and 4,
+    so the four-pixel kernel's groups hang over the right and the top edge at every level (same bounds)."""
+    _atrous_four_pixel_kernel_against_the_one_pixel_kernel(sponza, 100, 52)
+
+
+def _atrous_four_pixel_kernel_against_the_one_pixel_kernel(sponza, w, h):
     """the default a-trous kernel (k_svgf_atrous4, four pixels per thread) sums a pixel's 24 weighted taps in LATTICE
     order, the one-pixel kernel (k_svgf_atrous, ATEN_AMD_SVGF_ATROUS4=0) in the reference's ring order (svgf_impl.h:693-726):
     same taps, same weights, another association of the float sums.  Both kernels on IDENTICAL planes, frame after frame (each
@@ -351,7 +362,6 @@ def test_atrous_four_pixel_kernel_against_the_one_pixel_kernel(sponza):
     from aten_amd.renderer import PathTracing
     from aten_amd.scene.camera import create_camera
     fs, cam = sponza
-    w, h = 192, 108
     ctx = {}
     old = os.environ.get("ATEN_AMD_SVGF_ATROUS4")
     try:

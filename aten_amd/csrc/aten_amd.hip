@@ -31,38 +31,9 @@
 #include "device/taa.hpp"
 #include "host/scene_upload.hpp"
 #include "host/ibl_precompute.hpp"
+#include "host/devbuf.hpp"
 
 namespace atn {
-
-#define ATN_HIP(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) { return fail(ATN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { release(); }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; n = 0; } }
-    hipError_t resize(size_t count)
-    {
-        if (count <= n && p) return hipSuccess;
-        release();
-        if (count == 0) return hipSuccess;
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(T) + 256);     // slack: the walk's pair fetch reads 32 B past a record
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
-    hipError_t upload(const std::vector<T>& v, hipStream_t s)
-    {
-        hipError_t e = resize(v.size() ? v.size() : 1);
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
-    }
-};
 
 // ---- which streams really run side by side ---------------------------------------------------------------------------
 // HIP streams are multiplexed onto a few hardware queues (4 by default; under RCCL that number holds whatever
@@ -95,21 +66,103 @@ inline bool streams_run_side_by_side(hipStream_t a, hipStream_t b, bool& ok)
     return false;
 }
 
-class PathTracing {
+// Frames in flight (atn_set_frames_in_flight): everything a frame's kernels write except the film lives in a BANK --
+// path state, queues, counters, tile buffer, and the streams / events the frame runs on.  PathTracing derives from Bank: its
+// base IS the current bank; render() rotates it with the spare banks, so frame f + 1 is enqueued on another stream while frame
+// f's launch tails (a few long rays keep a handful of waves alive at the end of every trace launch) still run.
+// Only the film orders consecutive frames: a frame's k_gather waits for the previous frame's.
+struct Bank {
+    static constexpr int kMaxBatches = 8;
+    DevBuf<float4> ray_o, ray_d, thr, contrib, isect, sh_o, sh_d, sh_c, accum, tile_out;
+    DevBuf<float4> sh_w;                    // deferred NEE: {incoming direction, sampler dimension} of the vertex behind a slot's shadow ray
+    DevBuf<uint32_t> nee_reached;           // deferred NEE: per slot, the shadow ray reached its light (isect then holds two planes of hit records); these
+                                            // and isect's second plane exist only in a bank that has run a deferred frame (run_paths)
+    DevBuf<float4> pend;                    // path regeneration: a pixel's previous sample while its last shadow ray is in flight
+    DevBuf<float4> rg_frames;               // path regeneration: [frames of the burst][slots] pixel values on their way to the film (k_regen_end)
+    DevBuf<uint32_t> done, queue0, queue1, shadow_q, counters;
+    DevBuf<uint32_t> rg_counters;           // path regeneration: [3][rg_stages + 3] live paths, shadow rays, fetch cursor of every stage (from stage -1)
+    DevBuf<uint32_t> rg_regions;            // path regeneration: what a shade launch hands to the compaction: [2][slots + chunk] entries, counts per chunk and group
+    int32_t rg_stages = 0;                  // stages the counters hold (of the bank's last regenerated burst: atn_regen_stage_counts)
+    DevBuf<float> ns_depth_s, ns_lit, ns_depth, ns_plane;      // the NPR shadow pre-pass's planes of the bank's last mode-1 frame
+    uint32_t ns_slots = 0;
+    int32_t ns_w = 0, ns_h = 0;
+    uint32_t n_slots = 0;
+    int32_t counters_depth = 0;
+    uint64_t bank_epoch = 0;        // the scene update this bank's stream is behind (wait_scene_epoch)
+    int scene_set = 0;              // id of the scene set this bank's last frame read
+    DevEvent ev_read[3];            // [scene set id]: the last frame of this bank that read that set has finished with the scene
+    DevStream stream, bstream[kMaxBatches];
+    DevEvent ev_fork, ev_join[kMaxBatches], ev_gather;      // ev_gather: the bank's "film updated" event
+    int batch_streams_checked = 0;  // bstream[0 .. n-1] of this bank are known to be pairwise concurrent
+};
+
+// A caller's motion/depth plane (PathTracing::set_motion_depth): SVGF and ReSTIR keep one each.
+struct MotionDepth {
+    DevBuf<float4> buf;
+    bool is_set = false;
+    size_t count = 0;       // elements of the last set / upload (buf.n is the capacity)
+};
+
+inline void mat_mul(const float* a, const float* b, float* out)        // mat4::operator*=, mat4.h:140-156
+{
+    float tmp[16];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            float acc = 0.0f;
+            for (int k = 0; k < 4; k++) acc += a[4 * i + k] * b[4 * k + j];
+            tmp[4 * i + j] = acc;
+        }
+    std::memcpy(out, tmp, sizeof(tmp));
+}
+
+// MatricesForRendering (pt_params.h:150-185): SVGF and ReSTIR keep one each.
+struct FrameMatrices {
+    float W2V[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    float V2C[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    float prevW2V[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    void reset_identity() { *this = FrameMatrices(); }
+    // MatricesForRendering::Reset = Camera::ComputeCameraMatrices: mat4::lookat(origin, center, up) and
+    // mat4::perspective(znear, zfar, vfov, aspect) written into the existing matrices (mat4.h:457-513)
+    void advance(const atn_camera_param& camera)
+    {
+        std::memcpy(prevW2V, W2V, 16 * sizeof(float));
+        const float* e = camera.origin; const float* at = camera.center; const float* up = camera.up;
+        float z[3] = { e[0] - at[0], e[1] - at[1], e[2] - at[2] };
+        float il = 1.0f / std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);        // glm::normalize = v * inversesqrt(dot(v, v))
+        z[0] *= il; z[1] *= il; z[2] *= il;
+        float x[3] = { up[1] * z[2] - z[1] * up[2], up[2] * z[0] - z[2] * up[0], up[0] * z[1] - z[0] * up[1] };
+        il = 1.0f / std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+        x[0] *= il; x[1] *= il; x[2] *= il;
+        const float y[3] = { z[1] * x[2] - x[1] * z[2], z[2] * x[0] - x[2] * z[0], z[0] * x[1] - x[0] * z[1] };
+        float* m = W2V;
+        m[0] = x[0]; m[4] = y[0]; m[8] = z[0];
+        m[1] = x[1]; m[5] = y[1]; m[9] = z[1];
+        m[2] = x[2]; m[6] = y[2]; m[10] = z[2];
+        m[3] = -(x[0] * e[0] + x[1] * e[1] + x[2] * e[2]);
+        m[7] = -(y[0] * e[0] + y[1] * e[1] + y[2] * e[2]);
+        m[11] = -(z[0] * e[0] + z[1] * e[1] + z[2] * e[2]);
+        m[15] = 1;
+        const float fH = 1 / std::tan((3.14159265358979323846F * (camera.vfov) / 180.0F) * 0.5f);
+        const float fW = fH / camera.aspect;
+        float* p = V2C;
+        p[0] = fW; p[5] = fH;
+        p[10] = camera.zfar / (camera.znear - camera.zfar);
+        p[11] = camera.znear * camera.zfar / (camera.znear - camera.zfar);
+        p[14] = -1.0f; p[15] = 0.0f;
+    }
+};
+
+class PathTracing : public Bank {
 public:
     std::string last_error;
     int device = 0;
-    hipStream_t stream = nullptr;
     // A frame's paths are cut into n_batches independent batches (contiguous slot ranges = groups of screen tiles),
     // each with its own queues and counters, and every batch runs its gen -> [trace, shade, shadow] x depth sequence on
     // its own stream.  A trace launch has a size-independent part of ~0.2 ms (ramp-up, and a tail in which a few rays
     // that visit 10x the mean number of nodes keep a handful of waves alive); with several batches in flight the other
     // batches' kernels fill the machine meanwhile.  Measured (sponza_lod 1080p): 6.83 -> 6.58 ms
     // on the whole frame, 4.35 -> 3.71 ms on half of it (the 2-GPU shard), no gain below ~200 K paths per batch.
-    static constexpr int kMaxBatches = 8;
     static constexpr int kMaxShards = 64;       // screen shards of one node (atn_mgpu_*)
-    hipStream_t bstream[kMaxBatches] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxBatches] = {};
     int n_batches = 3;
     bool batches_forced = false;    // ATEN_AMD_BATCHES / atn_set_path_batches given: no size policy on top
     bool fuse_traces = true;    // shadow(b) + closest(b+1) in one launch (k_trace_fused); ATEN_AMD_FUSE=0 disables (experiments)
@@ -234,72 +287,27 @@ public:
     DevBuf<uint32_t> seeds;
     uint32_t n_seeds = 0;
 
-    // path state
-    DevBuf<float4> ray_o, ray_d, thr, contrib, isect, sh_o, sh_d, sh_c, accum, film, tile_out;
-    DevBuf<float4> sh_w;                    // deferred NEE: {incoming direction, sampler dimension} of the vertex behind a slot's shadow ray
-    DevBuf<uint32_t> nee_reached;           // deferred NEE: per slot, the shadow ray reached its light (isect then holds two planes of hit records); these
-                                            // and isect's second plane exist only in a bank that has run a deferred frame (run_paths)
+    // what of the path state is not per bank (the rest: struct Bank)
+    DevBuf<float4> film;
     DevBuf<unsigned long long> nee_stats;   // deferred NEE: {shadow rays cast, rays that reached the light} of the deferred frames since the last reset
-    DevBuf<float4> pend;                    // path regeneration: a pixel's previous sample while its last shadow ray is in flight
-    DevBuf<float4> rg_frames;               // path regeneration: [frames of the burst][slots] pixel values on their way to the film (k_regen_end)
-    DevBuf<uint32_t> done, queue0, queue1, shadow_q, counters;
-    DevBuf<uint32_t> rg_counters;           // path regeneration: [3][rg_stages + 3] live paths, shadow rays, fetch cursor of every stage (from stage -1)
-    DevBuf<uint32_t> rg_regions;            // path regeneration: what a shade launch hands to the compaction: [2][slots + chunk] entries, counts per chunk and group
-    int32_t rg_stages = 0;                  // stages the counters hold (of the bank's last regenerated burst: atn_regen_stage_counts)
     DevBuf<unsigned long long> stats;
     DevBuf<uint32_t> cost, cost_film;       // per-slot / per-pixel {node visits, triangle tests} of the last count_stats frame
     int32_t cost_w = 0, cost_h = 0;
     int32_t film_w = 0, film_h = 0;
     int32_t rank = 0, world = 1;
-    uint32_t n_slots = 0;
-    int32_t counters_depth = 0;
 
-    // Frames in flight (atn_set_frames_in_flight): everything a frame's kernels write except the film lives in a BANK --
-    // path state, queues, counters, tile buffer, and the streams / events the frame runs on.  The members above ARE the
-    // current bank; render() rotates them with the spare banks, so frame f + 1 is enqueued on another stream while frame
-    // f's launch tails (a few long rays keep a handful of waves alive at the end of every trace launch) still run.
-    // Only the film orders consecutive frames: a frame's k_gather waits for the previous frame's.
     static constexpr int kMaxInFlight = 4;      // (5 / 6 / 8 banks with 8 hardware queues: no gain, profiles/r04_variants_shade_waves.txt)
-    struct Bank {
-        DevBuf<float4> ray_o, ray_d, thr, contrib, isect, sh_o, sh_d, sh_c, sh_w, accum, tile_out, pend, rg_frames;
-        DevBuf<uint32_t> done, queue0, queue1, shadow_q, nee_reached, counters, rg_counters, rg_regions;
-        DevBuf<float> ns_depth_s, ns_lit, ns_depth, ns_plane;      // the NPR shadow pre-pass's planes of the bank's last mode-1 frame
-        uint32_t ns_slots = 0;
-        int32_t ns_w = 0, ns_h = 0;
-        int32_t rg_stages = 0;
-        uint32_t n_slots = 0;
-        int32_t counters_depth = 0;
-        uint64_t bank_epoch = 0;
-        int scene_set = 0;
-        hipEvent_t ev_read[3] = {};     // [scene set id]: the last frame of this bank that read that set has finished with the scene
-        hipStream_t stream = nullptr, bstream[kMaxBatches] = {};
-        hipEvent_t ev_fork = nullptr, ev_join[kMaxBatches] = {}, ev_gather = nullptr;
-        int batch_streams_checked = 0;
-    };
     Bank spare[kMaxInFlight - 1];
     int frames_in_flight = 1, n_spare_ready = 0;
     uint64_t frame_seq = 0;
-    hipEvent_t ev_gather = nullptr;         // the current bank's "film updated" event
     // the film is one running mean shared by every bank: its last writer (a render()'s k_gather, or reset()'s clear).  One
     // event owned by the context, NOT by a bank -- svgf_render rotates banks without writing the film, so "the previous
     // bank's ev_gather" is not the film's last writer.  (A wait refers to the record that precedes it; re-recording is fine.)
-    hipEvent_t ev_film = nullptr;
+    DevEvent ev_film;
     bool film_pending = false;
 
-    void swap_bank(Bank& b)
-    {
-        ray_o.swap(b.ray_o); ray_d.swap(b.ray_d); thr.swap(b.thr); contrib.swap(b.contrib); isect.swap(b.isect);
-        sh_o.swap(b.sh_o); sh_d.swap(b.sh_d); sh_c.swap(b.sh_c); sh_w.swap(b.sh_w); nee_reached.swap(b.nee_reached); accum.swap(b.accum); tile_out.swap(b.tile_out);
-        done.swap(b.done); queue0.swap(b.queue0); queue1.swap(b.queue1); shadow_q.swap(b.shadow_q);
-        counters.swap(b.counters); pend.swap(b.pend); rg_frames.swap(b.rg_frames); rg_counters.swap(b.rg_counters); rg_regions.swap(b.rg_regions); std::swap(rg_stages, b.rg_stages);
-        std::swap(n_slots, b.n_slots); std::swap(counters_depth, b.counters_depth); std::swap(bank_epoch, b.bank_epoch); std::swap(bank_scene_set, b.scene_set);
-        for (int k = 0; k < 3; k++) std::swap(ev_read[k], b.ev_read[k]);
-        std::swap(stream, b.stream); std::swap(ev_fork, b.ev_fork); std::swap(ev_gather, b.ev_gather);
-        for (int k = 0; k < kMaxBatches; k++) { std::swap(bstream[k], b.bstream[k]); std::swap(ev_join[k], b.ev_join[k]); }
-        std::swap(batch_streams_checked, b.batch_streams_checked);
-        ns_depth_s.swap(b.ns_depth_s); ns_lit.swap(b.ns_lit); ns_depth.swap(b.ns_depth); ns_plane.swap(b.ns_plane);
-        std::swap(ns_slots, b.ns_slots); std::swap(ns_w, b.ns_w); std::swap(ns_h, b.ns_h);
-    }
+    // the whole bank at once: a member added to Bank rotates with it
+    void swap_bank(Bank& b) { std::swap(static_cast<Bank&>(*this), b); }
 
     int set_frames_in_flight(int n)
     {
@@ -309,12 +317,12 @@ public:
         if (rc) return rc;
         for (; n_spare_ready < n - 1; n_spare_ready++) {
             Bank& b = spare[n_spare_ready];
-            ATN_HIP(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
-            ATN_HIP(hipEventCreateWithFlags(&b.ev_fork, hipEventDisableTiming));
-            ATN_HIP(hipEventCreateWithFlags(&b.ev_gather, hipEventDisableTiming));
+            ATN_HIP(hipStreamCreateWithFlags(&b.stream.h, hipStreamNonBlocking));
+            ATN_HIP(hipEventCreateWithFlags(&b.ev_fork.h, hipEventDisableTiming));
+            ATN_HIP(hipEventCreateWithFlags(&b.ev_gather.h, hipEventDisableTiming));
             for (int k = 0; k < kMaxBatches; k++) {
-                ATN_HIP(hipStreamCreateWithFlags(&b.bstream[k], hipStreamNonBlocking));
-                ATN_HIP(hipEventCreateWithFlags(&b.ev_join[k], hipEventDisableTiming));
+                ATN_HIP(hipStreamCreateWithFlags(&b.bstream[k].h, hipStreamNonBlocking));
+                ATN_HIP(hipEventCreateWithFlags(&b.ev_join[k].h, hipEventDisableTiming));
             }
         }
         // the spare scene sets are only kept current while ticks flip through them: an in-place update (one frame in
@@ -364,10 +372,10 @@ public:
         if (n <= bank_streams_checked) return ATN_OK;
         hipStream_t* st[kMaxInFlight + 1];
         int m = 0;
-        st[m++] = &stream;
-        if (side_stream) st[m++] = &side_stream;
+        st[m++] = &stream.h;
+        if (side_stream) st[m++] = &side_stream.h;
         const int fixed = m;
-        for (int i = 1; i < n; i++) st[m++] = &spare[i - 1].stream;
+        for (int i = 1; i < n; i++) st[m++] = &spare[i - 1].stream.h;
         const int first = fixed + (bank_streams_checked > 1 ? bank_streams_checked - 1 : 0);
         const int rc = separate_streams(st, m, first);
         if (rc) return rc;
@@ -379,7 +387,6 @@ public:
     // never fork.  The probe times spin kernels against each other, so it runs on an IDLE device (quiesce: the other banks'
     // frames would read as a clash and cost stream re-creations in the middle of a frame); the count of probed streams is
     // recorded only when the probe succeeded, and a later, larger batch count probes the additional streams.
-    int batch_streams_checked = 0;      // bstream[0 .. n-1] of this bank are known to be pairwise concurrent
     int separate_batch_streams(int nb)
     {
         const int n = nb < 3 ? nb : 3;        // the size policy never uses more than two; three when forced
@@ -387,7 +394,7 @@ public:
         int rc = quiesce();
         if (rc) return rc;
         hipStream_t* st[kMaxBatches];
-        for (int i = 0; i < n; i++) st[i] = &bstream[i];
+        for (int i = 0; i < n; i++) st[i] = &bstream[i].h;
         rc = separate_streams(st, n, batch_streams_checked > 1 ? batch_streams_checked : 1);
         if (rc) return rc;
         batch_streams_checked = n;
@@ -395,7 +402,7 @@ public:
     }
 
     // the caller's side stream (atn_side_stream): concurrent with every bank stream if a queue is left
-    hipStream_t side_stream = nullptr;
+    DevStream side_stream;
     hipStream_t get_side_stream()
     {
         // handed out once: the caller holds the handle (a torch ExternalStream, a C++ app's own work); banks created later
@@ -413,16 +420,16 @@ public:
         };
         std::vector<hipStream_t> rejected;
         for (int t = 0; t < kStreamTries; t++) {
-            if (!side_stream && hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking) != hipSuccess) { side_stream = nullptr; break; }
+            if (!side_stream && hipStreamCreateWithFlags(&side_stream.h, hipStreamNonBlocking) != hipSuccess) { side_stream.h = nullptr; break; }
             bool ok = true;
             const bool clash = env_probe_streams ? clashes(side_stream, ok) : false;
             if (!ok) break;
             if (!clash || t == kStreamTries - 1) break;
             rejected.push_back(side_stream);
-            side_stream = nullptr;
+            side_stream.h = nullptr;
         }
         // out of tries (fewer queues than banks + 1): any stream will do
-        if (!side_stream && !rejected.empty()) { side_stream = rejected.back(); rejected.pop_back(); }
+        if (!side_stream && !rejected.empty()) { side_stream.h = rejected.back(); rejected.pop_back(); }
         for (auto r : rejected) (void)hipStreamDestroy(r);
         return side_stream;
     }
@@ -467,8 +474,7 @@ public:
     SceneSet alt[kMaxSceneSets - 1];
     int n_alt = 0;                                  // allocated sets besides the current one
     bool frame_since_update = true, scene_in_place = false;
-    int cur_set = 0, bank_scene_set = 0;            // ids; bank_scene_set: the set this bank's last frame read (travels with the bank)
-    hipEvent_t ev_read[3] = {};                     // the current bank's (see Bank::ev_read)
+    int cur_set = 0;                                // id (Bank::scene_set: the set a bank's last frame read)
     uint64_t cur_tick = 0, tick_counter = 0;
     std::vector<SceneRange> log_now;                // what the updates since the last flip wrote into the current set
     struct TickLog { uint64_t tick; std::vector<SceneRange> ranges; };
@@ -515,7 +521,7 @@ public:
     DevBuf<float4> gm_vtx, gm_mtx;
     uint32_t gm_mtx_quads = 0;                  // matrices rows the history holds (scene.mtx_quads when it was last made equal)
     std::vector<SceneRange> gm_dirty;           // written since the last mode-2 frame
-    hipEvent_t gm_ev = nullptr;                 // the last mode-2 frame is done with the history
+    DevEvent gm_ev;                 // the last mode-2 frame is done with the history
     DevBuf<float4> gm_ids[2], gm_rs_ids;        // ids planes: SVGF's per hand-over slot, ReSTIR's
     float4* gm_capture = nullptr;               // run_paths: where the frame's bounce-0 hit records go (null: not captured)
     bool gm_sv_ids[2] = { false, false }, gm_rs_has_ids = false;       // the plane holds a frame's ids
@@ -581,7 +587,7 @@ public:
         }
         if (scene_in_place) return fail(ATN_ERR_UNSUPPORTED, "geometry motion needs to see every scene update: not once the caller writes the scene arrays itself (atn_scene_device_arrays)");
         if (gm_on) return ATN_OK;
-        if (!gm_ev) ATN_HIP(hipEventCreateWithFlags(&gm_ev, hipEventDisableTiming));
+        if (!gm_ev) ATN_HIP(hipEventCreateWithFlags(&gm_ev.h, hipEventDisableTiming));
         gm_on = true;
         return has_scene ? gm_reset_history() : ATN_OK;
     }
@@ -692,17 +698,17 @@ public:
         return ATN_OK;
     }
 
-    hipEvent_t ev_scene = nullptr, ev_stage = nullptr;
-    hipStream_t scene_stream = nullptr;             // updates run here when frames are in flight: not behind the newest frame
+    DevEvent ev_scene, ev_stage;
+    DevStream scene_stream;            // updates run here when frames are in flight: not behind the newest frame
     hipStream_t upd = nullptr;                      // the stream of the update in progress (scene_stream, or `stream` with one frame in flight)
-    uint64_t scene_epoch = 0, bank_epoch = 0;       // bank_epoch travels with the bank (swap_bank)
+    uint64_t scene_epoch = 0;                       // (Bank::bank_epoch: the update a bank's stream is behind)
     bool stage_busy = false;
     char* stage_p = nullptr;
     size_t stage_cap = 0, stage_used = 0;
 
     int begin_scene_update(size_t stage_bytes)
     {
-        if (!ev_scene) { ATN_HIP(hipEventCreateWithFlags(&ev_scene, hipEventDisableTiming)); ATN_HIP(hipEventCreateWithFlags(&ev_stage, hipEventDisableTiming)); }
+        if (!ev_scene) { ATN_HIP(hipEventCreateWithFlags(&ev_scene.h, hipEventDisableTiming)); ATN_HIP(hipEventCreateWithFlags(&ev_stage.h, hipEventDisableTiming)); }
         if (stage_busy) { ATN_HIP(hipEventSynchronize(ev_stage)); stage_busy = false; }       // the previous update's copies
         stage_used = 0;
         if (stage_bytes > stage_cap) {
@@ -712,7 +718,7 @@ public:
             ATN_HIP(hipHostMalloc((void**)&stage_p, cap, hipHostMallocDefault));
             stage_cap = cap;
         }
-        if (frames_in_flight > 1 && !scene_stream) ATN_HIP(hipStreamCreateWithFlags(&scene_stream, hipStreamNonBlocking));
+        if (frames_in_flight > 1 && !scene_stream) ATN_HIP(hipStreamCreateWithFlags(&scene_stream.h, hipStreamNonBlocking));
         upd = frames_in_flight > 1 ? scene_stream : stream;
         if (frames_in_flight > 1 && n_spare_ready > 0 && !scene_in_place) {
             // a frame may be reading the current set: write the other one.  (Several updates in a row -- geometry, LBVH,
@@ -753,8 +759,8 @@ public:
     int record_scene_read()
     {
         ATN_HIP(hipEventRecord(ev_gather, stream));
-        hipEvent_t& e = ev_read[bank_scene_set];
-        if (!e) ATN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        DevEvent& e = ev_read[scene_set];
+        if (!e) ATN_HIP(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
         ATN_HIP(hipEventRecord(e, stream));
         return ATN_OK;
     }
@@ -763,7 +769,7 @@ public:
     {
         if (bank_epoch != scene_epoch && ev_scene) ATN_HIP(hipStreamWaitEvent(stream, ev_scene, 0));
         bank_epoch = scene_epoch;
-        bank_scene_set = cur_set;
+        scene_set = cur_set;
         frame_since_update = true;
         return ATN_OK;
     }
@@ -771,7 +777,7 @@ public:
     // profiling
     float k_ms[ATN_K_COUNT] = {};
     uint32_t k_launches[ATN_K_COUNT] = {};
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<DevEvent> ev_pool;
     struct Span { int kind; size_t e0, e1; };
     static constexpr size_t kMaxSpans = 8192;
     std::vector<Span> spans;
@@ -789,13 +795,13 @@ public:
         if (device_ordinal < 0 || device_ordinal >= n) return fail(ATN_ERR_INVALID_ARG, "device ordinal out of range");
         device = device_ordinal;
         ATN_HIP(hipSetDevice(device));
-        ATN_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        ATN_HIP(hipStreamCreateWithFlags(&stream.h, hipStreamNonBlocking));
         for (int k = 0; k < kMaxBatches; k++) {
-            ATN_HIP(hipStreamCreateWithFlags(&bstream[k], hipStreamNonBlocking));
-            ATN_HIP(hipEventCreateWithFlags(&ev_join[k], hipEventDisableTiming));
+            ATN_HIP(hipStreamCreateWithFlags(&bstream[k].h, hipStreamNonBlocking));
+            ATN_HIP(hipEventCreateWithFlags(&ev_join[k].h, hipEventDisableTiming));
         }
-        ATN_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        ATN_HIP(hipEventCreateWithFlags(&ev_gather, hipEventDisableTiming));
+        ATN_HIP(hipEventCreateWithFlags(&ev_fork.h, hipEventDisableTiming));
+        ATN_HIP(hipEventCreateWithFlags(&ev_gather.h, hipEventDisableTiming));
         // environment switches (README.md "Environment variables": which are supported controls, which are experiment hooks);
         // read once here, never inside a frame
         if (const char* e = std::getenv("ATEN_AMD_FUSE")) fuse_traces = e[0] != '0';
@@ -821,41 +827,10 @@ public:
         return ATN_OK;
     }
 
-    ~PathTracing()
-    {
-        for (auto& e : ev_pool) (void)hipEventDestroy(e);
-        for (int k = 0; k < kMaxBatches; k++) {
-            if (ev_join[k]) (void)hipEventDestroy(ev_join[k]);
-            if (bstream[k]) (void)hipStreamDestroy(bstream[k]);
-        }
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (rs_ev) (void)hipEventDestroy(rs_ev);
-        if (ta_ev) (void)hipEventDestroy(ta_ev);
-        if (gm_ev) (void)hipEventDestroy(gm_ev);
-        if (ao_ev) (void)hipEventDestroy(ao_ev);
-        if (ev_gather) (void)hipEventDestroy(ev_gather);
-        for (auto& e : sv_ev_prepare) if (e) (void)hipEventDestroy(e);
-        if (ev_film) (void)hipEventDestroy(ev_film);
-        if (sv_stream) (void)hipStreamDestroy(sv_stream);
-        for (int i = 0; i < n_spare_ready; i++) {
-            Bank& b = spare[i];
-            for (int k = 0; k < kMaxBatches; k++) {
-                if (b.ev_join[k]) (void)hipEventDestroy(b.ev_join[k]);
-                if (b.bstream[k]) (void)hipStreamDestroy(b.bstream[k]);
-            }
-            if (b.ev_fork) (void)hipEventDestroy(b.ev_fork);
-            if (b.ev_gather) (void)hipEventDestroy(b.ev_gather);
-            for (auto& e : b.ev_read) if (e) (void)hipEventDestroy(e);
-            if (b.stream) (void)hipStreamDestroy(b.stream);
-        }
-        if (stream) (void)hipStreamDestroy(stream);
-        if (side_stream) (void)hipStreamDestroy(side_stream);
-        if (scene_stream) (void)hipStreamDestroy(scene_stream);
-        for (auto& e : ev_read) if (e) (void)hipEventDestroy(e);
-        if (ev_scene) (void)hipEventDestroy(ev_scene);
-        if (ev_stage) (void)hipEventDestroy(ev_stage);
-        if (stage_p) (void)hipHostFree(stage_p);
-    }
+    // Streams, events and buffers go with their wrappers: this class's members in reverse order of declaration (the renderers' state,
+    // the update streams, the spare banks), then the base -- the current bank, its main stream among the last.  hipStreamDestroy and
+    // hipEventDestroy let queued work finish, and every hipFree waits for the device.
+    ~PathTracing() { if (stage_p) (void)hipHostFree(stage_p); }
 
     // ≙ idaten::Renderer::UpdateSceneData, src/libidaten/kernel/renderer.cpp:12-131
     int UpdateSceneData(const atn_scene_desc* s)
@@ -1700,7 +1675,7 @@ public:
             prof_collect();
         }
         if (ev_used + 2 > ev_pool.size()) {
-            for (int i = 0; i < 64; i++) { hipEvent_t e; (void)hipEventCreate(&e); ev_pool.push_back(e); }
+            for (int i = 0; i < 64; i++) { ev_pool.emplace_back(); (void)hipEventCreate(&ev_pool.back().h); }
         }
         spans.push_back(Span{ kind, ev_used, ev_used + 1 });
         (void)hipEventRecord(ev_pool[ev_used], st);
@@ -1864,7 +1839,7 @@ public:
     int record_film_writer()
     {
         if (frames_in_flight <= 1) return ATN_OK;
-        if (!ev_film) ATN_HIP(hipEventCreateWithFlags(&ev_film, hipEventDisableTiming));
+        if (!ev_film) ATN_HIP(hipEventCreateWithFlags(&ev_film.h, hipEventDisableTiming));
         ATN_HIP(hipEventRecord(ev_film, stream));
         film_pending = true;
         return ATN_OK;
@@ -1873,6 +1848,15 @@ public:
     {
         const int rc = frames_in_flight > 1 ? record_scene_read() : ATN_OK;
         return rc ? rc : record_film_writer();
+    }
+    // ... and the film in host memory, if the caller asked for it
+    int end_film_frame(const atn_destination& d, atn_vec4* out_host)
+    {
+        const int rc = end_film_frame();
+        if (rc || !out_host) return rc;
+        ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d.width * d.height * sizeof(float4), hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        return ATN_OK;
     }
 
     // ≙ idaten::PathTracing::render + OnRender (src/libidaten/kernel/pathtracing.cpp:49-153), loop
@@ -2072,13 +2056,7 @@ public:
         regen_launch_end(g_all, stream, pb, fp, ro);
         prof_end(prof);
         ATN_HIP(hipGetLastError());
-        rc = end_film_frame();
-        if (rc) return rc;
-        if (out_host) {
-            ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
-            ATN_HIP(hipStreamSynchronize(stream));
-        }
-        return ATN_OK;
+        return end_film_frame(*d, out_host);
     }
 
     // The shard's pixel slots that lie inside the frame, ascending (kernels.hpp: the items of a burst index it).  Built on the host from
@@ -2128,72 +2106,48 @@ public:
     // SVGF (aten::SVGFRenderer, src/libaten/renderer/svgf/svgf.cpp): frame-persistent state = SVGFParams
     // (svgf_types.h:54-166) + MatricesForRendering (pt_params.h:150-185)
     // ------------------------------------------------------------------------------------------------
-    DevBuf<float4> sv_aov[2][4], sv_scratch, sv_atrous[2], sv_tmp, sv_motion, sv_out, sv_stages;
+    DevBuf<float4> sv_aov[2][4], sv_scratch, sv_atrous[2], sv_tmp, sv_out, sv_stages;
+    MotionDepth sv_motion;
     // what the path pass hands to the filters, two slots so that frame f + 1's path pass can run while frame f is filtered:
     // G-buffer staging (normal+depth, albedo+id), primary hit positions, contributions
     DevBuf<float4> sv_gnd[2], sv_gam[2], sv_primary[2], sv_contribs[2];
     int32_t sv_slot = 0, sv_last_slot = 0;      // slot of the next frame / of the last frame, upload or denoise
-    hipEvent_t sv_ev_prepare[2] = { nullptr, nullptr };     // the prepare pass that consumed slot k has finished
+    DevEvent sv_ev_prepare[2];     // the prepare pass that consumed slot k has finished
     bool sv_prepare_recorded[2] = { false, false };
     float4* sv_cv[2] = { nullptr, nullptr };    // colour+variance of the two AOV sets (the variance pass swaps with sv_spare)
     float4* sv_spare = nullptr;
     int32_t sv_w = 0, sv_h = 0, sv_curr = 0, sv_atrous_iters = 5;
-    bool sv_motion_set = false;
     bool sv_frame_done = false;             // a frame has been rendered / denoised into sv_out at sv_w x sv_h (the display tail's source 0)
     hipStream_t sv_last_fs = nullptr;       // the stream its filter passes ran on
-    hipStream_t sv_stream = nullptr;        // filter stream of pipelined SVGF frames (frames in flight > 1)
+    DevStream sv_stream;        // filter stream of pipelined SVGF frames (frames in flight > 1)
     bool w_or_h_changed(int32_t w, int32_t h) const { return w != sv_w || h != sv_h || w != film_w || h != film_h; }
     DevBuf<float> sv_weight;        // scalar plane of the optional temporal-weight dilation
     int32_t sv_dilate_weight = 0;
-    size_t sv_motion_count = 0;     // elements of the last atn_svgf_set_motion_depth / upload (sv_motion.n is the capacity)
-    float sv_W2V[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-    float sv_V2C[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-    float sv_prevW2V[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    FrameMatrices sv_mtx;
 
-    static void mat_mul(const float* a, const float* b, float* out)        // mat4::operator*=, mat4.h:140-156
+    // ≙ SVGFRenderer::SetMotionDepthBuffer (svgf.cpp:441-450), ReSTIRRenderer::SetMotionDepthBuffer (restir.cpp:472-480) /
+    // ReSTIRPathTracing::SetGBuffer's motion-depth texture
+    int set_motion_depth(MotionDepth& m, const atn_vec4* md, uint32_t n)
     {
-        float tmp[16];
-        for (int i = 0; i < 4; i++)
-            for (int j = 0; j < 4; j++) {
-                float acc = 0.0f;
-                for (int k = 0; k < 4; k++) acc += a[4 * i + k] * b[4 * k + j];
-                tmp[4 * i + j] = acc;
-            }
-        std::memcpy(out, tmp, sizeof(tmp));
+        if (!md || n == 0) return fail(ATN_ERR_INVALID_ARG, "empty motion/depth buffer");
+        ATN_HIP(hipSetDevice(device));
+        ATN_HIP(m.buf.resize(n));
+        ATN_HIP(hipMemcpyAsync(m.buf.p, md, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        m.is_set = true;
+        m.count = n;
+        return ATN_OK;
+    }
+    // the common opening of the downloads and resets: every frame in flight has finished, and so has `stream`
+    int settle()
+    {
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        ATN_HIP(hipStreamSynchronize(stream));
+        return ATN_OK;
     }
 
-    // MatricesForRendering::Reset = Camera::ComputeCameraMatrices: mat4::lookat(origin, center, up) and
-    // mat4::perspective(znear, zfar, vfov, aspect) written into the existing matrices (mat4.h:457-513)
-    void svgf_reset_matrices() { camera_matrices(camera, sv_W2V, sv_V2C, sv_prevW2V); }
-    static void camera_matrices(const atn_camera_param& camera, float* W2V, float* V2C, float* prevW2V)
-    {
-        std::memcpy(prevW2V, W2V, 16 * sizeof(float));
-        const float* e = camera.origin; const float* at = camera.center; const float* up = camera.up;
-        float z[3] = { e[0] - at[0], e[1] - at[1], e[2] - at[2] };
-        float il = 1.0f / std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);        // glm::normalize = v * inversesqrt(dot(v, v))
-        z[0] *= il; z[1] *= il; z[2] *= il;
-        float x[3] = { up[1] * z[2] - z[1] * up[2], up[2] * z[0] - z[2] * up[0], up[0] * z[1] - z[0] * up[1] };
-        il = 1.0f / std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-        x[0] *= il; x[1] *= il; x[2] *= il;
-        const float y[3] = { z[1] * x[2] - x[1] * z[2], z[2] * x[0] - x[2] * z[0], z[0] * x[1] - x[0] * z[1] };
-        float* m = W2V;
-        m[0] = x[0]; m[4] = y[0]; m[8] = z[0];
-        m[1] = x[1]; m[5] = y[1]; m[9] = z[1];
-        m[2] = x[2]; m[6] = y[2]; m[10] = z[2];
-        m[3] = -(x[0] * e[0] + x[1] * e[1] + x[2] * e[2]);
-        m[7] = -(y[0] * e[0] + y[1] * e[1] + y[2] * e[2]);
-        m[11] = -(z[0] * e[0] + z[1] * e[1] + z[2] * e[2]);
-        m[15] = 1;
-        const float fH = 1 / std::tan((3.14159265358979323846F * (camera.vfov) / 180.0F) * 0.5f);
-        const float fW = fH / camera.aspect;
-        float* p = V2C;
-        p[0] = fW; p[5] = fH;
-        p[10] = camera.zfar / (camera.znear - camera.zfar);
-        p[11] = camera.znear * camera.zfar / (camera.znear - camera.zfar);
-        p[14] = -1.0f; p[15] = 0.0f;
-    }
-
-    int svgf_fill(float4* p, size_t n, float4 v)
+    int fill4(float4* p, size_t n, float4 v)
     {
         hipLaunchKernelGGL(k_svgf_fill, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, p, (uint32_t)n, v);
         return ATN_OK;
@@ -2205,16 +2159,16 @@ public:
         const size_t n = (size_t)w * h;
         if (w != sv_w || h != sv_h) {
             const float4 init = make_float4(0.0F, 0.0F, 0.0F, 1.0F);
-            for (auto& set : sv_aov) for (auto& b : set) { ATN_HIP(b.resize(n)); svgf_fill(b.p, n, init); }
-            ATN_HIP(sv_scratch.resize(n)); svgf_fill(sv_scratch.p, n, init);
-            for (auto& b : sv_atrous) { ATN_HIP(b.resize(n)); svgf_fill(b.p, n, init); }
-            ATN_HIP(sv_tmp.resize(n)); svgf_fill(sv_tmp.p, n, init);
+            for (auto& set : sv_aov) for (auto& b : set) { ATN_HIP(b.resize(n)); fill4(b.p, n, init); }
+            ATN_HIP(sv_scratch.resize(n)); fill4(sv_scratch.p, n, init);
+            for (auto& b : sv_atrous) { ATN_HIP(b.resize(n)); fill4(b.p, n, init); }
+            ATN_HIP(sv_tmp.resize(n)); fill4(sv_tmp.p, n, init);
             for (int k = 0; k < 2; k++) {
-                ATN_HIP(sv_primary[k].resize(n)); svgf_fill(sv_primary[k].p, n, make_float4(0, 0, 0, 0));
+                ATN_HIP(sv_primary[k].resize(n)); fill4(sv_primary[k].p, n, make_float4(0, 0, 0, 0));
                 ATN_HIP(sv_contribs[k].resize(n)); ATN_HIP(sv_gnd[k].resize(n)); ATN_HIP(sv_gam[k].resize(n));
             }
             ATN_HIP(sv_out.resize(n));
-            if (!sv_motion_set || sv_motion_count < n) { ATN_HIP(sv_motion.resize(n)); sv_motion_set = false; sv_motion_count = 0; }
+            if (!sv_motion.is_set || sv_motion.count < n) { ATN_HIP(sv_motion.buf.resize(n)); sv_motion.is_set = false; sv_motion.count = 0; }
             sv_cv[0] = sv_aov[0][2].p; sv_cv[1] = sv_aov[1][2].p; sv_spare = sv_scratch.p;
             sv_w = w; sv_h = h; sv_curr = 0; sv_slot = 0; sv_last_slot = 0;
             sv_frame_done = false;
@@ -2223,25 +2177,11 @@ public:
         return ATN_OK;
     }
 
-    // ≙ SVGFRenderer::SetMotionDepthBuffer (svgf.cpp:441-450)
-    int svgf_set_motion_depth(const atn_vec4* md, uint32_t n)
-    {
-        if (!md || n == 0) return fail(ATN_ERR_INVALID_ARG, "empty motion/depth buffer");
-        ATN_HIP(hipSetDevice(device));
-        ATN_HIP(sv_motion.resize(n));
-        ATN_HIP(hipMemcpyAsync(sv_motion.p, md, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, stream));
-        ATN_HIP(hipStreamSynchronize(stream));
-        sv_motion_set = true;
-        sv_motion_count = n;
-        return ATN_OK;
-    }
-
     int svgf_reset()
     {
         sv_w = 0; sv_h = 0; sv_curr = 0;        // buffers are re-initialised by the next svgf_render
         sv_frame_done = false;
-        const float id[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-        std::memcpy(sv_W2V, id, sizeof(id)); std::memcpy(sv_V2C, id, sizeof(id)); std::memcpy(sv_prevW2V, id, sizeof(id));
+        sv_mtx.reset_identity();
         return ATN_OK;
     }
 
@@ -2254,7 +2194,7 @@ public:
         if (which >= 0 && which < 4) return which == 2 ? sv_cv[c] : sv_aov[c][which].p;
         if (which < 8) return which == 6 ? sv_cv[p] : sv_aov[p][which - 4].p;
         switch (which) {
-        case 8: return sv_tmp.p; case 9: return sv_motion.p; case 10: return sv_primary[k].p;
+        case 8: return sv_tmp.p; case 9: return sv_motion.buf.p; case 10: return sv_primary[k].p;
         case 11: return sv_atrous[0].p; case 12: return sv_atrous[1].p; case 13: return sv_out.p; case 14: return sv_contribs[k].p;
         case 15: return (!for_upload && gm_sv_ids[k]) ? gm_ids[k].p : nullptr;      // the ids plane of the last mode-2 frame (device/motion.hpp)
         }
@@ -2285,22 +2225,22 @@ public:
         if (!pipelined && frames_in_flight > 1) { rc = quiesce(); if (rc) return rc; }
         else if (w_or_h_changed(d->width, d->height)) { rc = quiesce(); if (rc) return rc; }
         if (pipelined && !sv_stream) {
-            ATN_HIP(hipStreamCreateWithFlags(&sv_stream, hipStreamNonBlocking));
-            for (auto& e : sv_ev_prepare) ATN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            ATN_HIP(hipStreamCreateWithFlags(&sv_stream.h, hipStreamNonBlocking));
+            for (auto& e : sv_ev_prepare) ATN_HIP(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
         }
         rc = begin_frame(*d, pipelined);
         if (rc) return rc;
         hipStream_t fs = pipelined ? sv_stream : stream;       // the stream the filter passes run on
         rc = svgf_ensure(d->width, d->height, stages_host != nullptr);
         if (rc) return rc;
-        if (!compute_motion && (!sv_motion_set || sv_motion_count < (size_t)d->width * d->height))
+        if (!compute_motion && (!sv_motion.is_set || sv_motion.count < (size_t)d->width * d->height))
             return fail(ATN_ERR_INVALID_ARG, "no motion/depth buffer: call atn_svgf_set_motion_depth or pass compute_motion = 1");
         const bool prof = d->profile != 0;
         PathBuffers pb = buffers(false);
         FrameParams fp = frame_params(*d);
         fp.break_on_terminate = 1;
 
-        svgf_reset_matrices();
+        sv_mtx.advance(camera);
         const int32_t cur = sv_curr, prv = 1 - sv_curr;
         SvgfFrame sf{};
         sf.nd = sv_aov[cur][0].p; sf.am = sv_aov[cur][1].p; sf.cv = sv_cv[cur]; sf.mt = sv_aov[cur][3].p;
@@ -2309,11 +2249,11 @@ public:
         sf.atrous[0] = sv_atrous[0].p; sf.atrous[1] = sv_atrous[1].p;
         const int32_t slot = sv_slot;
         sv_last_slot = slot;
-        sf.tmp = sv_tmp.p; sf.motion = sv_motion.p; sf.primary = sv_primary[slot].p; sf.contribs = sv_contribs[slot].p;
+        sf.tmp = sv_tmp.p; sf.motion = sv_motion.buf.p; sf.primary = sv_primary[slot].p; sf.contribs = sv_contribs[slot].p;
         sf.g_nd = path_pass ? sv_gnd[slot].p : nullptr; sf.g_am = path_pass ? sv_gam[slot].p : nullptr;
         sf.out = sv_out.p; sf.stages = stages_host ? sv_stages.p : nullptr;
-        mat_mul(sv_V2C, sv_W2V, sf.w2c);
-        mat_mul(sv_V2C, sv_prevW2V, sf.prev_w2c);
+        mat_mul(sv_mtx.V2C, sv_mtx.W2V, sf.w2c);
+        mat_mul(sv_mtx.V2C, sv_mtx.prevW2V, sf.prev_w2c);
         sf.width = d->width; sf.height = d->height; sf.frame = d->frame; sf.atrous_iter_cnt = sv_atrous_iters;
         // Camera::ComputeScreenDistance (camera.h:216-221): tan of half the fov IN DEGREES, as the reference writes it
         sf.camera_distance = (float)d->height / (2.0f * std::tan(0.5f * camera.vfov));
@@ -2408,18 +2348,16 @@ public:
     // ReSTIR (aten::ReSTIRRenderer / idaten::ReSTIRPathTracing, device/restir.hpp): frame-persistent state = the two reservoir and
     // info sets (ReuseParams, restir_types.h:117-168), the AOVs, the motion/depth buffer and MatricesForRendering
     // ------------------------------------------------------------------------------------------------
-    DevBuf<float4> rs_res[2][kRestirResPlanes], rs_info[2][kRestirInfoPlanes], rs_nd, rs_am, rs_motion, rs_motion_own, rs_vis, rs_stage;
+    DevBuf<float4> rs_res[2][kRestirResPlanes], rs_info[2][kRestirInfoPlanes], rs_nd, rs_am, rs_motion_own, rs_vis, rs_stage;
+    MotionDepth rs_motion;
     // rs_motion: the caller's motion/depth buffer (atn_restir_set_motion_depth); rs_motion_own: the one compute_motion fills
     DevBuf<float> rs_dims;
     int32_t rs_w = 0, rs_h = 0, rs_pos = 0, rs_last = 0;     // rs_pos: the current set of the next frame; rs_last: of the last frame
     int32_t rs_mode = 1, rs_candidates = 32, rs_capture = 0;
-    bool rs_motion_set = false, rs_pending = false, rs_rendered = false;
+    bool rs_pending = false, rs_rendered = false;
     bool rs_captured = false, rs_last_own_motion = false;      // the last frame wrote the stage buffers / used rs_motion_own
-    size_t rs_motion_count = 0;
-    hipEvent_t rs_ev = nullptr;     // the last frame's reuse passes are done with the sets (the next frame's shade waits for it)
-    float rs_W2V[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-    float rs_V2C[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-    float rs_prevW2V[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    DevEvent rs_ev;     // the last frame's reuse passes are done with the sets (the next frame's shade waits for it)
+    FrameMatrices rs_mtx;
 
     int restir_set_options(int32_t mode, int32_t n_candidates)
     {
@@ -2429,25 +2367,11 @@ public:
         return ATN_OK;
     }
 
-    // ≙ ReSTIRRenderer::SetMotionDepthBuffer (restir.cpp:472-480) / ReSTIRPathTracing::SetGBuffer's motion-depth texture
-    int restir_set_motion_depth(const atn_vec4* md, uint32_t n)
-    {
-        if (!md || n == 0) return fail(ATN_ERR_INVALID_ARG, "empty motion/depth buffer");
-        ATN_HIP(hipSetDevice(device));
-        ATN_HIP(rs_motion.resize(n));
-        ATN_HIP(hipMemcpyAsync(rs_motion.p, md, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, stream));
-        ATN_HIP(hipStreamSynchronize(stream));
-        rs_motion_set = true;
-        rs_motion_count = n;
-        return ATN_OK;
-    }
-
     // forget the history: both sets are re-initialised by the next frame, the camera matrices start from the identity
     int restir_reset()
     {
         rs_w = 0; rs_h = 0; rs_pos = 0; rs_last = 0; rs_rendered = false; rs_captured = false;
-        const float id[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-        std::memcpy(rs_W2V, id, sizeof(id)); std::memcpy(rs_V2C, id, sizeof(id)); std::memcpy(rs_prevW2V, id, sizeof(id));
+        rs_mtx.reset_identity();
         return ATN_OK;
     }
 
@@ -2459,15 +2383,15 @@ public:
         { const int32_t m1 = -1; std::memcpy(&neg1, &m1, 4); }
         if (w != rs_w || h != rs_h) {
             for (int k = 0; k < 2; k++) {
-                for (auto& b : rs_res[k]) { ATN_HIP(b.resize(n)); svgf_fill(b.p, n, make_float4(0, 0, 0, 0)); }
-                for (auto& b : rs_info[k]) { ATN_HIP(b.resize(n)); svgf_fill(b.p, n, make_float4(0, 0, 0, 0)); }
-                svgf_fill(rs_res[k][0].p, n, make_float4(0.0F, 0.0F, neg1, 0.0F));
-                svgf_fill(rs_info[k][0].p, n, make_float4(0.0F, 0.0F, 0.0F, neg1));
-                svgf_fill(rs_info[k][3].p, n, make_float4(0.0F, neg1, 0.0F, 0.0F));
+                for (auto& b : rs_res[k]) { ATN_HIP(b.resize(n)); fill4(b.p, n, make_float4(0, 0, 0, 0)); }
+                for (auto& b : rs_info[k]) { ATN_HIP(b.resize(n)); fill4(b.p, n, make_float4(0, 0, 0, 0)); }
+                fill4(rs_res[k][0].p, n, make_float4(0.0F, 0.0F, neg1, 0.0F));
+                fill4(rs_info[k][0].p, n, make_float4(0.0F, 0.0F, 0.0F, neg1));
+                fill4(rs_info[k][3].p, n, make_float4(0.0F, neg1, 0.0F, 0.0F));
             }
-            ATN_HIP(rs_nd.resize(n)); svgf_fill(rs_nd.p, n, make_float4(0, 0, 0, 1));
-            ATN_HIP(rs_am.resize(n)); svgf_fill(rs_am.p, n, make_float4(0, 0, 0, 1));
-            if (!rs_motion_set || rs_motion_count < n) { ATN_HIP(rs_motion.resize(n)); rs_motion_set = false; rs_motion_count = 0; }
+            ATN_HIP(rs_nd.resize(n)); fill4(rs_nd.p, n, make_float4(0, 0, 0, 1));
+            ATN_HIP(rs_am.resize(n)); fill4(rs_am.p, n, make_float4(0, 0, 0, 1));
+            if (!rs_motion.is_set || rs_motion.count < n) { ATN_HIP(rs_motion.buf.resize(n)); rs_motion.is_set = false; rs_motion.count = 0; }
             rs_w = w; rs_h = h; rs_pos = 0; rs_last = 0;
         }
         ATN_HIP(rs_vis.resize(n_slots));
@@ -2497,14 +2421,14 @@ public:
         rc = restir_ensure(d->width, d->height);
         if (rc) return rc;
         const size_t n = (size_t)d->width * d->height;
-        if (!compute_motion && (!rs_motion_set || rs_motion_count < n))
+        if (!compute_motion && (!rs_motion.is_set || rs_motion.count < n))
             return fail(ATN_ERR_INVALID_ARG, "no motion/depth buffer: call atn_restir_set_motion_depth or pass compute_motion = 1");
         if (compute_motion) ATN_HIP(rs_motion_own.resize(n));
         if (geo_motion) ATN_HIP(gm_rs_ids.resize(n));
         gm_rs_has_ids = geo_motion;
-        if (!rs_ev) ATN_HIP(hipEventCreateWithFlags(&rs_ev, hipEventDisableTiming));
+        if (!rs_ev) ATN_HIP(hipEventCreateWithFlags(&rs_ev.h, hipEventDisableTiming));
         const bool prof = d->profile != 0;
-        camera_matrices(camera, rs_W2V, rs_V2C, rs_prevW2V);
+        rs_mtx.advance(camera);
 
         FrameParams fp = frame_params(*d);
         PathBuffers pb = buffers(false);
@@ -2514,9 +2438,9 @@ public:
         RestirArgs ra{};
         for (int k = 0; k < kRestirResPlanes; k++) { ra.cur.res[k] = rs_res[cur][k].p; ra.other.res[k] = rs_res[oth][k].p; }
         for (int k = 0; k < kRestirInfoPlanes; k++) { ra.cur.info[k] = rs_info[cur][k].p; ra.other.info[k] = rs_info[oth][k].p; }
-        ra.nd = rs_nd.p; ra.am = rs_am.p; ra.motion = compute_motion ? rs_motion_own.p : rs_motion.p; ra.vis = rs_vis.p;
-        mat_mul(rs_V2C, rs_W2V, ra.w2c);
-        mat_mul(rs_V2C, rs_prevW2V, ra.prev_w2c);
+        ra.nd = rs_nd.p; ra.am = rs_am.p; ra.motion = compute_motion ? rs_motion_own.p : rs_motion.buf.p; ra.vis = rs_vis.p;
+        mat_mul(rs_mtx.V2C, rs_mtx.W2V, ra.w2c);
+        mat_mul(rs_mtx.V2C, rs_mtx.prevW2V, ra.prev_w2c);
         for (int k = 0; k < 4; k++) ra.w2c3[k] = ra.w2c[12 + k];
         ra.n_candidates = rs_candidates;
         ra.stage_res = rs_capture ? rs_stage.p : nullptr;
@@ -2580,13 +2504,7 @@ public:
         hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
         prof_end(prof);
         ATN_HIP(hipGetLastError());
-        rc = end_film_frame();
-        if (rc) return rc;
-        if (out_host) {
-            ATN_HIP(hipMemcpyAsync(out_host, film.p, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
-            ATN_HIP(hipStreamSynchronize(stream));
-        }
-        return ATN_OK;
+        return end_film_frame(*d, out_host);
     }
 
     // stage buffers of the last frame (tests): 0 / 1 / 2 the reservoirs after the shade, temporal (visibility) and spatial passes as
@@ -2597,9 +2515,7 @@ public:
     {
         if (!rs_rendered || !out) return fail(ATN_ERR_INVALID_ARG, "no ReSTIR frame has been rendered");
         const size_t n = (size_t)rs_w * rs_h;
-        ATN_HIP(hipSetDevice(device));
-        { int q = quiesce(); if (q) return q; }
-        ATN_HIP(hipStreamSynchronize(stream));
+        { const int s = settle(); if (s) return s; }
         if ((which <= 2 || which == 7) && !rs_captured) return fail(ATN_ERR_INVALID_ARG, "the last frame kept no stage buffers: atn_restir_capture(ctx, 1) before the frame");
         if (which >= 0 && which <= 2) {
             std::vector<float4> h(2 * n);
@@ -2618,7 +2534,7 @@ public:
                 ATN_HIP(hipMemcpy(static_cast<float4*>(out) + (size_t)k * n, rs_info[rs_last][k].p, n * sizeof(float4), hipMemcpyDeviceToHost));
             return ATN_OK;
         }
-        const void* src = which == 4 ? (const void*)rs_nd.p : which == 5 ? (const void*)rs_am.p : which == 6 ? (const void*)(rs_last_own_motion ? rs_motion_own.p : rs_motion.p)
+        const void* src = which == 4 ? (const void*)rs_nd.p : which == 5 ? (const void*)rs_am.p : which == 6 ? (const void*)(rs_last_own_motion ? rs_motion_own.p : rs_motion.buf.p)
                         : which == 7 ? (const void*)rs_dims.p : (which == 8 && gm_rs_has_ids) ? (const void*)gm_rs_ids.p : nullptr;
         if (!src) return fail(ATN_ERR_INVALID_ARG, "no such ReSTIR buffer");
         if (which == 7) {
@@ -2643,7 +2559,7 @@ public:
     bool ta_valid = false;          // a history exists (false: the next frame takes the pass-through rule for every pixel)
     bool ta_resolved = false, ta_has_gamma = false;     // a frame has been resolved at ta_w x ta_h / and it wrote the float gamma plane
     bool ta_pending = false;
-    hipEvent_t ta_ev = nullptr;     // the last display tail has finished (its reads of the source planes and of the history)
+    DevEvent ta_ev;     // the last display tail has finished (its reads of the source planes and of the history)
     hipStream_t ta_last_stream = nullptr;
     static constexpr int32_t kTaaMaxSide = 16384;
 
@@ -2730,12 +2646,12 @@ public:
         case 0:
             if (!sv_frame_done) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: source 0 needs an atn_svgf_render / atn_svgf_denoise frame");
             if (w != sv_w || h != sv_h) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: the last SVGF frame has another size");
-            a.cur = sv_out.p; a.motion = sv_motion.p; st = sv_last_fs;
+            a.cur = sv_out.p; a.motion = sv_motion.buf.p; st = sv_last_fs;
             break;
         case 1:
             if (!rs_rendered) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: source 1 needs an atn_restir_render frame");
             if (w != rs_w || h != rs_h || w != film_w || h != film_h) return fail(ATN_ERR_INVALID_ARG, "atn_taa_resolve: the last ReSTIR frame has another size");
-            a.cur = film.p; a.motion = rs_last_own_motion ? rs_motion_own.p : rs_motion.p;      // (the frame's film writer ran on `stream`)
+            a.cur = film.p; a.motion = rs_last_own_motion ? rs_motion_own.p : rs_motion.buf.p;      // (the frame's film writer ran on `stream`)
             break;
         case 2:
             if (ta_up_w[0] != w || ta_up_h[0] != h || ta_up_w[1] != w || ta_up_h[1] != h)
@@ -2753,7 +2669,7 @@ public:
             if (rc) return rc;
             ATN_HIP(ta_gamma.resize(n));
         }
-        if (!ta_ev) ATN_HIP(hipEventCreateWithFlags(&ta_ev, hipEventDisableTiming));
+        if (!ta_ev) ATN_HIP(hipEventCreateWithFlags(&ta_ev.h, hipEventDisableTiming));
         // behind the previous display tail (it wrote this frame's history), whatever stream that ran on
         if (ta_pending && ta_last_stream != st) ATN_HIP(hipStreamWaitEvent(st, ta_ev, 0));
         a.hist = ta_hist[ta_pos].p; a.out = ta_hist[1 - ta_pos].p;
@@ -2787,7 +2703,7 @@ public:
     uint32_t np_slots = 0;
     int32_t np_w = 0, np_h = 0, np_capture = 0, np_depth = 0;
     bool np_captured = false, np_pending = false;
-    hipEvent_t np_ev = nullptr;     // the last NPR frame's kernels are done with the sample-ray state (the next frame waits for it)
+    DevEvent np_ev;     // the last NPR frame's kernels are done with the sample-ray state (the next frame waits for it)
 
     int npr_decode(const atn_scene_desc* s, const HostSceneImage& img)
     {
@@ -2864,7 +2780,7 @@ public:
         if (rc) return rc;
         // atn_npr_shadow_set_mode(1): the same pre-pass as with lines off (docs/NPR_SHADOW.md)
         if (ns_frame()) { rc = ns_prepass(d); if (rc) return rc; }
-        if (!np_ev) ATN_HIP(hipEventCreateWithFlags(&np_ev, hipEventDisableTiming));
+        if (!np_ev) ATN_HIP(hipEventCreateWithFlags(&np_ev.h, hipEventDisableTiming));
         const bool prof = d->profile != 0;
         FrameParams fp = frame_params(*d);
         PathBuffers pb = buffers(false);
@@ -2933,13 +2849,7 @@ public:
         else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
         prof_end(prof);
         ATN_HIP(hipGetLastError());
-        rc = end_film_frame();
-        if (rc) return rc;
-        if (out_host) {
-            ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
-            ATN_HIP(hipStreamSynchronize(stream));
-        }
-        return ATN_OK;
+        return end_film_frame(*d, out_host);
     }
 
     // the film and the sample-ray state of a fresh context
@@ -2959,9 +2869,7 @@ public:
     {
         if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
         if (!np_captured) return fail(ATN_ERR_INVALID_ARG, "the last NPR frame kept no stage buffers: atn_npr_capture(ctx, 1) before the frame");
-        ATN_HIP(hipSetDevice(device));
-        { int q = quiesce(); if (q) return q; }
-        ATN_HIP(hipStreamSynchronize(stream));
+        { const int s = settle(); if (s) return s; }
         const size_t n = (size_t)np_w * np_h;
         switch (which) {
         case 0: ATN_HIP(hipMemcpy(out, np_st_line.p, n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
@@ -2988,7 +2896,7 @@ public:
     uint32_t vl_slots = 0;
     int32_t vl_w = 0, vl_h = 0, vl_capture = -1, vl_captured = -1;
     bool vl_rendered = false, vl_pending = false;
-    hipEvent_t vl_ev = nullptr;     // the last volume frame's kernels are done with the per-slot state (the next frame waits for it)
+    DevEvent vl_ev;     // the last volume frame's kernels are done with the per-slot state (the next frame waits for it)
 
     int vol_decode(const atn_scene_desc* s, const HostSceneImage& img)
     {
@@ -3060,7 +2968,7 @@ public:
         if (rc) return rc;
         rc = vol_ensure(d->width, d->height);
         if (rc) return rc;
-        if (!vl_ev) ATN_HIP(hipEventCreateWithFlags(&vl_ev, hipEventDisableTiming));
+        if (!vl_ev) ATN_HIP(hipEventCreateWithFlags(&vl_ev.h, hipEventDisableTiming));
         const bool prof = d->profile != 0;
         FrameParams fp = frame_params(*d);
         PathBuffers pb = buffers(false);
@@ -3120,13 +3028,7 @@ public:
         else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
         prof_end(prof);
         ATN_HIP(hipGetLastError());
-        rc = end_film_frame();
-        if (rc) return rc;
-        if (out_host) {
-            ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
-            ATN_HIP(hipStreamSynchronize(stream));
-        }
-        return ATN_OK;
+        return end_film_frame(*d, out_host);
     }
 
     int volume_reset()
@@ -3142,9 +3044,7 @@ public:
         if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
         if (!vl_rendered) return fail(ATN_ERR_INVALID_ARG, "no volume frame has been rendered");
         if (which != 4 && vl_captured < 0) return fail(ATN_ERR_INVALID_ARG, "the last volume frame kept no stage buffers: atn_volume_capture(ctx, iteration) before the frame");
-        ATN_HIP(hipSetDevice(device));
-        { int q = quiesce(); if (q) return q; }
-        ATN_HIP(hipStreamSynchronize(stream));
+        { const int s = settle(); if (s) return s; }
         const size_t n = (size_t)vl_w * vl_h;
         switch (which) {
         case 0: ATN_HIP(hipMemcpy(out, vl_st_state.p, n * sizeof(uint4), hipMemcpyDeviceToHost)); return ATN_OK;
@@ -3188,7 +3088,7 @@ public:
     uint32_t ao_slots = 0;
     int32_t ao_w = 0, ao_h = 0, ao_capture = 0;
     bool ao_captured = false, ao_pending = false, ao_rendered = false;
-    hipEvent_t ao_ev = nullptr;     // the last AO frame's kernels are done with the AO state (the next frame waits for it)
+    DevEvent ao_ev;     // the last AO frame's kernels are done with the AO state (the next frame waits for it)
 
     int ao_set_params(int32_t num_rays, float radius, int32_t filter)
     {
@@ -3245,7 +3145,7 @@ public:
         if (frames_in_flight > 1 && (size_t)ao_num_rays * n_slots > ao_rays_cap) { rc = quiesce(); if (rc) return rc; }
         rc = ao_ensure(d->width, d->height);
         if (rc) return rc;
-        if (!ao_ev) ATN_HIP(hipEventCreateWithFlags(&ao_ev, hipEventDisableTiming));
+        if (!ao_ev) ATN_HIP(hipEventCreateWithFlags(&ao_ev.h, hipEventDisableTiming));
         const bool prof = d->profile != 0;
         FrameParams fp = frame_params(*d);
         PathBuffers pb = buffers(false);
@@ -3294,13 +3194,7 @@ public:
         ao_pending = true;
         ao_captured = ao_capture != 0;
         ao_rendered = true;
-        rc = end_film_frame();
-        if (rc) return rc;
-        if (out_host) {
-            ATN_HIP(hipMemcpyAsync(out_host, film.p, (size_t)d->width * d->height * sizeof(float4), hipMemcpyDeviceToHost, stream));
-            ATN_HIP(hipStreamSynchronize(stream));
-        }
-        return ATN_OK;
+        return end_film_frame(*d, out_host);
     }
 
     // the film and the AO planes of a fresh context
@@ -3323,9 +3217,7 @@ public:
         if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
         if (!ao_rendered) return fail(ATN_ERR_INVALID_ARG, "no AO frame has been rendered");
         if (which >= 4 && !ao_captured) return fail(ATN_ERR_INVALID_ARG, "the last AO frame kept no stage buffers: atn_ao_capture(ctx, 1) before the frame");
-        ATN_HIP(hipSetDevice(device));
-        { int q = quiesce(); if (q) return q; }
-        ATN_HIP(hipStreamSynchronize(stream));
+        { const int s = settle(); if (s) return s; }
         const size_t n = (size_t)ao_w * ao_h;
         switch (which) {
         case 0: ATN_HIP(hipMemcpy(out, ao_state.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
@@ -3344,7 +3236,6 @@ public:
     // the next frame's pre-pass -- on another bank's stream -- overwrites nothing this frame's shade launches still read, and nothing
     // orders the two.
     // ------------------------------------------------------------------------------------------------
-    DevBuf<float> ns_depth_s, ns_lit, ns_depth, ns_plane;       // (the current bank's)
     DevBuf<float> ns_f_lit, ns_f_depth, ns_f_out;               // atn_npr_shadow_filter's own
     // the planes of the last frame that ran the pre-pass, whichever bank is current now (atn_npr_shadow_download): they stay valid until
     // that bank runs its next pre-pass, which becomes the last one
@@ -3352,8 +3243,6 @@ public:
     int32_t ns_last_w = 0, ns_last_h = 0;
     int32_t ns_mode = 0;            // atn_npr_shadow_set_mode
     bool ns_any = false;            // an uploaded Toon / StylizedBrdf material has stylized_shadow.enable (upload)
-    uint32_t ns_slots = 0;
-    int32_t ns_w = 0, ns_h = 0;
     bool ns_rendered = false;
 
     int ns_set_mode(int32_t mode)
@@ -3447,9 +3336,7 @@ public:
         if (!ns_rendered) return fail(ATN_ERR_INVALID_ARG, "no frame has run the NPR shadow pre-pass");
         if (which < 0 || which > 2) return fail(ATN_ERR_INVALID_ARG, "no such NPR shadow plane");
         if ((size_t)n != (size_t)ns_last_w * ns_last_h) return fail(ATN_ERR_INVALID_ARG, "NPR shadow planes have width x height floats");
-        ATN_HIP(hipSetDevice(device));
-        { int q = quiesce(); if (q) return q; }
-        ATN_HIP(hipStreamSynchronize(stream));
+        { const int s = settle(); if (s) return s; }
         ATN_HIP(hipMemcpy(out, ns_last[which], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
         return ATN_OK;
     }
@@ -3828,7 +3715,7 @@ int atn_svgf_render(atn_ctx* ctx, const atn_destination* dst, int32_t compute_mo
     CTX_OR_FAIL(ctx);
     return guarded(ctx, [&] { return ctx->r.svgf_render(dst, compute_motion, out_host, stages_host); });
 }
-int atn_svgf_set_motion_depth(atn_ctx* ctx, const atn_vec4* motion_depth, uint32_t n) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.svgf_set_motion_depth(motion_depth, n); }); }
+int atn_svgf_set_motion_depth(atn_ctx* ctx, const atn_vec4* motion_depth, uint32_t n) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.set_motion_depth(ctx->r.sv_motion, motion_depth, n); }); }
 int atn_svgf_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return ctx->r.svgf_reset(); }
 int atn_svgf_set_atrous_iterations(atn_ctx* ctx, int32_t n)
 {
@@ -3864,7 +3751,7 @@ int atn_restir_render(atn_ctx* ctx, const atn_destination* dst, int32_t compute_
     CTX_OR_FAIL(ctx);
     return guarded(ctx, [&] { return ctx->r.restir_render(dst, compute_motion, out_host); });
 }
-int atn_restir_set_motion_depth(atn_ctx* ctx, const atn_vec4* motion_depth, uint32_t n) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.restir_set_motion_depth(motion_depth, n); }); }
+int atn_restir_set_motion_depth(atn_ctx* ctx, const atn_vec4* motion_depth, uint32_t n) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.set_motion_depth(ctx->r.rs_motion, motion_depth, n); }); }
 int atn_restir_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return ctx->r.restir_reset(); }
 int atn_restir_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.rs_capture = on != 0; return ATN_OK; }
 int atn_restir_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.restir_download(which, out_host); }); }
@@ -3928,7 +3815,7 @@ int atn_svgf_upload(atn_ctx* ctx, int32_t which, int32_t width, int32_t height, 
     if (!p) return r.fail(ATN_ERR_INVALID_ARG, "no such SVGF buffer");
     C_HIP(r, hipMemcpyAsync(p, host, (size_t)width * height * sizeof(float4), hipMemcpyHostToDevice, r.stream));
     C_HIP(r, hipStreamSynchronize(r.stream));
-    if (which == 9) { r.sv_motion_set = true; r.sv_motion_count = (size_t)width * height; }
+    if (which == 9) { r.sv_motion.is_set = true; r.sv_motion.count = (size_t)width * height; }
     return ATN_OK;
 }
 void* atn_svgf_output_device(atn_ctx* ctx) { return ctx ? (void*)ctx->r.sv_out.p : nullptr; }

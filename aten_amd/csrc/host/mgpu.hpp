@@ -85,10 +85,10 @@ public:
     int n = 0;
 
     // exchange state, all on shard 0's device
-    hipStream_t comm = nullptr;
+    DevStream comm;
     DevBuf<float4> gathered[2], full;
-    hipEvent_t ev_pushed[2][PathTracing::kMaxShards] = {};  // shard i's tiles of the frame using buffer k have arrived
-    hipEvent_t ev_assembled[2] = {};                         // buffer k has been scattered into `full`
+    DevEvent ev_pushed[2][PathTracing::kMaxShards];         // shard i's tiles of the frame using buffer k have arrived
+    DevEvent ev_assembled[2];                                // buffer k has been scattered into `full`
     bool assembled_recorded[2] = { false, false };
     uint64_t frames = 0;
     int32_t width = 0, height = 0;
@@ -130,12 +130,12 @@ public:
             }       // otherwise hipMemcpyPeerAsync stages through host memory: slower, still correct
         }
         ATN_HIP(hipSetDevice(d0));
-        ATN_HIP(hipStreamCreateWithFlags(&comm, hipStreamNonBlocking));
+        ATN_HIP(hipStreamCreateWithFlags(&comm.h, hipStreamNonBlocking));
         for (int k = 0; k < 2; k++) {
-            ATN_HIP(hipEventCreateWithFlags(&ev_assembled[k], hipEventDisableTiming));
+            ATN_HIP(hipEventCreateWithFlags(&ev_assembled[k].h, hipEventDisableTiming));
             for (int i = 0; i < n; i++) {
                 ATN_HIP(hipSetDevice(shard[i]->device));
-                ATN_HIP(hipEventCreateWithFlags(&ev_pushed[k][i], hipEventDisableTiming));
+                ATN_HIP(hipEventCreateWithFlags(&ev_pushed[k][i].h, hipEventDisableTiming));
             }
         }
         return ATN_OK;
@@ -143,12 +143,7 @@ public:
 
     ~MultiGpu()
     {
-        worker.clear();     // joins the threads
-        for (int k = 0; k < 2; k++) {
-            if (ev_assembled[k]) (void)hipEventDestroy(ev_assembled[k]);
-            for (int i = 0; i < n; i++) if (ev_pushed[k][i]) (void)hipEventDestroy(ev_pushed[k][i]);
-        }
-        if (comm) (void)hipStreamDestroy(comm);
+        worker.clear();     // joins the threads; the events and `comm` go with their wrappers, before the shards
         if (!shard.empty()) (void)hipSetDevice(shard[0]->device);
         gathered[0].release(); gathered[1].release(); full.release();
     }

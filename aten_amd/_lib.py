@@ -43,6 +43,8 @@ SYMBOLS = [
     "atn_mgpu_set_regeneration", "atn_mgpu_render_burst", "atn_set_upload_options", "atn_libm_probe", "atn_set_shade_math",
     "atn_set_rr_lookahead", "atn_rr_lookahead_active", "atn_rr_lookahead_stats",
     "atn_set_nee_deferral", "atn_nee_deferral_active", "atn_nee_deferral_stats",
+    "atn_update_materials", "atn_update_lights", "atn_update_texture", "atn_update_rendering_config",
+    "atn_mgpu_update_materials", "atn_mgpu_update_lights", "atn_mgpu_update_texture", "atn_mgpu_update_rendering_config",
 ]
 
 
@@ -72,6 +74,11 @@ def lib():
         l.atn_download_path_cost.argtypes = [vp, vp]
         l.atn_update_geometry.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32]
         l.atn_scene_device_arrays.argtypes = [vp, vp, vp, vp]
+        for pre in ("atn_", "atn_mgpu_"):
+            getattr(l, pre + "update_materials").argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+            getattr(l, pre + "update_lights").argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_int32]
+            getattr(l, pre + "update_texture").argtypes = [vp, C.c_int32, vp]
+            getattr(l, pre + "update_rendering_config").argtypes = [vp, vp]
         l.atn_lbvh_rebuild_list.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
         l.atn_lbvh_build.argtypes = [vp, vp, C.c_uint32, C.c_int32, vp, vp, vp, C.c_uint32, C.c_int32, vp, vp, vp]
         l.atn_skin_create.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]

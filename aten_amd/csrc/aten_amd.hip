@@ -202,6 +202,7 @@ public:
     // keeps no copy of the vertices).  r06: a deformation tick (new blob vertices, rebuilt list, same lamp) used to drop them --
     // deformable room 1.97 -> 2.04 ms per frame after the first tick (profiles/r06_rebuilt_layout_bound.jsonl).
     struct PlanarCert {
+        int32_t light = -1;             // which light the certificate is for
         int32_t inst_obj = -1, mesh_obj = -1, mtx_id = -1;
         atn_object_param inst{}, mesh{};
         atn_mat4 l2w{}, w2l{};
@@ -214,6 +215,7 @@ public:
         for (size_t i = 0; i < lights.size() && i < s->n_lights; i++) {
             if (!lights[i]._pad) continue;
             PlanarCert c;                                          // (planar_area_light accepted this light: every index below is in range)
+            c.light = (int32_t)i;
             c.inst_obj = s->lights[i].arealight_objid;
             c.inst = s->objects[c.inst_obj];
             const atn_object_param* o = &s->objects[c.inst_obj];
@@ -261,6 +263,12 @@ public:
     std::vector<atn_mat4> host_matrices;    // the caller's matrices as last uploaded
     std::vector<uint32_t> list_base, list_bytes, list_tri_leaves, list_inner;   // region of every list in the node image
     uint32_t n_scene_tris = 0, n_scene_vtx = 0, n_scene_mtrls = 0;
+    // What atn_update_materials / _lights / _texture / _rendering_config edit (docs/SCENE_EDITS.md): the caller's editable data as
+    // last handed in, the planar flag of every uploaded light, the textures' storage records and how much of `texels` is in use.
+    SceneSource src;
+    std::vector<uint8_t> light_planar;
+    std::vector<DevTexture> host_textures;
+    size_t n_texels_used = 0;
 
     // LBVH rebuild scratch (atn_lbvh_*), grown on demand
     struct LbvhScratch {
@@ -879,19 +887,15 @@ public:
         scene.mtx_quads = (uint32_t)img.matrices.size();
         has_scene = true;
         if (gm_on) { gm_sv_ids[0] = gm_sv_ids[1] = gm_rs_has_ids = false; const int grc = gm_reset_history(); if (grc) return grc; }
-        { const int nrc = npr_decode(s, img); if (nrc) return nrc; }
-        { const int vrc = vol_decode(s, img); if (vrc) return vrc; }
-        env_host.clear(); env_w = env_h = 0; ibl_tables_ready = false;
+        src = std::move(img.source);
+        light_planar.assign(img.lights.size(), 0);
+        for (size_t i = 0; i < img.lights.size(); i++) light_planar[i] = img.lights[i]._pad != 0 ? 1 : 0;
+        host_textures = img.textures; n_texels_used = img.texels.size();
+        { const int nrc = npr_decode(img.materials); if (nrc) return nrc; }
+        { const int vrc = vol_decode(img.materials); if (vrc) return vrc; }
         {
             const int32_t ei = s->config.bg.envmap_tex_idx;
-            if (ei >= 0 && (uint32_t)ei < s->n_textures && s->config.bg.enable_env_map) {
-                const atn_texture_desc& t = s->textures[ei];
-                env_host.assign(t.texels, t.texels + (size_t)t.width * t.height);
-                env_w = t.width; env_h = t.height; env_multiplyer = s->config.bg.multiplyer;
-            }
-        }
-        {
-            int orc = apply_sampling_options();
+            int orc = refresh_envmap(ei >= 0 && (uint32_t)ei < s->n_textures ? s->textures[ei].texels : nullptr);
             if (orc) return orc;
         }
         list_root_link = img.list_root_link; list_twin_delta = img.list_twin_delta; tlas_refs = img.tlas_refs;
@@ -936,6 +940,176 @@ public:
         scene.ibl_importance = 1;
         return ATN_OK;
     }
+    // The host copy of the environment map the config names (what the IBL tables are built from), then the sampling options again.
+    // `texels`: that texture's content where the caller has just handed it in; null: read back from the device.
+    int refresh_envmap(const atn_vec4* texels)
+    {
+        env_host.clear(); env_w = env_h = 0; ibl_tables_ready = false;
+        const int32_t ei = src.config.bg.envmap_tex_idx;
+        if (ei >= 0 && (size_t)ei < src.tex.size() && src.config.bg.enable_env_map) {
+            const HostTexInfo& t = src.tex[ei];
+            if (texels) env_host.assign(texels, texels + (size_t)t.width * t.height);
+            else { const int rc = download_texture(ei, env_host); if (rc) return rc; }
+            env_w = t.width; env_h = t.height; env_multiplyer = src.config.bg.multiplyer;
+        }
+        return apply_sampling_options();
+    }
+    // texture `i` as the floats a lookup returns (fetch_texel's conversions, which give back the caller's floats)
+    int download_texture(int32_t i, std::vector<atn_vec4>& out)
+    {
+        const DevTexture& t = host_textures[i];
+        const size_t n = (size_t)t.width * t.height;
+        out.resize(n);
+        if (!n) return ATN_OK;
+        if (t.format == 0) {
+            ATN_HIP(hipMemcpyAsync(out.data(), texels.p + t.offset, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            ATN_HIP(hipStreamSynchronize(stream));
+            return ATN_OK;
+        }
+        std::vector<uint32_t> packed(n);
+        ATN_HIP(hipMemcpyAsync(packed.data(), texels8.p + t.offset, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        const float norm = 1.0F / 255;
+        for (size_t j = 0; j < n; j++) {
+            const uint32_t p = packed[j];
+            const float r = (float)(p & 255u), g = (float)((p >> 8) & 255u), b = (float)((p >> 16) & 255u), a = (float)(p >> 24);
+            out[j] = t.format == 1 ? atn_vec4{ r / 255.0F, g / 255.0F, b / 255.0F, a / 255.0F } : atn_vec4{ r * norm, g * norm, b * norm, a * norm };
+        }
+        return ATN_OK;
+    }
+
+    // ---------------------------------------------------------------------------------------------------------------
+    // Scene edits (docs/SCENE_EDITS.md): ≙ idaten::Renderer::updateMaterial / updateLight / UpdateTexture /
+    // UpdateSceneRenderingConfig, src/libidaten/kernel/renderer.cpp:207-252.  Each call applies the change to a copy of `src`, derives
+    // the device form with the functions the upload uses (host/scene_upload.hpp) and only then writes buffers and DevScene fields: a
+    // refused edit leaves everything as it was.  They wait for the frames in flight and reset nothing.
+
+    // the material-derived state of src.materials -> device
+    int commit_materials(const MaterialState& ms)
+    {
+        ATN_HIP(materials.upload(ms.materials, stream));
+        ATN_HIP(carpaint.upload(ms.carpaint, stream));
+        ATN_HIP(toon.upload(ms.toon, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        scene.any_alpha = ms.any_alpha; scene.material_set = ms.material_set; scene.rr_lookahead = ms.rr_lookahead;
+        scene.nee_deferral = nee_deferral_class(scene.material_set, src.lights.data(), (uint32_t)src.lights.size());
+        { const int rc = npr_decode(ms.materials); if (rc) return rc; }
+        return vol_decode(ms.materials);
+    }
+    int edit_begin()
+    {
+        ATN_HIP(hipSetDevice(device));
+        return quiesce();
+    }
+    int update_materials(const atn_material_param* m, uint32_t n, uint32_t first)
+    {
+        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+        if (!m) return fail(ATN_ERR_INVALID_ARG, "null material array");
+        if ((uint64_t)first + n > src.materials.size()) return fail(ATN_ERR_INVALID_ARG, "material range outside the uploaded scene");
+        MaterialState ms;
+        std::string err;
+        if (!edit_materials(src, m, n, first, ms, err)) return fail(ATN_ERR_UNSUPPORTED, err);
+        { const int rc = edit_begin(); if (rc) return rc; }
+        return commit_materials(ms);
+    }
+    int update_lights(const atn_light_param* l, uint32_t n, uint32_t first, int32_t npr_target)
+    {
+        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+        if (!l) return fail(ATN_ERR_INVALID_ARG, "null light array");
+        const std::vector<atn_light_param>& have = npr_target ? src.npr_lights : src.lights;
+        if ((uint64_t)first + n > have.size()) return fail(ATN_ERR_INVALID_ARG, "light range outside the uploaded scene");
+        // The planar flag (scene_upload.hpp: planar_area_light) was derived from the vertices, which the host does not keep: a light
+        // whose type and object are unchanged keeps its flag, plane and certificate, any other edited light loses them, and no edit
+        // grants one.  (The flag only lets a shadow walk stop early: the films are the same with and without it.)
+        std::vector<atn_light_param> dev(l, l + n);
+        if (!npr_target)
+            for (uint32_t k = 0; k < n; k++) {
+                const atn_light_param& was = have[first + k];
+                dev[k]._pad = light_planar[first + k] && l[k].type == was.type && l[k].arealight_objid == was.arealight_objid ? 1 : 0;
+            }
+        std::string err;
+        if (!edit_lights(src, l, n, first, npr_target != 0, err)) return fail(ATN_ERR_UNSUPPORTED, err);
+        { const int rc = edit_begin(); if (rc) return rc; }
+        if (!n) return ATN_OK;
+        if (npr_target) {
+            ATN_HIP(hipMemcpyAsync(npr_lights.p + first, dev.data(), (size_t)n * sizeof(atn_light_param), hipMemcpyHostToDevice, stream));
+            ATN_HIP(hipStreamSynchronize(stream));
+            return ATN_OK;
+        }
+        const float4 no_plane = make_float4(0, 0, 0, 0);
+        for (uint32_t k = 0; k < n; k++) {
+            const uint32_t i = first + k;
+            if (!light_planar[i] || dev[k]._pad) continue;
+            ATN_HIP(hipMemcpyAsync(light_plane.p + i, &no_plane, sizeof(float4), hipMemcpyHostToDevice, stream));
+            light_planar[i] = 0; n_planar_lights--;
+            for (size_t c = 0; c < planar_certs.size(); c++)
+                if (planar_certs[c].light == (int32_t)i) { planar_certs.erase(planar_certs.begin() + (ptrdiff_t)c); break; }
+        }
+        ATN_HIP(hipMemcpyAsync(lights.p + first, dev.data(), (size_t)n * sizeof(atn_light_param), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        scene.nee_deferral = nee_deferral_class(scene.material_set, src.lights.data(), (uint32_t)src.lights.size());
+        return ATN_OK;
+    }
+    int update_texture(int32_t texid, const atn_texture_desc* t)
+    {
+        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+        if (!t || !t->texels) return fail(ATN_ERR_INVALID_ARG, "null texture");
+        if (texid < 0 || (size_t)texid >= src.tex.size()) return fail(ATN_ERR_INVALID_ARG, "texture index outside the uploaded scene");
+        MaterialState ms;
+        bool rederived = false;
+        std::string err;
+        if (!edit_texture(src, texid, *t, ms, rederived, err)) return fail(ATN_ERR_UNSUPPORTED, err);
+        { const int rc = edit_begin(); if (rc) return rc; }
+        // Texel storage: a lookup returns exactly the floats handed in.  RGBA8 storage takes them if every one is what its 8-bit
+        // conversion gives back (either conversion: the record names it); otherwise the texture moves to float4 storage at the end
+        // of `texels` and stays there.
+        const size_t n = (size_t)t->width * t->height;
+        DevTexture rec = host_textures[texid];
+        std::vector<uint32_t> packed;
+        const int32_t fmt = rec.format ? encode_texels8(*t, packed) : 0;
+        if (fmt) {
+            ATN_HIP(hipMemcpyAsync(texels8.p + rec.offset, packed.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            rec.format = fmt;
+        }
+        else {
+            if (rec.format) {
+                DevBuf<float4> grown;
+                ATN_HIP(grown.resize(n_texels_used + n));
+                if (n_texels_used) ATN_HIP(hipMemcpyAsync(grown.p, texels.p, n_texels_used * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+                ATN_HIP(hipStreamSynchronize(stream));
+                texels.swap(grown);
+                scene.texels = texels.p;
+                rec.offset = (uint32_t)n_texels_used; rec.format = 0;
+                n_texels_used += n;
+            }
+            ATN_HIP(hipMemcpyAsync(texels.p + rec.offset, t->texels, n * sizeof(float4), hipMemcpyHostToDevice, stream));
+        }
+        ATN_HIP(hipMemcpyAsync(textures.p + texid, &rec, sizeof(DevTexture), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        host_textures[texid] = rec;
+        if (rederived) { const int rc = commit_materials(ms); if (rc) return rc; }
+        if (texid == src.config.bg.envmap_tex_idx && src.config.bg.enable_env_map) return refresh_envmap(t->texels);
+        return ATN_OK;
+    }
+    int update_rendering_config(const atn_scene_rendering_config* cfg)
+    {
+        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+        if (!cfg) return fail(ATN_ERR_INVALID_ARG, "null rendering config");
+        const atn_background was = src.config.bg;
+        std::string err;
+        if (!edit_config(src, *cfg, err)) return fail(ATN_ERR_UNSUPPORTED, err);
+        { const int rc = edit_begin(); if (rc) return rc; }
+        apply_config(scene, src.config);
+        // what the NPR and volume frames read of the config (the materials are as they were: nothing is uploaded again)
+        std::memcpy(&np_cfg, src.config.feature_line, sizeof(np_cfg));
+        np_alpha = vl_alpha = src.config.enable_alpha_blending != 0 && maybe_alpha;
+        vl_eps_bias = src.config.epsilon_bias_for_traversing_shadow_ray_in_medium;
+        const atn_background& bg = src.config.bg;
+        const bool had_env = was.envmap_tex_idx >= 0 && was.enable_env_map, has_env = bg.envmap_tex_idx >= 0 && bg.enable_env_map;
+        if (had_env != has_env || (has_env && (was.envmap_tex_idx != bg.envmap_tex_idx || was.multiplyer != bg.multiplyer))) return refresh_envmap(nullptr);
+        return ATN_OK;
+    }
+
     int set_sampling_options(int32_t ibl_importance, int32_t tex_bilinear)
     {
         ATN_HIP(hipSetDevice(device));
@@ -2699,29 +2873,34 @@ public:
     DevBuf<float> np_hpd;
     std::vector<uint32_t> np_mflags_host;
     atn_feature_line_config np_cfg{};
-    bool np_stencil = false, np_alpha = false, np_carpaint = false;     // what the refusals need (upload)
+    bool np_stencil = false, np_alpha = false, np_carpaint = false;     // what the refusals need (upload, edits)
+    bool maybe_alpha = false;       // a material has kAttrMaybeAlpha (np_alpha / vl_alpha = that and the config's enable_alpha_blending)
     uint32_t np_slots = 0;
     int32_t np_w = 0, np_h = 0, np_capture = 0, np_depth = 0;
     bool np_captured = false, np_pending = false;
     DevEvent np_ev;     // the last NPR frame's kernels are done with the sample-ray state (the next frame waits for it)
 
-    int npr_decode(const atn_scene_desc* s, const HostSceneImage& img)
+    // (of src, the editable scene data as last uploaded or edited; `mats` = the device form of src.materials)
+    int npr_decode(const std::vector<DevMaterial>& mats)
     {
-        std::memcpy(&np_cfg, s->config.feature_line, sizeof(np_cfg));
-        np_mflags_host.assign((size_t)s->n_materials + 1, 0u);        // (+ the white-diffuse fallback: no lines)
+        std::memcpy(&np_cfg, src.config.feature_line, sizeof(np_cfg));
+        const size_t nm = src.materials.size();
+        np_mflags_host.assign(nm + 1, 0u);        // (+ the white-diffuse fallback: no lines)
         np_stencil = false; np_carpaint = false;
-        bool maybe_alpha = false, any_shadow = false;
-        for (uint32_t i = 0; i < s->n_materials; i++) {
+        bool any_shadow = false;
+        for (size_t i = 0; i < nm; i++) {
+            const atn_material_param& m = src.materials[i];
             atn_feature_line_mtrl fl;
-            std::memcpy(&fl, s->materials[i].feature_line, sizeof(fl));
+            std::memcpy(&fl, m.feature_line, sizeof(fl));
             np_mflags_host[i] = (fl.enable ? 1u : 0u) | ((uint32_t)fl.metric_flag << 8);
-            if (s->materials[i].stencil_type == 2) np_stencil = true;         // StencilType::STENCIL
-            if (s->materials[i].type == ATN_MTRL_CARPAINT) np_carpaint = true;
-            if ((s->materials[i].type == ATN_MTRL_TOON || s->materials[i].type == ATN_MTRL_STYLIZED_BRDF) && s->materials[i].toon.stylized_shadow.enable) any_shadow = true;
+            if (m.stencil_type == 2) np_stencil = true;         // StencilType::STENCIL
+            if (m.type == ATN_MTRL_CARPAINT) np_carpaint = true;
+            if ((m.type == ATN_MTRL_TOON || m.type == ATN_MTRL_STYLIZED_BRDF) && m.toon.stylized_shadow.enable) any_shadow = true;
         }
         ns_any = any_shadow;
-        for (const DevMaterial& dm : img.materials) if (dm.attrib & kAttrMaybeAlpha) maybe_alpha = true;
-        np_alpha = s->config.enable_alpha_blending != 0 && maybe_alpha;
+        maybe_alpha = false;
+        for (const DevMaterial& dm : mats) if (dm.attrib & kAttrMaybeAlpha) maybe_alpha = true;
+        np_alpha = src.config.enable_alpha_blending != 0 && maybe_alpha;
         ATN_HIP(np_mflags.upload(np_mflags_host, stream));
         return ATN_OK;
     }
@@ -2898,14 +3077,15 @@ public:
     bool vl_rendered = false, vl_pending = false;
     DevEvent vl_ev;     // the last volume frame's kernels are done with the per-slot state (the next frame waits for it)
 
-    int vol_decode(const atn_scene_desc* s, const HostSceneImage& img)
+    int vol_decode(const std::vector<DevMaterial>& mats)
     {
-        std::vector<VolMedium> med((size_t)s->n_materials + 1, VolMedium{});       // (+ the white-diffuse fallback: no medium)
+        const size_t nm = src.materials.size();
+        std::vector<VolMedium> med(nm + 1, VolMedium{});       // (+ the white-diffuse fallback: no medium)
         vl_refuse.clear();
         vl_stencil = vl_carpaint = vl_toon = false;
-        bool maybe_alpha = false;
-        for (uint32_t i = 0; i < s->n_materials; i++) {
-            const atn_material_param& m = s->materials[i];
+        bool any_maybe_alpha = false;
+        for (size_t i = 0; i < nm; i++) {
+            const atn_material_param& m = src.materials[i];
             if (m.stencil_type == 2) vl_stencil = true;         // StencilType::STENCIL
             if (m.type == ATN_MTRL_CARPAINT) vl_carpaint = true;
             if (m.type == ATN_MTRL_TOON || m.type == ATN_MTRL_STYLIZED_BRDF) vl_toon = true;
@@ -2922,9 +3102,9 @@ public:
             else if (!(mp.sigma_a + mp.sigma_s > 0.0F)) vl_refuse = "material " + std::to_string(i) + " is a medium with sigma_a + sigma_s <= 0";
             else if ((uint32_t)m.id != i) vl_refuse = "material " + std::to_string(i) + " is a medium whose id is not its index (the medium stack holds material ids)";
         }
-        for (const DevMaterial& dm : img.materials) if (dm.attrib & kAttrMaybeAlpha) maybe_alpha = true;
-        vl_alpha = s->config.enable_alpha_blending != 0 && maybe_alpha;
-        vl_eps_bias = s->config.epsilon_bias_for_traversing_shadow_ray_in_medium;
+        for (const DevMaterial& dm : mats) if (dm.attrib & kAttrMaybeAlpha) any_maybe_alpha = true;
+        vl_alpha = src.config.enable_alpha_blending != 0 && any_maybe_alpha;
+        vl_eps_bias = src.config.epsilon_bias_for_traversing_shadow_ray_in_medium;
         ATN_HIP(vl_med.upload(med, stream));
         return ATN_OK;
     }
@@ -3482,6 +3662,27 @@ int atn_update_geometry(atn_ctx* ctx, const atn_vec4* vtx_pos, const atn_vec4* v
     CTX_OR_FAIL(ctx);
     return guarded(ctx, [&] { return ctx->r.updateGeometry(vtx_pos, vtx_nml, n_vertices, vtx_offset, triangles, n_triangles, tri_offset); });
 }
+// scene edits: synchronous (they wait for the frames in flight), atomic, nothing is reset
+int atn_update_materials(atn_ctx* ctx, const atn_material_param* materials, uint32_t n, uint32_t first)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.update_materials(materials, n, first); });
+}
+int atn_update_lights(atn_ctx* ctx, const atn_light_param* lights, uint32_t n, uint32_t first, int32_t npr_target)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.update_lights(lights, n, first, npr_target); });
+}
+int atn_update_texture(atn_ctx* ctx, int32_t texid, const atn_texture_desc* tex)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.update_texture(texid, tex); });
+}
+int atn_update_rendering_config(atn_ctx* ctx, const atn_scene_rendering_config* config)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.update_rendering_config(config); });
+}
 int atn_lbvh_rebuild_list(atn_ctx* ctx, uint32_t list_index, uint32_t tri_offset, uint32_t n_triangles, const float* bbox_min, const float* bbox_max)
 {
     CTX_OR_FAIL(ctx);
@@ -3990,6 +4191,26 @@ int atn_mgpu_lbvh_rebuild_list(atn_mgpu* mg, uint32_t list_index, uint32_t tri_o
         PathTracing& r = *mg->m.shard[i];
         if (hipSetDevice(r.device) != hipSuccess) return r.fail(ATN_ERR_HIP, "hipSetDevice");
         return r.lbvh_rebuild_list(list_index, tri_offset, n_triangles, bbox_min, bbox_max, false); }); });
+}
+int atn_mgpu_update_materials(atn_mgpu* mg, const atn_material_param* materials, uint32_t n, uint32_t first)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&] { return mg->m.on_all([&](int i) { return mg->m.shard[i]->update_materials(materials, n, first); }); });
+}
+int atn_mgpu_update_lights(atn_mgpu* mg, const atn_light_param* lights, uint32_t n, uint32_t first, int32_t npr_target)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&] { return mg->m.on_all([&](int i) { return mg->m.shard[i]->update_lights(lights, n, first, npr_target); }); });
+}
+int atn_mgpu_update_texture(atn_mgpu* mg, int32_t texid, const atn_texture_desc* tex)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&] { return mg->m.on_all([&](int i) { return mg->m.shard[i]->update_texture(texid, tex); }); });
+}
+int atn_mgpu_update_rendering_config(atn_mgpu* mg, const atn_scene_rendering_config* config)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&] { return mg->m.on_all([&](int i) { return mg->m.shard[i]->update_rendering_config(config); }); });
 }
 int atn_mgpu_update_camera(atn_mgpu* mg, const atn_camera_param* camera)
 {

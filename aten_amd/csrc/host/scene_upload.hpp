@@ -11,6 +11,25 @@
 
 namespace atn {
 
+// The part of a scene that can be edited after the upload, as the caller handed it in (see derive_materials below).
+struct HostTexInfo { int32_t width = 0, height = 0; uint8_t has_alpha = 0; };
+struct SceneSource {
+    std::vector<atn_material_param> materials;
+    std::vector<atn_light_param> lights, npr_lights;
+    uint32_t n_npr_declared = 0;        // atn_scene_desc::n_npr_target_lights (npr_lights is empty when the array was null)
+    bool npr_array = false;             // atn_scene_desc::npr_target_lights was not null
+    atn_scene_rendering_config config{};
+    std::vector<HostTexInfo> tex;
+    uint32_t n_objects = 0;
+};
+// What the materials (with the textures' alpha flags) decide.
+struct MaterialState {
+    std::vector<DevMaterial> materials;     // + the white-diffuse fallback at index n
+    std::vector<float4> carpaint;
+    std::vector<atn_toon_param> toon;       // per material + the fallback slot
+    int32_t any_alpha = 0, material_set = kMsCore, rr_lookahead = 0;
+};
+
 struct HostSceneImage {
     std::vector<float4> nodes;          // the byte image of all records (16-byte units)
     uint64_t n_nodes = 0;
@@ -36,6 +55,7 @@ struct HostSceneImage {
     std::vector<uint32_t> texels8;
     std::vector<DevTexture> textures;
     DevScene params{};                  // scalar fields filled; pointers left null
+    SceneSource source;                 // the caller's editable data (the context keeps it for atn_update_*)
     uint64_t n_inner = 0, n_tri_leaf = 0, n_tlas_leaf = 0;
 };
 
@@ -381,9 +401,10 @@ constexpr uint64_t kTwinBudgetBytes = 512ull << 20;
 // iff the material is neither SINGULAR nor TRANSLUCENT, the picked light a function of the draw alone.  A hit adds light only on an
 // emissive surface (HitImplicitLight), which an any-hit walk could not tell from whatever lies in front of it.  So EVERY uploaded
 // material, the appended white-diffuse fallback included, has to be one of the types below without those attributes; any other type
-// (and any unknown one) switches the look-ahead off.  The scene has no call that changes materials or lights in place: they arrive
-// with atn_upload_scene only, which decides this again; a caller that writes the triangle array itself (atn_scene_device_arrays) can
-// only point a triangle at another checked material or at the fallback.
+// (and any unknown one) switches the look-ahead off.  Materials arrive with atn_upload_scene and change with atn_update_materials /
+// atn_update_texture: both go through derive_materials (below), which decides this again over the whole array, so the answer
+// always describes the materials the next frame reads; lights do not enter it.  A caller that writes the triangle array itself
+// (atn_scene_device_arrays) can only point a triangle at another checked material or at the fallback.
 inline bool rr_lookahead_valid(const std::vector<DevMaterial>& materials)
 {
     for (const DevMaterial& dm : materials) {
@@ -412,6 +433,188 @@ inline int32_t nee_deferral_class(int32_t material_set, const atn_light_param* l
     bool all_infinite = true;
     for (uint32_t i = 0; i < n_lights; i++) if (!(lights[i].attrib & ATN_LIGHT_ATTR_INFINITE)) all_infinite = false;
     return all_infinite ? 3 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The part of a scene an application edits after the upload (atn_update_materials / _lights / _texture / _rendering_config,
+// docs/SCENE_EDITS.md).  The uploaded form of that data is DERIVED state: attribute bits, side tables and the scalars that pick
+// a kernel flavour.  SceneSource is the host's copy of what the caller handed in; the derive_* / validate_* functions below turn
+// it into the device form.  build_host_image and the edit calls both go through them, so a context after an edit holds what a
+// fresh upload of the edited description would.
+inline bool texture_has_alpha(const atn_texture_desc& t)
+{
+    const size_t n = (size_t)t.width * t.height;
+    for (size_t j = 0; j < n; j++) if (t.texels[j].w < 1.0F) return true;
+    return false;
+}
+
+inline void capture_source(SceneSource& src, const atn_scene_desc* s)
+{
+    src.materials.assign(s->materials, s->materials + s->n_materials);
+    src.lights.assign(s->lights, s->lights + s->n_lights);
+    src.npr_lights.clear();
+    src.n_npr_declared = s->n_npr_target_lights; src.npr_array = s->npr_target_lights != nullptr;
+    if (s->n_npr_target_lights && s->npr_target_lights) src.npr_lights.assign(s->npr_target_lights, s->npr_target_lights + s->n_npr_target_lights);
+    src.config = s->config;
+    src.tex.resize(s->n_textures);
+    for (uint32_t i = 0; i < s->n_textures; i++) {
+        src.tex[i].width = s->textures[i].width; src.tex[i].height = s->textures[i].height;
+        src.tex[i].has_alpha = texture_has_alpha(s->textures[i]) ? 1 : 0;
+    }
+    src.n_objects = s->n_objects;
+}
+
+// A texture index is "none" when negative; any other value must name an uploaded texture.
+inline bool tex_index_ok(int32_t idx, size_t n_textures) { return idx < 0 || (size_t)idx < n_textures; }
+
+// DevMaterial[], the carpaint and toon side tables, any_alpha, material_set and rr_lookahead of `mats`.  False (err set): a material
+// names a texture or an NPR target light that does not exist.
+inline bool derive_materials(const std::vector<atn_material_param>& mats, const SceneSource& src, MaterialState& ms, std::string& err)
+{
+    const size_t nm = mats.size();
+    ms.materials.assign(nm, DevMaterial{});
+    ms.carpaint.assign((nm + 1) * 4, make_float4(0, 0, 0, 0));
+    ms.toon.assign(nm + 1, atn_toon_param{});
+    for (size_t i = 0; i < nm; i++) {
+        const atn_material_param& m = mats[i];
+        if (!tex_index_ok(m.albedoMap, src.tex.size()) || !tex_index_ok(m.normalMap, src.tex.size()) || !tex_index_ok(m.roughnessMap, src.tex.size())) {
+            err = "material texture index out of range"; return false;
+        }
+        const float* c = m.u.carpaint;
+        for (int k = 0; k < 4; k++) ms.carpaint[4 * i + k] = make_float4(c[4 * k], c[4 * k + 1], c[4 * k + 2], c[4 * k + 3]);
+        DevMaterial& d = ms.materials[i];
+        d.baseColor = make_float4(m.baseColor.x, m.baseColor.y, m.baseColor.z, m.baseColor.w);
+        d.type = m.type; d.attrib = (m.attrib & 0xFu) | (m.isIdealRefraction ? kAttrIdealRefraction : 0u); d.id = m.id;
+        if (m.baseColor.w < 1.0F || (m.albedoMap >= 0 && src.tex[m.albedoMap].has_alpha)) d.attrib |= kAttrMaybeAlpha;
+        if (m.stencil_type == 1) d.attrib |= kAttrStencilAlways;
+        if (m.stencil_type == 2) d.attrib |= kAttrStencilStencil;
+        d.albedoMap = m.albedoMap; d.normalMap = m.normalMap; d.roughnessMap = m.roughnessMap;
+        const atn_standard_mtrl& st = m.u.standard;
+        d.ior = st.ior; d.roughness = st.roughness; d.subsurface = st.subsurface; d.metallic = st.metallic;
+        d.specular = st.specular; d.specularTint = st.specularTint; d.sheen = st.sheen; d.sheenTint = st.sheenTint;
+        d.clearcoat = st.clearcoat; d.clearcoatGloss = st.clearcoatGloss;
+        // NPR: ToonParameter per material
+        ms.toon[i] = m.toon;
+        if (m.type == ATN_MTRL_TOON || m.type == ATN_MTRL_STYLIZED_BRDF) {
+            const atn_toon_param& tp = ms.toon[i];
+            if (tp.target_light_idx >= 0 && (uint32_t)tp.target_light_idx >= src.n_npr_declared) { err = "toon material's target light index out of range"; return false; }
+            if (tp.target_light_idx >= 0 && !src.npr_array) { err = "null NPR target light array"; return false; }
+        }
+    }
+    {   // FillMaterial's fallback for mtrl_id < 0 (material_impl.h:253-259), stored at index n_materials
+        DevMaterial d{};
+        d.baseColor = make_float4(1, 1, 1, 1); d.type = ATN_MTRL_DIFFUSE; d.attrib = 0; d.id = 0;
+        d.albedoMap = d.normalMap = d.roughnessMap = -1; d.ior = 1.0F; d.roughness = 0.5F;
+        d.subsurface = d.metallic = d.specular = d.specularTint = 0.5F;
+        d.sheen = d.sheenTint = d.clearcoat = d.clearcoatGloss = 0.5F;
+        ms.materials.push_back(d);
+    }
+    ms.any_alpha = 0;
+    for (const DevMaterial& dm : ms.materials) if (dm.attrib & (kAttrMaybeAlpha | kAttrStencilStencil)) ms.any_alpha = 1;
+    ms.rr_lookahead = rr_lookahead_valid(ms.materials) ? 1 : 0;
+    ms.material_set = kMsCore;
+    for (const DevMaterial& dm : ms.materials) {
+        const int32_t t = dm.type;
+        const bool core = t == ATN_MTRL_EMISSIVE || t == ATN_MTRL_DIFFUSE || t == ATN_MTRL_SPECULAR || t == ATN_MTRL_GGX;
+        const int32_t need = (t == ATN_MTRL_TOON || t == ATN_MTRL_STYLIZED_BRDF) ? kMsToon
+                           : t == ATN_MTRL_CARPAINT ? kMsCarPaint : t == ATN_MTRL_DISNEY ? kMsDisney : core ? kMsCore : kMsAnalytic;
+        if (need > ms.material_set) ms.material_set = need;
+    }
+    return true;
+}
+
+// The ids a light carries.  `npr`: the array is atn_scene_desc::npr_target_lights.
+inline bool validate_lights(const atn_light_param* lights, size_t n, const SceneSource& src, bool npr, std::string& err)
+{
+    for (size_t i = 0; i < n; i++) {
+        const atn_light_param& l = lights[i];
+        if (l.arealight_objid >= 0 && (uint32_t)l.arealight_objid >= src.n_objects) {
+            err = npr ? "NPR target light refers to an object id out of range" : "light refers to an object id out of range"; return false;
+        }
+        if (l.type == ATN_LIGHT_IBL && !tex_index_ok(l.envmapidx, src.tex.size())) { err = "IBL light's environment map index out of range"; return false; }
+    }
+    return true;
+}
+
+inline bool validate_config(const atn_scene_rendering_config& cfg, const SceneSource& src, std::string& err)
+{
+    if (!tex_index_ok(cfg.bg.envmap_tex_idx, src.tex.size())) { err = "the config's environment map texture index out of range"; return false; }
+    return true;
+}
+
+// The host half of the edit calls: the change goes into `src` and the derived state comes back, or (false, err set) `src` stays as
+// it was.  The ranges have been checked against src's counts by the caller.
+inline bool edit_materials(SceneSource& src, const atn_material_param* m, uint32_t n, uint32_t first, MaterialState& ms, std::string& err)
+{
+    std::vector<atn_material_param> mats = src.materials;
+    std::copy(m, m + n, mats.begin() + first);
+    if (!derive_materials(mats, src, ms, err)) return false;
+    src.materials.swap(mats);
+    return true;
+}
+inline bool edit_lights(SceneSource& src, const atn_light_param* l, uint32_t n, uint32_t first, bool npr, std::string& err)
+{
+    if (!validate_lights(l, n, src, npr, err)) return false;
+    std::vector<atn_light_param>& have = npr ? src.npr_lights : src.lights;
+    std::copy(l, l + n, have.begin() + first);
+    return true;
+}
+// A texture's new content: its has-alpha flag, and -- `rederived` -- the materials again when the flag changed (it is part of
+// kAttrMaybeAlpha of every material that names the texture as its albedo map).
+inline bool edit_texture(SceneSource& src, int32_t texid, const atn_texture_desc& t, MaterialState& ms, bool& rederived, std::string& err)
+{
+    HostTexInfo& info = src.tex[texid];
+    if (t.width != info.width || t.height != info.height) { err = "a texture update keeps the texture's size"; return false; }
+    const uint8_t had = info.has_alpha;
+    info.has_alpha = texture_has_alpha(t) ? 1 : 0;
+    rederived = info.has_alpha != had;
+    if (rederived && !derive_materials(src.materials, src, ms, err)) { info.has_alpha = had; return false; }
+    return true;
+}
+inline bool edit_config(SceneSource& src, const atn_scene_rendering_config& cfg, std::string& err)
+{
+    if (!validate_config(cfg, src, err)) return false;
+    src.config = cfg;
+    return true;
+}
+
+// The DevScene fields that are the rendering config's.
+inline void apply_config(DevScene& p, const atn_scene_rendering_config& cfg)
+{
+    p.bvh_hit_min = cfg.bvh_hit_min;
+    p.bg_color[0] = cfg.bg.bg_color[0]; p.bg_color[1] = cfg.bg.bg_color[1]; p.bg_color[2] = cfg.bg.bg_color[2];
+    p.envmap_tex_idx = cfg.bg.envmap_tex_idx;
+    p.avgIllum = cfg.bg.avgIllum;
+    p.multiplyer = cfg.bg.multiplyer;
+    p.enable_env_map = cfg.bg.enable_env_map;
+    p.enable_alpha_blending = cfg.enable_alpha_blending ? 1 : 0;
+}
+
+// Texel storage: RGBA8 where every channel of every texel is exactly what an 8-bit -> float conversion gives back (DevTexture), float4
+// otherwise.  Which conversion reproduces EVERY channel of EVERY texel?  format 1: k / 255.0f,  2: k * (1.0f / 255)
+// (aten::Image::Load multiplies by `norm = 1.0F / 255`, image/image.cpp:76-80).  Returns the format (`packed` filled), 0 = store floats.
+// `only` != 0 asks for that one format (an edit writing into storage that already has it).
+inline int32_t encode_texels8(const atn_texture_desc& t, std::vector<uint32_t>& packed, int32_t only = 0)
+{
+    const size_t n = (size_t)t.width * t.height;
+    packed.resize(n);
+    for (int32_t cand = 1; cand <= 2 && n > 0; cand++) {
+        if (only && cand != only) continue;
+        auto decode = [cand](uint32_t k) { return cand == 1 ? (float)k / 255.0F : (float)k * (1.0F / 255); };
+        auto code = [&](float v, uint32_t& k) {
+            if (!(v >= 0.0F && v <= 1.0F)) return false;
+            k = (uint32_t)(v * 255.0F + 0.5F);
+            return k <= 255u && decode(k) == v;
+        };
+        bool ok = true;
+        for (size_t j = 0; j < n && ok; j++) {
+            uint32_t r = 0, g = 0, b = 0, a = 0;
+            ok = code(t.texels[j].x, r) && code(t.texels[j].y, g) && code(t.texels[j].z, b) && code(t.texels[j].w, a);
+            packed[j] = r | (g << 8) | (b << 16) | (a << 24);
+        }
+        if (ok) return cand;
+    }
+    return 0;
 }
 
 inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::string& err, int anyhit_twins = 0, int twin_dirs = 8,
@@ -523,40 +726,15 @@ inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::
     for (uint32_t i = 0; i < s->n_matrices; i++)
         for (int r = 0; r < 4; r++)
             img.matrices[4 * (size_t)i + r] = make_float4(s->matrices[i].m[r][0], s->matrices[i].m[r][1], s->matrices[i].m[r][2], s->matrices[i].m[r][3]);
-    std::vector<uint8_t> tex_has_alpha(s->n_textures, 0);
-    for (uint32_t i = 0; i < s->n_textures; i++) {
-        const atn_texture_desc& t = s->textures[i];
-        const size_t n = (size_t)t.width * t.height;
-        for (size_t j = 0; j < n; j++) if (t.texels[j].w < 1.0F) { tex_has_alpha[i] = 1; break; }
-    }
-    img.materials.resize(s->n_materials);
-    img.carpaint.assign((size_t)(s->n_materials + 1) * 4, make_float4(0, 0, 0, 0));
-    for (uint32_t i = 0; i < s->n_materials; i++) {
-        const float* c = s->materials[i].u.carpaint;
-        for (int k = 0; k < 4; k++) img.carpaint[4 * (size_t)i + k] = make_float4(c[4 * k], c[4 * k + 1], c[4 * k + 2], c[4 * k + 3]);
-    }
-    for (uint32_t i = 0; i < s->n_materials; i++) {
-        const atn_material_param& m = s->materials[i];
-        DevMaterial& d = img.materials[i];
-        d.baseColor = make_float4(m.baseColor.x, m.baseColor.y, m.baseColor.z, m.baseColor.w);
-        d.type = m.type; d.attrib = (m.attrib & 0xFu) | (m.isIdealRefraction ? kAttrIdealRefraction : 0u); d.id = m.id;
-        if (m.baseColor.w < 1.0F || (m.albedoMap >= 0 && (uint32_t)m.albedoMap < s->n_textures && tex_has_alpha[m.albedoMap])) d.attrib |= kAttrMaybeAlpha;
-        if (m.stencil_type == 1) d.attrib |= kAttrStencilAlways;
-        if (m.stencil_type == 2) d.attrib |= kAttrStencilStencil;
-        d.albedoMap = m.albedoMap; d.normalMap = m.normalMap; d.roughnessMap = m.roughnessMap;
-        const atn_standard_mtrl& st = m.u.standard;
-        d.ior = st.ior; d.roughness = st.roughness; d.subsurface = st.subsurface; d.metallic = st.metallic;
-        d.specular = st.specular; d.specularTint = st.specularTint; d.sheen = st.sheen; d.sheenTint = st.sheenTint;
-        d.clearcoat = st.clearcoat; d.clearcoatGloss = st.clearcoatGloss;
-    }
-    {   // FillMaterial's fallback for mtrl_id < 0 (material_impl.h:253-259), stored at index n_materials
-        DevMaterial d{};
-        d.baseColor = make_float4(1, 1, 1, 1); d.type = ATN_MTRL_DIFFUSE; d.attrib = 0; d.id = 0;
-        d.albedoMap = d.normalMap = d.roughnessMap = -1; d.ior = 1.0F; d.roughness = 0.5F;
-        d.subsurface = d.metallic = d.specular = d.specularTint = 0.5F;
-        d.sheen = d.sheenTint = d.clearcoat = d.clearcoatGloss = 0.5F;
-        img.materials.push_back(d);
-    }
+    SceneSource& src = img.source;
+    capture_source(src, s);
+    MaterialState ms;
+    if (!derive_materials(src.materials, src, ms, err)) return false;
+    if (!validate_lights(src.lights.data(), src.lights.size(), src, false, err)) return false;
+    if (!validate_lights(src.npr_lights.data(), src.npr_lights.size(), src, true, err)) return false;
+    if (!validate_config(src.config, src, err)) return false;
+    img.materials.swap(ms.materials); img.carpaint.swap(ms.carpaint); img.toon.swap(ms.toon);
+    img.npr_lights = src.npr_lights;
     img.lights.assign(s->lights, s->lights + s->n_lights);
     // area lights whose shadow rays may stop early (planar_area_light, below): the flag lives in OUR copy's padding word
     img.light_plane.assign(s->n_lights ? s->n_lights : 1, make_float4(0, 0, 0, 0));       // {world-space unit normal, 1} of a planar area light, else 0
@@ -572,26 +750,9 @@ inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::
     for (uint32_t i = 0; i < s->n_textures; i++) {
         const atn_texture_desc& t = s->textures[i];
         const size_t n = (size_t)t.width * t.height;
-        // which 8-bit -> float conversion reproduces EVERY channel of EVERY texel?  1: k / 255.0f,  2: k * (1.0f / 255)
-        // (aten::Image::Load multiplies by `norm = 1.0F / 255`, image/image.cpp:76-80)
-        int32_t fmt = 0;
         const size_t at8 = img.texels8.size();
-        std::vector<uint32_t> packed(n);
-        for (int32_t cand = 1; cand <= 2 && !fmt && n > 0; cand++) {
-            auto decode = [cand](uint32_t k) { return cand == 1 ? (float)k / 255.0F : (float)k * (1.0F / 255); };
-            auto code = [&](float v, uint32_t& k) {
-                if (!(v >= 0.0F && v <= 1.0F)) return false;
-                k = (uint32_t)(v * 255.0F + 0.5F);
-                return k <= 255u && decode(k) == v;
-            };
-            bool ok = true;
-            for (size_t j = 0; j < n && ok; j++) {
-                uint32_t r = 0, g = 0, b = 0, a = 0;
-                ok = code(t.texels[j].x, r) && code(t.texels[j].y, g) && code(t.texels[j].z, b) && code(t.texels[j].w, a);
-                packed[j] = r | (g << 8) | (b << 16) | (a << 24);
-            }
-            if (ok) fmt = cand;
-        }
+        std::vector<uint32_t> packed;
+        const int32_t fmt = encode_texels8(t, packed);
         const bool unorm8 = fmt != 0;
         img.textures[i].width = t.width; img.textures[i].height = t.height;
         if (unorm8) {
@@ -610,31 +771,8 @@ inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::
     p.root_link = img.list_root_link[0];
     fill_root_direct(p, img.nodes.data(), 0, s->matrices, s->n_matrices);
     p.n_lights = (int32_t)s->n_lights; p.inv_n_lights = s->n_lights ? 1.0f / (float)s->n_lights : 0.0f; p.n_textures = (int32_t)s->n_textures; p.n_materials = (int32_t)s->n_materials;
-    p.bvh_hit_min = s->config.bvh_hit_min;
-    p.bg_color[0] = s->config.bg.bg_color[0]; p.bg_color[1] = s->config.bg.bg_color[1]; p.bg_color[2] = s->config.bg.bg_color[2];
-    p.envmap_tex_idx = s->config.bg.envmap_tex_idx;
-    p.avgIllum = s->config.bg.avgIllum;
-    p.multiplyer = s->config.bg.multiplyer;
-    p.enable_env_map = s->config.bg.enable_env_map;
-    p.any_alpha = 0;
-    for (const DevMaterial& dm : img.materials) if (dm.attrib & (kAttrMaybeAlpha | kAttrStencilStencil)) p.any_alpha = 1;
-    p.enable_alpha_blending = s->config.enable_alpha_blending ? 1 : 0;
-    // NPR: ToonParameter per material, the target lights, the screen-space shadow texture (x channel)
-    img.toon.assign((size_t)s->n_materials + 1, atn_toon_param{});
-    for (uint32_t i = 0; i < s->n_materials; i++) {
-        img.toon[i] = s->materials[i].toon;
-        const int32_t t = s->materials[i].type;
-        if (t == ATN_MTRL_TOON || t == ATN_MTRL_STYLIZED_BRDF) {
-            const atn_toon_param& tp = img.toon[i];
-            if (tp.target_light_idx >= 0 && (uint32_t)tp.target_light_idx >= s->n_npr_target_lights) { err = "toon material's target light index out of range"; return false; }
-            if (tp.target_light_idx >= 0 && !s->npr_target_lights) { err = "null NPR target light array"; return false; }
-        }
-    }
-    if (s->n_npr_target_lights && s->npr_target_lights) {
-        img.npr_lights.assign(s->npr_target_lights, s->npr_target_lights + s->n_npr_target_lights);
-        for (const atn_light_param& l : img.npr_lights)
-            if (l.arealight_objid >= 0 && (uint32_t)l.arealight_objid >= s->n_objects) { err = "NPR target light refers to an object id out of range"; return false; }
-    }
+    apply_config(p, src.config);
+    p.any_alpha = ms.any_alpha;
     p.n_npr_lights = (int32_t)img.npr_lights.size();
     p.enable_shadowray_base_stylized_shadow = s->enable_shadowray_base_stylized_shadow ? 1 : 0;
     p.ss_w = p.ss_h = 0;
@@ -644,15 +782,8 @@ inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::
         img.screen_shadow.resize(n);
         for (size_t i = 0; i < n; i++) img.screen_shadow[i] = s->screen_space_texture.texels[i].x;
     }
-    p.rr_lookahead = rr_lookahead_valid(img.materials) ? 1 : 0;
-    p.material_set = kMsCore;
-    for (const DevMaterial& dm : img.materials) {
-        const int32_t t = dm.type;
-        const bool core = t == ATN_MTRL_EMISSIVE || t == ATN_MTRL_DIFFUSE || t == ATN_MTRL_SPECULAR || t == ATN_MTRL_GGX;
-        const int32_t need = (t == ATN_MTRL_TOON || t == ATN_MTRL_STYLIZED_BRDF) ? kMsToon
-                           : t == ATN_MTRL_CARPAINT ? kMsCarPaint : t == ATN_MTRL_DISNEY ? kMsDisney : core ? kMsCore : kMsAnalytic;
-        if (need > p.material_set) p.material_set = need;
-    }
+    p.rr_lookahead = ms.rr_lookahead;
+    p.material_set = ms.material_set;
     p.nee_deferral = nee_deferral_class(p.material_set, s->lights, s->n_lights);
     // ImageBasedLight::sample's scene_radius (light/ibl.h:106-111; aabb::IsValid / getCenter /
     // ComputeDistanceToCoverBoundingSphere, math/aabb.h:176-180,231-234,346-362), evaluated once on the host.

@@ -16,6 +16,11 @@ class AtenAmdError(RuntimeError):
     pass
 
 
+def _elem_ptr(base, first, dtype):
+    """Address of element `first` of the C array at `base` (None stays None: the library reports the null pointer)."""
+    return None if not base else C.c_void_p(int(base) + first * dtype.itemsize)
+
+
 class PathTracing:
     def __init__(self, device=0):
         self._l = lib()
@@ -59,6 +64,34 @@ class PathTracing:
         top = np.ascontiguousarray(a["bvh_lists"][0])
         self._check(self._l.atn_update_tlas(self._ctx, objs.ctypes.data, len(objs), mtx.ctypes.data if len(mtx) else None,
                                             len(mtx), top.ctypes.data, len(top)))
+
+    # ---- scene edits (docs/SCENE_EDITS.md; idaten::Renderer::updateMaterial / updateLight / UpdateTexture /
+    # UpdateSceneRenderingConfig, renderer.cpp:207-252): each reads the edited data from `scene` (a SceneBuilder result, or
+    # anything with its `desc`), whose counts and texture sizes are the uploaded ones.  Nothing is reset: call reset() for that.
+    def updateMaterial(self, scene, first=0, n=None):
+        """Materials [first, first + n) of `scene` (default: from `first` to the end) replace the uploaded ones."""
+        d = scene.desc
+        n = int(d.n_materials) - first if n is None else n
+        self._check(self._l.atn_update_materials(self._ctx, _elem_ptr(d.materials, first, L.MATERIAL_PARAM), n, first))
+
+    def updateLight(self, scene, npr_target=False, first=0, n=None):
+        """Lights [first, first + n) of `scene`; npr_target: of its NPR target lights."""
+        d = scene.desc
+        base, count = (d.npr_target_lights, d.n_npr_target_lights) if npr_target else (d.lights, d.n_lights)
+        n = int(count) - first if n is None else n
+        self._check(self._l.atn_update_lights(self._ctx, _elem_ptr(base, first, L.LIGHT_PARAM), n, first, 1 if npr_target else 0))
+
+    def UpdateTexture(self, scene, texid):
+        """Texture `texid` of `scene` (same size as uploaded) replaces the uploaded one."""
+        d = scene.desc
+        if texid < 0 or texid >= int(d.n_textures):
+            raise ValueError("UpdateTexture: the scene has no texture %d" % texid)
+        tex = C.cast(d.textures, C.POINTER(L.TextureDesc))
+        self._check(self._l.atn_update_texture(self._ctx, texid, C.byref(tex[texid])))
+
+    def UpdateSceneRenderingConfig(self, scene):
+        """The rendering config of `scene` (atn_scene_desc::config) replaces the uploaded one."""
+        self._check(self._l.atn_update_rendering_config(self._ctx, C.byref(scene.desc.config)))
 
     # ---- dynamic geometry (the reference's deformation renderer, src/deformation_renderer/main.cpp:636-710)
     def updateGeometry(self, vtx_pos=None, vtx_nml=None, vtx_offset=0, triangles=None, tri_offset=0):
@@ -810,6 +843,34 @@ class MultiGpuPathTracing:
         objs = np.ascontiguousarray(a["objects"]); mtx = np.ascontiguousarray(a["matrices"]); top = np.ascontiguousarray(a["bvh_lists"][0])
         self._check(self._l.atn_mgpu_update_tlas(self._mg, objs.ctypes.data, len(objs), mtx.ctypes.data if len(mtx) else None,
                                                  len(mtx), top.ctypes.data, len(top)))
+
+    # ---- scene edits (docs/SCENE_EDITS.md; idaten::Renderer::updateMaterial / updateLight / UpdateTexture /
+    # UpdateSceneRenderingConfig, renderer.cpp:207-252): each reads the edited data from `scene` (a SceneBuilder result, or
+    # anything with its `desc`), whose counts and texture sizes are the uploaded ones.  Nothing is reset: call reset() for that.
+    def updateMaterial(self, scene, first=0, n=None):
+        """Materials [first, first + n) of `scene` (default: from `first` to the end) replace the uploaded ones."""
+        d = scene.desc
+        n = int(d.n_materials) - first if n is None else n
+        self._check(self._l.atn_mgpu_update_materials(self._mg, _elem_ptr(d.materials, first, L.MATERIAL_PARAM), n, first))
+
+    def updateLight(self, scene, npr_target=False, first=0, n=None):
+        """Lights [first, first + n) of `scene`; npr_target: of its NPR target lights."""
+        d = scene.desc
+        base, count = (d.npr_target_lights, d.n_npr_target_lights) if npr_target else (d.lights, d.n_lights)
+        n = int(count) - first if n is None else n
+        self._check(self._l.atn_mgpu_update_lights(self._mg, _elem_ptr(base, first, L.LIGHT_PARAM), n, first, 1 if npr_target else 0))
+
+    def UpdateTexture(self, scene, texid):
+        """Texture `texid` of `scene` (same size as uploaded) replaces the uploaded one."""
+        d = scene.desc
+        if texid < 0 or texid >= int(d.n_textures):
+            raise ValueError("UpdateTexture: the scene has no texture %d" % texid)
+        tex = C.cast(d.textures, C.POINTER(L.TextureDesc))
+        self._check(self._l.atn_mgpu_update_texture(self._mg, texid, C.byref(tex[texid])))
+
+    def UpdateSceneRenderingConfig(self, scene):
+        """The rendering config of `scene` (atn_scene_desc::config) replaces the uploaded one."""
+        self._check(self._l.atn_mgpu_update_rendering_config(self._mg, C.byref(scene.desc.config)))
 
     # ---- dynamic geometry (the reference's deformation renderer, src/deformation_renderer/main.cpp:636-710)
     def updateGeometry(self, vtx_pos=None, vtx_nml=None, vtx_offset=0, triangles=None, tri_offset=0):

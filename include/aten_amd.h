@@ -56,7 +56,9 @@ void atn_destroy(atn_ctx* ctx);
 const char* atn_last_error(atn_ctx* ctx);
 
 /* ≙ idaten::Renderer::UpdateSceneData (src/libidaten/kernel/renderer.cpp:12-131): copies the
- * scene to HBM (and re-lays-out the BVH).  The caller keeps ownership of `scene`. */
+ * scene to HBM (and re-lays-out the BVH).  The caller keeps ownership of `scene`.
+ * ATN_ERR_UNSUPPORTED for an id out of range: an object, matrix, triangle, vertex, material or light id, and a texture index
+ * (a material's maps, an IBL light's envmapidx, the config's envmap_tex_idx; negative = none) that is not below n_textures. */
 int atn_upload_scene(atn_ctx* ctx, const atn_scene_desc* scene);
 
 /* ≙ idaten::Renderer::updateBVH (src/libidaten/kernel/renderer.cpp:133-153): new ObjectParameters and
@@ -78,6 +80,24 @@ int atn_set_upload_options(atn_ctx* ctx, int32_t anyhit_twin, int32_t anyhit_twi
 
 /* ≙ idaten::Renderer::updateCamera (renderer.cpp:202-205). */
 int atn_update_camera(atn_ctx* ctx, const atn_camera_param* camera);
+
+/* ---- scene edits (docs/SCENE_EDITS.md): ≙ idaten::Renderer::updateMaterial / updateLight / UpdateTexture /
+ * UpdateSceneRenderingConfig (renderer.cpp:207-252).  `first` and `n` name a range of the uploaded array (the reference's call
+ * is first = 0); counts never change.  npr_target != 0 addresses atn_scene_desc::npr_target_lights instead of lights.  A
+ * texture update keeps the texture's width and height.
+ * After a successful edit the context behaves as one that was handed the edited atn_scene_desc by atn_upload_scene -- every
+ * film of every renderer, every refusal, atn_rr_lookahead_active, atn_nee_deferral_active and atn_sample_texture -- except that
+ * what was made on the device since the upload survives (skins, rebuilt lists, the geometry-motion history, films and the
+ * renderers' histories) and that atn_planar_area_lights may be lower: a light whose type and arealight_objid are unchanged keeps
+ * its planar flag, any other edited light loses it, no edit grants one (films do not depend on the flag).
+ * The calls wait for the frames in flight, reset nothing (atn_reset where the reference's reset() is wanted) and are atomic: a
+ * refused edit changes nothing.  ATN_ERR_NO_SCENE before an upload; ATN_ERR_INVALID_ARG for null pointers and ranges outside
+ * the uploaded counts; ATN_ERR_UNSUPPORTED, with atn_upload_scene's message, for content the upload refuses (a texture, object
+ * or NPR target light index out of range) and for a texture of another size.  Additive entry points: atn_abi_version stays 3. */
+int atn_update_materials(atn_ctx* ctx, const atn_material_param* materials, uint32_t n, uint32_t first);
+int atn_update_lights(atn_ctx* ctx, const atn_light_param* lights, uint32_t n, uint32_t first, int32_t npr_target);
+int atn_update_texture(atn_ctx* ctx, int32_t texid, const atn_texture_desc* tex);
+int atn_update_rendering_config(atn_ctx* ctx, const atn_scene_rendering_config* config);
 
 /* Scene updates between frames -- atn_update_tlas, atn_update_geometry, atn_lbvh_rebuild_list -- return when they are
  * ENQUEUED: the caller's arrays have been copied (they may be reused at once), the frames in flight keep running, and
@@ -351,6 +371,11 @@ int atn_mgpu_update_geometry(atn_mgpu* mg, const atn_vec4* vtx_pos, const atn_ve
                              const atn_triangle_param* triangles, uint32_t n_triangles, uint32_t tri_offset);
 int atn_mgpu_lbvh_rebuild_list(atn_mgpu* mg, uint32_t list_index, uint32_t tri_offset, uint32_t n_triangles,
                                const float bbox_min[3], const float bbox_max[3]);
+/* the scene edits (atn_update_materials and its kin, above) on every shard */
+int atn_mgpu_update_materials(atn_mgpu* mg, const atn_material_param* materials, uint32_t n, uint32_t first);
+int atn_mgpu_update_lights(atn_mgpu* mg, const atn_light_param* lights, uint32_t n, uint32_t first, int32_t npr_target);
+int atn_mgpu_update_texture(atn_mgpu* mg, int32_t texid, const atn_texture_desc* tex);
+int atn_mgpu_update_rendering_config(atn_mgpu* mg, const atn_scene_rendering_config* config);
 int atn_mgpu_update_camera(atn_mgpu* mg, const atn_camera_param* camera);
 int atn_mgpu_init_sampler(atn_mgpu* mg, int32_t width, int32_t height, int32_t seed);
 int atn_mgpu_set_random(atn_mgpu* mg, const uint32_t* seeds, uint32_t n);

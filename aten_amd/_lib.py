@@ -24,6 +24,7 @@ SYMBOLS = [
     "atn_volume_render", "atn_volume_reset", "atn_volume_capture", "atn_volume_download", "atn_volume_phase_table",
     "atn_ao_set_params", "atn_ao_render", "atn_ao_reset", "atn_ao_capture", "atn_ao_download",
     "atn_npr_shadow_set_mode", "atn_npr_shadow_download", "atn_npr_shadow_filter",
+    "atn_npr_hatching_set", "atn_npr_hatching_get", "atn_npr_hatching_filter", "atn_npr_hatching_download",
     "atn_film_device", "atn_tile_device", "atn_tile_slots", "atn_anyhit_twins", "atn_planar_area_lights", "atn_stream", "atn_synchronize",
     "atn_assemble_tiles", "atn_assemble_tiles_on", "atn_download_film", "atn_upload_film", "atn_get_stats", "atn_get_kernel_times",
     "atn_reset_kernel_times", "atn_generate_paths", "atn_trace_closest", "atn_cmj_samples", "atn_cmj_batch", "atn_ray_offset", "atn_get_random", "atn_random_count",
@@ -146,6 +147,10 @@ def lib():
         l.atn_npr_shadow_set_mode.argtypes = [vp, C.c_int32]
         l.atn_npr_shadow_download.argtypes = [vp, C.c_int32, vp, C.c_uint32]
         l.atn_npr_shadow_filter.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp]
+        l.atn_npr_hatching_set.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_float]
+        l.atn_npr_hatching_get.argtypes = [vp, vp, vp, vp, vp]
+        l.atn_npr_hatching_filter.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]
+        l.atn_npr_hatching_download.argtypes = [vp, C.c_int32, vp, C.c_uint32]
         l.atn_svgf_set_dilate_temporal_weight.argtypes = [vp, C.c_int32]
         l.atn_svgf_denoise.argtypes = [vp, vp, C.c_int32, vp, vp]
         l.atn_svgf_upload.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp]

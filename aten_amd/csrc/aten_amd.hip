@@ -24,6 +24,7 @@
 #include "device/npr.hpp"
 #include "device/ao.hpp"
 #include "device/npr_shadow.hpp"
+#include "device/npr_hatching.hpp"
 #include "device/volume.hpp"
 #include "device/lbvh.hpp"
 #include "device/skinning.hpp"
@@ -86,6 +87,11 @@ struct Bank {
     DevBuf<float> ns_depth_s, ns_lit, ns_depth, ns_plane;      // the NPR shadow pre-pass's planes of the bank's last mode-1 frame
     uint32_t ns_slots = 0;
     int32_t ns_w = 0, ns_h = 0;
+    // NPR hatching (atn_npr_hatching_set, docs/NPR_HATCHING.md): the first step's plane of a two-step direction, and with the AO base
+    // the bank's own AO ray list and per-slot / per-pixel words (device/ao.hpp's layout).  ns_lit holds the source plane of either base.
+    DevBuf<float> nh_first;
+    DevBuf<float4> nh_ray_o, nh_ray_d, nh_ray_n, nh_ray_res;
+    DevBuf<uint32_t> nh_work, nh_row_min, nh_counters, nh_state;
     uint32_t n_slots = 0;
     int32_t counters_depth = 0;
     uint64_t bank_epoch = 0;        // the scene update this bank's stream is behind (wait_scene_epoch)
@@ -2952,6 +2958,8 @@ public:
         if (regen_mode != 0) return fail(ATN_ERR_UNSUPPORTED, "NPR frames run the serial sample loop: switch path regeneration off (atn_set_regeneration(0))");
         if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "NPR frames have no relaxed-math kernels: atn_set_shade_math(0)");
         if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not count rays (count_stats must be 0)");
+        rc = nh_check(d);
+        if (rc) return rc;
         ATN_HIP(hipSetDevice(device));
         rc = begin_frame(*d, frames_in_flight > 1);
         if (rc) return rc;
@@ -3425,6 +3433,56 @@ public:
     bool ns_any = false;            // an uploaded Toon / StylizedBrdf material has stylized_shadow.enable (upload)
     bool ns_rendered = false;
 
+    // NPR hatching (idaten::NPRPathTracing's HatchingShadowBase x HatchingShadowDirection; device/npr_hatching.hpp,
+    // docs/NPR_HATCHING.md): what mode 1's pre-pass filters (0 the AO value at the primary hit, 1 the bounce-0 lit bit) and how (0 None,
+    // 1 Horizontal, 2 Vertical, 3 Orthogonal, 4 Cross, 5 OrthogonalCross).  The defaults are the pre-pass as it was, launch for launch.
+    int32_t nh_base = 1, nh_dir = kHatchHorizontal, nh_num_rays = 1;
+    float nh_radius = 1.0F;
+    int32_t ns_last_base = 1;               // the base of the last frame that ran the pre-pass
+    const float* nh_last_first = nullptr;   // its first step's plane (the final plane of a one-step direction)
+    DevBuf<float> nh_f_first;               // atn_npr_hatching_filter's own
+
+    int nh_set(int32_t base, int32_t direction, int32_t num_rays, float radius)
+    {
+        if (base != 0 && base != 1) return fail(ATN_ERR_INVALID_ARG, "NPR hatching: base is 0 (AO) or 1 (the shadow ray)");
+        if (direction < kHatchNone || direction > kHatchOrthogonalCross) return fail(ATN_ERR_INVALID_ARG, "NPR hatching: direction is 0 None, 1 Horizontal, 2 Vertical, 3 Orthogonal, 4 Cross or 5 OrthogonalCross");
+        if (num_rays < 1 || num_rays > kAoMaxRays) return fail(ATN_ERR_INVALID_ARG, "NPR hatching: ao_num_rays must be 1..64");
+        if (!(radius > 0.0F) || !std::isfinite(radius)) return fail(ATN_ERR_INVALID_ARG, "NPR hatching: ao_radius must be positive and finite");
+        nh_base = base; nh_dir = direction; nh_num_rays = num_rays; nh_radius = radius;
+        return ATN_OK;
+    }
+
+    // what the AO base cannot do on top of mode 1's refusals (atn_render and atn_npr_render, in front of the frame)
+    int nh_check(const atn_destination* d)
+    {
+        if (ns_mode != 1 || nh_base != 0) return ATN_OK;
+        if ((uint64_t)nh_num_rays * (uint64_t)d->width * (uint64_t)d->height > (uint64_t)kAoRayMask)
+            return fail(ATN_ERR_UNSUPPORTED, "NPR hatching: the AO base lists at most 2^28 rays per frame (fewer rays per pixel, or a smaller frame)");
+        return ATN_OK;
+    }
+
+    // would nh_ensure replace a buffer of this bank?  (with frames in flight the caller waits for them first)
+    bool nh_grows(int32_t w, int32_t h) const
+    {
+        const size_t n = (size_t)w * h;
+        if (nh_dir >= kHatchCross && n > nh_first.n) return true;
+        if (nh_base != 0) return false;
+        return (size_t)nh_num_rays * n_slots > nh_ray_o.n || n_slots > nh_work.n || n > nh_state.n || (size_t)h > nh_row_min.n || !nh_counters.p;
+    }
+
+    int nh_ensure(int32_t w, int32_t h)
+    {
+        const size_t n = (size_t)w * h;
+        if (nh_dir >= kHatchCross) ATN_HIP(nh_first.resize(n));
+        if (nh_base != 0) return ATN_OK;
+        const size_t r = (size_t)nh_num_rays * n_slots;
+        if (r > (size_t)kAoRayMask) return fail(ATN_ERR_UNSUPPORTED, "NPR hatching: the AO base lists at most 2^28 rays per frame (fewer rays per pixel, or a smaller frame)");
+        ATN_HIP(nh_ray_o.resize(r)); ATN_HIP(nh_ray_d.resize(r)); ATN_HIP(nh_ray_n.resize(r)); ATN_HIP(nh_ray_res.resize(r));
+        ATN_HIP(nh_work.resize(n_slots)); ATN_HIP(nh_state.resize(n)); ATN_HIP(nh_row_min.resize((size_t)h));
+        ATN_HIP(nh_counters.resize(kAoCounters));
+        return ATN_OK;
+    }
+
     int ns_set_mode(int32_t mode)
     {
         if (mode != 0 && mode != 1) return fail(ATN_ERR_INVALID_ARG, "NPR shadow: mode is 0 (the uploaded texture) or 1 (the shadow-ray pre-pass)");
@@ -3444,7 +3502,7 @@ public:
         if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: there are no relaxed-math kernels: atn_set_shade_math(0)");
         if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: its rays are not counted (count_stats must be 0)");
         if (np_carpaint) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: applyNormal's CarPaint flake samples are not drawn: CarPaint materials are refused");
-        return ATN_OK;
+        return nh_check(d);
     }
 
     int ns_ensure(int32_t w, int32_t h)
@@ -3466,8 +3524,10 @@ public:
     bool ns_swapped = false;
     int ns_prepass(const atn_destination* d)
     {
-        if (frames_in_flight > 1 && (d->width != ns_w || d->height != ns_h || n_slots != ns_slots)) { const int q = quiesce(); if (q) return q; }
+        if (frames_in_flight > 1 && (d->width != ns_w || d->height != ns_h || n_slots != ns_slots || nh_grows(d->width, d->height))) { const int q = quiesce(); if (q) return q; }
         int rc = ns_ensure(d->width, d->height);
+        if (rc) return rc;
+        rc = nh_ensure(d->width, d->height);
         if (rc) return rc;
         const bool prof = d->profile != 0;
         FrameParams fp = frame_params(*d);
@@ -3485,12 +3545,39 @@ public:
         prof_begin(prof, ATN_K_GEN);
         hipLaunchKernelGGL(k_gen_path, dim3(grid_for(n_slots)), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
         prof_end(prof);
-        prof_begin(prof, ATN_K_TRACE_CLOSEST);
-        ns_launch_primary(trace_launch(plan, 0), stream, pb, scene, na);
-        prof_end(prof);
-        prof_begin(prof, ATN_K_SHADE);
-        ns_launch_rays(nl, stream, pb, scene, fp, na);
-        ns_launch_filter(stream, ns_lit.p, ns_depth.p, ns_plane.p, d->width, d->height);
+        if (nh_base != 0) {
+            prof_begin(prof, ATN_K_TRACE_CLOSEST);
+            ns_launch_primary(trace_launch(plan, 0), stream, pb, scene, na);
+            prof_end(prof);
+            prof_begin(prof, ATN_K_SHADE);
+            ns_launch_rays(nl, stream, pb, scene, fp, na);
+        }
+        else {
+            // the AO base: ShandeByAO at every primary hit through the AO renderer's own kernels and sampler (docs/NPR_HATCHING.md), over
+            // this bank's ray list; the source plane (ns_lit) then holds AO values, and there is no lit bit
+            AoArgs aa{};
+            aa.ray_o = nh_ray_o.p; aa.ray_d = nh_ray_d.p; aa.ray_n = nh_ray_n.p; aa.ray_res = nh_ray_res.p;
+            aa.work = nh_work.p; aa.depth_s = ns_depth_s.p; aa.row_min = nh_row_min.p; aa.counters = nh_counters.p;
+            aa.state = nh_state.p; aa.value = ns_lit.p; aa.depth = ns_depth.p;
+            aa.num_rays = nh_num_rays; aa.radius = nh_radius;
+            const uint32_t n_rays = (uint32_t)nh_num_rays * n_slots;
+            AoLaunch al{};
+            al.grid = nl.grid; al.slot_grid = (n_slots + 255u) / 256u;
+            al.refill = plan.refill; al.lds_bytes = plan.lds_bytes;
+            al.trace_block = nl.trace_block;
+            al.trace_grid = plan.refill ? trace_grid(n_rays, true) : grid_for(n_rays) * (256u / plan.block);
+            ATN_HIP(hipMemsetAsync(nh_counters.p, 0, (size_t)kAoCounters * sizeof(uint32_t), stream));
+            ATN_HIP(hipMemsetAsync(nh_row_min.p, 0xff, (size_t)d->height * sizeof(uint32_t), stream));
+            prof_begin(prof, ATN_K_TRACE_CLOSEST);
+            ao_launch_primary(trace_launch(plan, 0), stream, pb, scene, aa);
+            prof_end(prof);
+            prof_begin(prof, ATN_K_SHADE);
+            ao_launch_rays(al, stream, pb, scene, fp, aa);
+            nh_launch_resolve(al.slot_grid, stream, fp, aa, ns_lit.p, ns_depth.p);
+        }
+        const bool two_step = nh_dir >= kHatchCross;
+        if (nh_dir == kHatchHorizontal) ns_launch_filter(stream, ns_lit.p, ns_depth.p, ns_plane.p, d->width, d->height);
+        else nh_launch_filter(nh_dir, stream, ns_lit.p, ns_depth.p, two_step ? nh_first.p : nullptr, ns_plane.p, d->width, d->height);
         prof_end(prof);
         ATN_HIP(hipGetLastError());
         ns_saved_tex = scene.screen_shadow; ns_saved_w = scene.ss_w; ns_saved_h = scene.ss_h;
@@ -3498,6 +3585,7 @@ public:
         ns_swapped = true;
         ns_rendered = true;
         ns_last[0] = ns_plane.p; ns_last[1] = ns_lit.p; ns_last[2] = ns_depth.p;
+        ns_last_base = nh_base; nh_last_first = two_step ? nh_first.p : ns_plane.p;
         ns_last_w = d->width; ns_last_h = d->height;
         return ATN_OK;
     }
@@ -3515,6 +3603,7 @@ public:
         if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
         if (!ns_rendered) return fail(ATN_ERR_INVALID_ARG, "no frame has run the NPR shadow pre-pass");
         if (which < 0 || which > 2) return fail(ATN_ERR_INVALID_ARG, "no such NPR shadow plane");
+        if (which == 1 && ns_last_base == 0) return fail(ATN_ERR_INVALID_ARG, "the last pre-pass filtered AO values (atn_npr_hatching_set base 0): there is no lit bit; atn_npr_hatching_download(0) has the source plane");
         if ((size_t)n != (size_t)ns_last_w * ns_last_h) return fail(ATN_ERR_INVALID_ARG, "NPR shadow planes have width x height floats");
         { const int s = settle(); if (s) return s; }
         ATN_HIP(hipMemcpy(out, ns_last[which], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
@@ -3533,6 +3622,37 @@ public:
         ATN_HIP(hipMemcpyAsync(ns_f_lit.p, lit, n * sizeof(float), hipMemcpyHostToDevice, stream));
         ATN_HIP(hipMemcpyAsync(ns_f_depth.p, depth, n * sizeof(float), hipMemcpyHostToDevice, stream));
         ns_launch_filter(stream, ns_f_lit.p, ns_f_depth.p, ns_f_out.p, w, h);
+        ATN_HIP(hipGetLastError());
+        ATN_HIP(hipMemcpyAsync(out, ns_f_out.p, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        return ATN_OK;
+    }
+
+    // 0 the unfiltered source plane of the last pre-pass (AO values / the bit as 0.0 / 1.0), 1 its first step's plane
+    int nh_download(int32_t which, float* out, uint32_t n)
+    {
+        if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
+        if (!ns_rendered) return fail(ATN_ERR_INVALID_ARG, "no frame has run the NPR shadow pre-pass");
+        if (which != 0 && which != 1) return fail(ATN_ERR_INVALID_ARG, "no such NPR hatching plane");
+        if ((size_t)n != (size_t)ns_last_w * ns_last_h) return fail(ATN_ERR_INVALID_ARG, "NPR hatching planes have width x height floats");
+        { const int s = settle(); if (s) return s; }
+        ATN_HIP(hipMemcpy(out, which == 0 ? ns_last[1] : nh_last_first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        return ATN_OK;
+    }
+
+    // the filter of one direction alone over uploaded planes (a stage entry for tests)
+    int nh_filter(const float* src, const float* depth, int32_t w, int32_t h, int32_t direction, float* out)
+    {
+        if (!src || !depth || !out) return fail(ATN_ERR_INVALID_ARG, "null plane");
+        if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(ATN_ERR_INVALID_ARG, "NPR hatching filter: sizes are 1..16384 per side");
+        if (direction < kHatchNone || direction > kHatchOrthogonalCross) return fail(ATN_ERR_INVALID_ARG, "NPR hatching filter: direction is 0..5");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        const size_t n = (size_t)w * h;
+        ATN_HIP(ns_f_lit.resize(n)); ATN_HIP(ns_f_depth.resize(n)); ATN_HIP(ns_f_out.resize(n)); ATN_HIP(nh_f_first.resize(n));
+        ATN_HIP(hipMemcpyAsync(ns_f_lit.p, src, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipMemcpyAsync(ns_f_depth.p, depth, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        nh_launch_filter(direction, stream, ns_f_lit.p, ns_f_depth.p, nh_f_first.p, ns_f_out.p, w, h);
         ATN_HIP(hipGetLastError());
         ATN_HIP(hipMemcpyAsync(out, ns_f_out.p, n * sizeof(float), hipMemcpyDeviceToHost, stream));
         ATN_HIP(hipStreamSynchronize(stream));
@@ -3994,6 +4114,26 @@ int atn_ao_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.ao
 int atn_ao_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.ao_download(which, out_host); }); }
 int atn_npr_shadow_set_mode(atn_ctx* ctx, int32_t mode) { CTX_QUIET_OR_FAIL(ctx); return ctx->r.ns_set_mode(mode); }
 int atn_npr_shadow_download(atn_ctx* ctx, int32_t which, float* out_host, uint32_t n) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.ns_download(which, out_host, n); }); }
+int atn_npr_hatching_set(atn_ctx* ctx, int32_t base, int32_t direction, int32_t ao_num_rays, float ao_radius)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    return ctx->r.nh_set(base, direction, ao_num_rays, ao_radius);
+}
+int atn_npr_hatching_get(atn_ctx* ctx, int32_t* base, int32_t* direction, int32_t* ao_num_rays, float* ao_radius)
+{
+    if (!ctx) return ATN_ERR_INVALID_ARG;
+    if (base) *base = ctx->r.nh_base;
+    if (direction) *direction = ctx->r.nh_dir;
+    if (ao_num_rays) *ao_num_rays = ctx->r.nh_num_rays;
+    if (ao_radius) *ao_radius = ctx->r.nh_radius;
+    return ATN_OK;
+}
+int atn_npr_hatching_filter(atn_ctx* ctx, const float* src, const float* depth, int32_t w, int32_t h, int32_t direction, float* out_host)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.nh_filter(src, depth, w, h, direction, out_host); });
+}
+int atn_npr_hatching_download(atn_ctx* ctx, int32_t which, float* out_host, uint32_t n) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.nh_download(which, out_host, n); }); }
 int atn_npr_shadow_filter(atn_ctx* ctx, const float* lit, const float* depth, int32_t w, int32_t h, float* out_host)
 {
     CTX_QUIET_OR_FAIL(ctx);

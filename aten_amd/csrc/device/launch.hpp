@@ -151,6 +151,12 @@ void ns_launch_primary(const TraceLaunch& l, hipStream_t st, const PathBuffers& 
 void ns_launch_rays(const NsLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const NsArgs& na);
 void ns_launch_filter(hipStream_t st, const float* lit, const float* depth, float* out, int32_t width, int32_t height);
 
+// ---- npr_hatching.hip (device/npr_hatching.hpp) ----
+// the AO rays' answers (ao_launch_primary / ao_launch_rays over `aa`) folded into the pre-pass's source and depth planes, per slot
+void nh_launch_resolve(uint32_t slot_grid, hipStream_t st, const FrameParams& fp, const AoArgs& aa, float* src, float* depth);
+// the filter of one HatchingShadowDirection (0..5) over w x h pixels; `first` receives the first step's plane of directions 4 / 5
+void nh_launch_filter(int32_t direction, hipStream_t st, const float* src, const float* depth, float* first, float* out, int32_t width, int32_t height);
+
 // ---- volume.hip (device/volume.hpp) ----
 struct VolArgs;
 // one iteration's volume launches: the closest-hit walk and the connection walk through the frame's walk (the plan's walk, LDS copy and

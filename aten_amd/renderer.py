@@ -629,6 +629,42 @@ class PathTracing:
         self._check(self._l.atn_npr_shadow_filter(self._ctx, l.ctypes.data, d.ctypes.data, l.shape[1], l.shape[0], out.ctypes.data))
         return out
 
+    # ---- NPR hatching shadows (idaten::NPRPathTracing's HatchingShadowBase x HatchingShadowDirection; docs/NPR_HATCHING.md)
+    HATCH_BASES = ("ao", "shadow_ray")
+    HATCH_DIRECTIONS = ("none", "horizontal", "vertical", "orthogonal", "cross", "orthogonal_cross")
+
+    def set_npr_hatching(self, base=1, direction=1, ao_num_rays=1, ao_radius=1.0):
+        """What the mode-1 pre-pass filters and how.  base: 0 / 'ao' the AO value at the primary hit (ao_num_rays rays of ao_radius),
+        1 / 'shadow_ray' the bounce-0 lit bit (default).  direction: 0..5 or a name of HATCH_DIRECTIONS (default 1, the row)."""
+        b = self.HATCH_BASES.index(base) if isinstance(base, str) else int(base)
+        d = self.HATCH_DIRECTIONS.index(direction) if isinstance(direction, str) else int(direction)
+        self._check(self._l.atn_npr_hatching_set(self._ctx, b, d, int(ao_num_rays), float(ao_radius)))
+
+    def npr_hatching(self):
+        """The settings: dict base, direction, ao_num_rays, ao_radius."""
+        b, d, n, r = C.c_int32(), C.c_int32(), C.c_int32(), C.c_float()
+        self._check(self._l.atn_npr_hatching_get(self._ctx, C.byref(b), C.byref(d), C.byref(n), C.byref(r)))
+        return dict(base=b.value, direction=d.value, ao_num_rays=n.value, ao_radius=r.value)
+
+    def npr_hatching_buffer(self, which):
+        """Planes of the last frame that ran the pre-pass, float32 [h, w]: 'source' / 0 what was filtered (AO values, or the bit as
+        0.0 / 1.0), 'first' / 1 the first step's plane (the final plane of a one-step direction)."""
+        k = ("source", "first").index(which) if isinstance(which, str) else int(which)
+        out = np.empty((self.height, self.width), np.float32)
+        self._check(self._l.atn_npr_hatching_download(self._ctx, k, out.ctypes.data, out.size))
+        return out
+
+    def npr_hatching_filter(self, src, depth, direction):
+        """The filter of one direction alone over host planes [h, w]."""
+        s = np.ascontiguousarray(src, np.float32)
+        d = np.ascontiguousarray(depth, np.float32)
+        if s.shape != d.shape or s.ndim != 2:
+            raise ValueError("src and depth are [h, w] planes of one shape")
+        k = self.HATCH_DIRECTIONS.index(direction) if isinstance(direction, str) else int(direction)
+        out = np.empty_like(s)
+        self._check(self._l.atn_npr_hatching_filter(self._ctx, s.ctypes.data, d.ctypes.data, s.shape[1], s.shape[0], k, out.ctypes.data))
+        return out
+
     def svgf_denoise(self, width, height, frame=0, compute_motion=False, stages=False, download=True, profile=False):
         """The filter passes of OnRender on the buffers as they stand (svgf_upload / a previous path pass)."""
         d = Destination(width, height, 1, 1, 1, frame, 0, 1, 0, int(profile))

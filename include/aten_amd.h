@@ -566,6 +566,28 @@ int atn_ao_download(atn_ctx* ctx, int32_t which, void* out_host);
 int atn_npr_shadow_set_mode(atn_ctx* ctx, int32_t mode);
 int atn_npr_shadow_download(atn_ctx* ctx, int32_t which, float* out_host, uint32_t n);
 int atn_npr_shadow_filter(atn_ctx* ctx, const float* lit, const float* depth, int32_t w, int32_t h, float* out_host);
+/* ---- NPR hatching shadows (idaten::NPRPathTracing's HatchingShadowBase x HatchingShadowDirection, src/libidaten/npr/
+ * npr_pathtracing.h:14-26, npr_pathtracing.cu:283-347,351-386,519-605; docs/NPR_HATCHING.md) ----
+ * What the pre-pass of atn_npr_shadow_set_mode(1) filters, and how.
+ *   atn_npr_hatching_set: base 0 = AO (ShandeByAO at the primary hit, ao_num_rays rays of ao_radius, drawn from the AO renderer's own
+ *                    sampler), 1 = ShadowRay (default: the bounce-0 lit bit).  direction 0 None, 1 Horizontal (default), 2 Vertical,
+ *                    3 Orthogonal, 4 Cross (Horizontal x Vertical), 5 OrthogonalCross (diagonal x anti-diagonal); the two-step
+ *                    products are darkened by `v < 1 ? v * 0.5 : v`.  ao_num_rays 1..64, ao_radius > 0 and finite (read with base 0
+ *                    only).  Anything else: ATN_ERR_INVALID_ARG, nothing changes.  Waits for the frames in flight; takes effect for
+ *                    the mode-1 frames of atn_render and atn_npr_render; context state, kept across atn_upload_scene.  The scene's
+ *                    enable_shadowray_base_stylized_shadow is not overridden in either base.  With base 0 a frame that would list more
+ *                    than 2^28 AO rays is ATN_ERR_UNSUPPORTED.
+ *   atn_npr_hatching_get: the four settings (null pointers are skipped).
+ *   atn_npr_hatching_filter: the filter of `direction` alone over host planes src / depth [h][w] -> out_host [h][w]; w, h 1..16384.
+ *   atn_npr_hatching_download: planes of the last frame that ran the pre-pass, n = width * height floats: which = 0 the unfiltered
+ *                    source plane (AO values with base 0, the bit as 0.0 / 1.0 with base 1), 1 the first step's plane (the final plane
+ *                    of a one-step direction).  ATN_ERR_INVALID_ARG before such a frame and for another n.
+ * atn_npr_shadow_download(0) is the final plane whatever the settings and (2) the depth; (1) is ATN_ERR_INVALID_ARG after a base-0
+ * frame (there is no bit).  Additive entry points: atn_abi_version stays 3. */
+int atn_npr_hatching_set(atn_ctx* ctx, int32_t base, int32_t direction, int32_t ao_num_rays, float ao_radius);
+int atn_npr_hatching_get(atn_ctx* ctx, int32_t* base, int32_t* direction, int32_t* ao_num_rays, float* ao_radius);
+int atn_npr_hatching_filter(atn_ctx* ctx, const float* src, const float* depth, int32_t w, int32_t h, int32_t direction, float* out_host);
+int atn_npr_hatching_download(atn_ctx* ctx, int32_t which, float* out_host, uint32_t n);
 /* The filter passes alone (everything of OnRender after the sample loop, svgf.cpp:515-637) on whatever the
  * path pass -- or atn_svgf_upload -- left in the buffers: contributions (which = 14: contrib.xyz, sample count),
  * the current AOVs (0, 1), primary hit positions (10), motion/depth (9).  This is how a caller that already has a

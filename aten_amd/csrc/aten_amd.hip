@@ -179,6 +179,7 @@ public:
     bool opt_node_layout = true, opt_planar_lights = true;      // ATEN_AMD_NODE_LAYOUT / ATEN_AMD_PLANAR_LIGHTS at creation; atn_set_upload_options
     bool env_atrous4 = true;    // SVGF a-trous levels with four pixels per thread (k_svgf_atrous4); ATEN_AMD_SVGF_ATROUS4=0: one pixel per thread
     int env_shade_waves = 0;    // ATEN_AMD_SHADE_WAVES=4|5 forces the k_shade_wn flavour (default: plan_pass)
+    bool env_shadow_plain = true;       // ATEN_AMD_SHADOW_PLAIN=0 (experiments, tests): DevScene::shadow_plain stays off, every shadow job reads its light record
     bool rr_lookahead_twin = true;      // ATEN_AMD_RR_LOOKAHEAD_TWIN=0 (experiments): doomed rays stop at their first hit on the list as given
     int rr_lookahead = 1;       // ATEN_AMD_RR_LOOKAHEAD / atn_set_rr_lookahead: 0 = off, 1 = render()'s serial passes on scenes that qualify
                                 // (counted frames keep the reference's accounting: off), 2 = counted frames too (atn_rr_lookahead_stats)
@@ -819,6 +820,7 @@ public:
         // environment switches (README.md "Environment variables": which are supported controls, which are experiment hooks);
         // read once here, never inside a frame
         if (const char* e = std::getenv("ATEN_AMD_FUSE")) fuse_traces = e[0] != '0';
+        if (const char* e = std::getenv("ATEN_AMD_SHADOW_PLAIN")) env_shadow_plain = e[0] != '0';
         if (const char* e = std::getenv("ATEN_AMD_SVGF_ATROUS4")) env_atrous4 = e[0] != '0';     // 0: the one-pixel-per-thread a-trous kernel
         if (const char* e = std::getenv("ATEN_AMD_SHADE_WAVES")) { const int v = std::atoi(e); if (v == 4 || v == 5) env_shade_waves = v; }   // else: plan_pass
         if (const char* e = std::getenv("ATEN_AMD_LDS_NODES")) env_lds_nodes = std::atoi(e) != 0;
@@ -886,6 +888,7 @@ public:
         ATN_HIP(hipGetLastError());
         ATN_HIP(hipStreamSynchronize(stream));      // `img` is pageable host memory
         scene = img.params;
+        if (!env_shadow_plain) scene.shadow_plain = 0;
         scene.nodes = nodes.p; scene.tris = tris.p; scene.shade_tris = shade_tris.p; scene.vtx_pos = vtx_pos.p; scene.vtx_nml = vtx_nml.p;
         scene.objects = objects.p; scene.matrices = matrices.p; scene.materials = materials.p; scene.carpaint = carpaint.p;
         scene.toon = toon.p; scene.npr_lights = npr_lights.p; scene.screen_shadow = img.screen_shadow.empty() ? nullptr : screen_shadow.p;
@@ -1054,6 +1057,7 @@ public:
         ATN_HIP(hipMemcpyAsync(lights.p + first, dev.data(), (size_t)n * sizeof(atn_light_param), hipMemcpyHostToDevice, stream));
         ATN_HIP(hipStreamSynchronize(stream));
         scene.nee_deferral = nee_deferral_class(scene.material_set, src.lights.data(), (uint32_t)src.lights.size());
+        scene.shadow_plain = env_shadow_plain ? shadow_plain_class(src.lights.data(), (uint32_t)src.lights.size()) : 0;
         return ATN_OK;
     }
     int update_texture(int32_t texid, const atn_texture_desc* t)

@@ -1341,10 +1341,22 @@ struct ShadowJob {
     DevScene sc;
     float t_min;
     ATN_DEV void fetch(uint32_t j, float4& a, float4& b, float& stop_t) const { fetch_slot(pb.shadow_q[j], a, b, stop_t); }
+    // PLAIN (DevScene::shadow_plain, wave-uniform; the ALPHA = false, serial-loop flavour only): every light is infinite and has no
+    // object, so the rules below give stop_t = +inf and `visible = !isHit` for every ray, whichever light it names: fetch reads no
+    // light record, and a blocked ray's finish touches no memory (docs/TRACE_RAY_COST.md).
+    static constexpr bool kPlain = !ALPHA && !REGEN;
     ATN_DEV void fetch_slot(uint32_t slot, float4& a, float4& b, float& stop_t) const
     {
         const float4 so = pb.sh_o[slot], sd = pb.sh_d[slot];
         const f3 dir = normalize(mk3(sd));      // aten::ray(org, dir) constructor re-normalises (pathtracing_impl.h:380)
+        if constexpr (kPlain) {
+            if (sc.shadow_plain) {
+                stop_t = kInf;
+                a = make_float4(so.x, so.y, so.z, so.w - kEps);
+                b = make_float4(dir.x, dir.y, dir.z, __uint_as_float(slot));
+                return;
+            }
+        }
         // scene::hitLight (scene/scene.h:118-131) needs the closest hit's OBJECT only for area lights.  For an
         // infinite light without object its answer is exactly `!isHit`: any accepted hit settles it.  For a point /
         // spot light it is `hit.t > distToLight`: the walk's t_max caps only box tests, so a triangle BEHIND the light
@@ -1381,6 +1393,16 @@ struct ShadowJob {
     ATN_DEV bool finish(uint32_t payload, const Hit& h, bool isHit, float4& ra, float4& rb, float& rstop) const
     {
         const uint32_t slot = payload & kShadowSlotMask;
+        if constexpr (kPlain) {
+            if (sc.shadow_plain) {
+                if (isHit) return false;
+                // a deferred-NEE frame: as below
+                if (pb.nee_reached) { pb.nee_reached[slot] = 1u; return false; }
+                const float4 lc = pb.sh_c[slot], c = pb.contrib[slot];
+                pb.contrib[slot] = make_float4(c.x + lc.x, c.y + lc.y, c.z + lc.z, 0.0F);
+                return false;
+            }
+        }
         const uint32_t lookups = (payload >> 27) & 15u;
         // one 16-byte read settles the common case: the light contribution carries the light bits; the distance and
         // the ray itself are read only by the branches that need them

@@ -146,6 +146,8 @@ struct DevScene {
     int32_t rr_lookahead;               // 1 = the roulette look-ahead is valid on this scene (host/scene_upload.hpp: rr_lookahead_valid; kernels.hpp, F_DOOMED)
     int32_t nee_deferral;               // the deferred NEE (host/scene_upload.hpp: nee_deferral_class; kernels.hpp, PathBuffers::nee_reached): bit 0 = the
                                         // scene qualifies, bit 1 = ... and every light is infinite (the default policy defers)
+    int32_t shadow_plain;               // 1 = every light is infinite and none is an area light with an object (host/scene_upload.hpp: shadow_plain_class):
+                                        // a shadow ray reaches its light iff it hits nothing, whichever light it is (kernels.hpp, ShadowJob)
 };
 
 } // namespace atn

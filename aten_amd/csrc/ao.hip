@@ -16,7 +16,7 @@ void ao_launch_primary(const TraceLaunch& l, hipStream_t st, const PathBuffers& 
     else hipLaunchKernelGGL((k_ao_primary<false>), dim3(l.grid), dim3(l.block), 0, st, pb, sc, aa);
 }
 
-void ao_launch_rays(const AoLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const AoArgs& aa)
+void ao_launch_rays(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const AoArgs& aa)
 {
     hipLaunchKernelGGL(k_ao_shade, dim3(l.grid), dim3(256), 0, st, pb, sc, fp, aa);
     // (the refill walk over an LDS copy -- only ever forced on a small scene -- walks global memory here, as the NPR sample rays do)
@@ -25,7 +25,7 @@ void ao_launch_rays(const AoLaunch& l, hipStream_t st, const PathBuffers& pb, co
     else hipLaunchKernelGGL((k_ao_trace<false, false>), dim3(l.trace_grid), dim3(l.trace_block), 0, st, sc, aa);
 }
 
-void ao_launch_resolve(const AoLaunch& l, hipStream_t st, const FrameParams& fp, const AoArgs& aa, float4* film, float4* tile_out)
+void ao_launch_resolve(const RayLaunch& l, hipStream_t st, const FrameParams& fp, const AoArgs& aa, float4* film, float4* tile_out)
 {
     hipLaunchKernelGGL(k_ao_resolve, dim3(l.slot_grid), dim3(256), 0, st, fp, aa, film, tile_out);
     if (aa.filter) hipLaunchKernelGGL(k_ao_bilateral, dim3(l.slot_grid), dim3(256), 0, st, fp, aa, film, tile_out);

@@ -67,6 +67,50 @@ inline bool streams_run_side_by_side(hipStream_t a, hipStream_t b, bool& ok)
     return false;
 }
 
+// An AO ray list (device/ao.hpp's layout): a frame's rays and their answers, the per-slot work words, the per-pixel state, the per-row
+// minima and the counters.  The AO renderer keeps one in the context, NPR hatching's AO base one per bank; the value and depth planes
+// are the holder's (the two point them at different buffers).
+struct AoRayList {
+    DevBuf<float4> ray_o, ray_d, ray_n, ray_res;
+    DevBuf<uint32_t> work, row_min, counters, state;
+    // would ensure() replace a buffer?  (with frames in flight the caller waits for them first)
+    bool would_grow(size_t n_rays, size_t n_slots, int32_t w, int32_t h) const
+    {
+        return n_rays > ray_o.n || n_slots > work.n || (size_t)w * h > state.n || (size_t)h > row_min.n || !counters.p;
+    }
+    hipError_t ensure(size_t n_rays, size_t n_slots, int32_t w, int32_t h)
+    {
+        hipError_t e = hipSuccess;
+        for (DevBuf<float4>* b : { &ray_o, &ray_d, &ray_n, &ray_res }) if ((e = b->resize(n_rays)) != hipSuccess) return e;
+        if ((e = work.resize(n_slots)) != hipSuccess || (e = state.resize((size_t)w * h)) != hipSuccess) return e;
+        if ((e = row_min.resize((size_t)h)) != hipSuccess) return e;
+        return counters.resize(kAoCounters);
+    }
+    // the list's part of a frame's AoArgs
+    AoArgs args() const
+    {
+        AoArgs aa{};
+        aa.ray_o = ray_o.p; aa.ray_d = ray_d.p; aa.ray_n = ray_n.p; aa.ray_res = ray_res.p;
+        aa.work = work.p; aa.row_min = row_min.p; aa.counters = counters.p; aa.state = state.p;
+        return aa;
+    }
+};
+
+// Orders consecutive frames that share state across the banks' streams: a frame records when it is done with the state, the next one
+// waits for that record.  The event is created at the first record; the holder decides when to wait and when the flag is void.
+struct FrameFence {
+    DevEvent ev;
+    bool pending = false;
+    hipError_t wait(hipStream_t st) const { return pending ? hipStreamWaitEvent(st, ev, 0) : hipSuccess; }
+    hipError_t record(hipStream_t st)
+    {
+        hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev.h, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ev, st);
+        if (e == hipSuccess) pending = true;
+        return e;
+    }
+};
+
 // Frames in flight (atn_set_frames_in_flight): everything a frame's kernels write except the film lives in a BANK --
 // path state, queues, counters, tile buffer, and the streams / events the frame runs on.  PathTracing derives from Bank: its
 // base IS the current bank; render() rotates it with the spare banks, so frame f + 1 is enqueued on another stream while frame
@@ -90,8 +134,7 @@ struct Bank {
     // NPR hatching (atn_npr_hatching_set, docs/NPR_HATCHING.md): the first step's plane of a two-step direction, and with the AO base
     // the bank's own AO ray list and per-slot / per-pixel words (device/ao.hpp's layout).  ns_lit holds the source plane of either base.
     DevBuf<float> nh_first;
-    DevBuf<float4> nh_ray_o, nh_ray_d, nh_ray_n, nh_ray_res;
-    DevBuf<uint32_t> nh_work, nh_row_min, nh_counters, nh_state;
+    AoRayList nh_list;
     uint32_t n_slots = 0;
     int32_t counters_depth = 0;
     uint64_t bank_epoch = 0;        // the scene update this bank's stream is behind (wait_scene_epoch)
@@ -457,7 +500,7 @@ public:
         if (sv_stream) ATN_HIP(hipStreamSynchronize(sv_stream));
         if (scene_stream) ATN_HIP(hipStreamSynchronize(scene_stream));
         film_pending = false;
-        ta_pending = false;     // (the display tail runs on one of the streams above)
+        ta_fence.pending = false;       // (the display tail runs on one of the streams above)
         sv_prepare_recorded[0] = sv_prepare_recorded[1] = false;
         return ATN_OK;
     }
@@ -530,13 +573,13 @@ public:
     // positions and matrices as the last frame rendered with compute_motion = 2 saw them.  One per context -- SVGF and ReSTIR frames
     // share it, and it belongs to no scene set: every update logs the ranges of SB_VTX_POS / SB_MATRICES it writes (the offsets are
     // the same in every set), and a mode-2 frame copies exactly those, from the set it reads, behind its motion pass.  Frames are
-    // ordered through gm_ev: a frame's motion pass reads the history only after the previous frame's copies, and writes it only
+    // ordered through gm_fence: a frame's motion pass reads the history only after the previous frame's copies, and writes it only
     // after the previous frame's reads -- on the device, frame after frame, like the film.
-    bool gm_on = false, gm_pending = false;
+    bool gm_on = false;
     DevBuf<float4> gm_vtx, gm_mtx;
     uint32_t gm_mtx_quads = 0;                  // matrices rows the history holds (scene.mtx_quads when it was last made equal)
     std::vector<SceneRange> gm_dirty;           // written since the last mode-2 frame
-    DevEvent gm_ev;                 // the last mode-2 frame is done with the history
+    FrameFence gm_fence;            // the last mode-2 frame is done with the history
     DevBuf<float4> gm_ids[2], gm_rs_ids;        // ids planes: SVGF's per hand-over slot, ReSTIR's
     float4* gm_capture = nullptr;               // run_paths: where the frame's bounce-0 hit records go (null: not captured)
     bool gm_sv_ids[2] = { false, false }, gm_rs_has_ids = false;       // the plane holds a frame's ids
@@ -587,7 +630,7 @@ public:
         ATN_HIP(hipStreamSynchronize(stream));
         gm_mtx_quads = scene.mtx_quads;
         gm_dirty.clear();
-        gm_pending = false;
+        gm_fence.pending = false;
         return ATN_OK;
     }
     int set_geometry_motion(int32_t on)
@@ -595,14 +638,13 @@ public:
         ATN_HIP(hipSetDevice(device));
         { int q = quiesce(); if (q) return q; }
         if (!on) {
-            gm_on = false; gm_dirty.clear(); gm_pending = false;
+            gm_on = false; gm_dirty.clear(); gm_fence.pending = false;
             gm_vtx.release(); gm_mtx.release(); gm_ids[0].release(); gm_ids[1].release(); gm_rs_ids.release();
             gm_sv_ids[0] = gm_sv_ids[1] = gm_rs_has_ids = false;
             return ATN_OK;
         }
         if (scene_in_place) return fail(ATN_ERR_UNSUPPORTED, "geometry motion needs to see every scene update: not once the caller writes the scene arrays itself (atn_scene_device_arrays)");
         if (gm_on) return ATN_OK;
-        if (!gm_ev) ATN_HIP(hipEventCreateWithFlags(&gm_ev.h, hipEventDisableTiming));
         gm_on = true;
         return has_scene ? gm_reset_history() : ATN_OK;
     }
@@ -610,7 +652,7 @@ public:
     // matrices filled in; the scene and the history are added here.
     int gm_motion_pass(MotionArgs ma, int32_t width, int32_t height)
     {
-        if (frames_in_flight > 1 && gm_pending) ATN_HIP(hipStreamWaitEvent(stream, gm_ev, 0));
+        if (frames_in_flight > 1) ATN_HIP(gm_fence.wait(stream));
         // another number of matrices (instances added / removed): no previous matrix to pair with -- object motion is zero this frame
         if (scene.mtx_quads != gm_mtx_quads) {
             if (matrices.n > gm_mtx.n) {
@@ -628,7 +670,7 @@ public:
         ma.width = width; ma.height = height;
         ma.n_objects = (uint32_t)objects.n; ma.n_tris = (uint32_t)(n_scene_tris < tris.n ? n_scene_tris : tris.n);
         ma.n_vtx = (uint32_t)(n_scene_vtx < gm_vtx.n ? n_scene_vtx : gm_vtx.n); ma.h_mtx_quads = (uint32_t)(gm_mtx_quads < gm_mtx.n ? gm_mtx_quads : gm_mtx.n);
-        motion_launch_geometry(motion_launch(width, height), stream, ma);
+        motion_launch_geometry(tile_launch(width, height), stream, ma);
         std::memcpy(gm_w2c, ma.w2c, sizeof(gm_w2c)); std::memcpy(gm_prev_w2c, ma.prev_w2c, sizeof(gm_prev_w2c));
         gm_stats[0]++;
         // the history := the scene this frame saw: the union of the logged ranges (two ticks between two frames wrote the same ones)
@@ -645,7 +687,7 @@ public:
         }
         gm_dirty.clear();
         ATN_HIP(hipGetLastError());
-        if (frames_in_flight > 1) { ATN_HIP(hipEventRecord(gm_ev, stream)); gm_pending = true; }
+        if (frames_in_flight > 1) ATN_HIP(gm_fence.record(stream));
         return ATN_OK;
     }
     void drop_alt_set()
@@ -1696,12 +1738,14 @@ public:
         return fp;
     }
 
-    // launch geometry: enough waves to fill 256 CUs several times over; grid-stride loops do the rest
-    static uint32_t grid_for(uint32_t n, uint32_t cap_blocks = 256u * 16u)
+    // How the renderers built on the serial pass open a frame (ReSTIR, NPR, AO, the shadow pre-pass): the frame's parameters with the
+    // plan's shade chunks, the bank's buffers uncounted, one serial pass over every slot
+    struct SerialFrame { FrameParams fp; PathBuffers pb; PassPlan plan; };
+    SerialFrame serial_frame(const atn_destination& d)
     {
-        uint32_t b = (n + 255u) / 256u;
-        if (b == 0) b = 1;
-        return b < cap_blocks ? b : cap_blocks;
+        SerialFrame f{ frame_params(d), buffers(false), plan_pass(PassKind::Serial, n_slots) };
+        f.fp.chunk_items = f.plan.shade_items;
+        return f;
     }
 
     // Traversal flavour.  Measured on MI355X: the persistent lane-refilling walk wins
@@ -2028,6 +2072,20 @@ public:
         film_pending = true;
         return ATN_OK;
     }
+    // a frame's accumulated samples into the film, behind the film's last writer (with one sample per pixel k_gather<true> does the
+    // sample's epilogue itself)
+    int gather_film(const atn_destination& d, const PathBuffers& pb, const FrameParams& fp)
+    {
+        const int rc = wait_film();
+        if (rc) return rc;
+        const uint32_t g_all = (n_slots + 255u) / 256u;
+        prof_begin(d.profile != 0, ATN_K_GATHER);
+        if (d.sample == 1) hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
+        else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
+        prof_end(d.profile != 0);
+        ATN_HIP(hipGetLastError());
+        return ATN_OK;
+    }
     int end_film_frame()
     {
         const int rc = frames_in_flight > 1 ? record_scene_read() : ATN_OK;
@@ -2075,13 +2133,8 @@ public:
         { const int e = ns_end_frame(); if (!rc) rc = e; }
         if (rc) return rc;
         fp.slot_begin = 0; fp.slot_end = (int32_t)n_slots;
-        rc = wait_film();
+        rc = gather_film(*d, pb, fp);
         if (rc) return rc;
-        prof_begin(prof, ATN_K_GATHER);
-        if (d->sample == 1) hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
-        else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
-        prof_end(prof);
-        ATN_HIP(hipGetLastError());
         rc = end_film_frame();
         if (rc) return rc;
 
@@ -2330,6 +2383,16 @@ public:
         ATN_HIP(hipStreamSynchronize(stream));
         return ATN_OK;
     }
+    // ... and their common end: buffer `which` of a renderer's table of stage buffers, behind settle()
+    struct StageBuf { const void* p; size_t bytes; };
+    template <size_t N>
+    int download_stage(const StageBuf (&bufs)[N], int32_t which, void* out, const char* no_such)
+    {
+        { const int s = settle(); if (s) return s; }
+        if (which < 0 || (size_t)which >= N) return fail(ATN_ERR_INVALID_ARG, no_such);
+        ATN_HIP(hipMemcpy(out, bufs[which].p, bufs[which].bytes, hipMemcpyDeviceToHost));
+        return ATN_OK;
+    }
 
     int fill4(float4* p, size_t n, float4 v)
     {
@@ -2538,9 +2601,9 @@ public:
     DevBuf<float> rs_dims;
     int32_t rs_w = 0, rs_h = 0, rs_pos = 0, rs_last = 0;     // rs_pos: the current set of the next frame; rs_last: of the last frame
     int32_t rs_mode = 1, rs_candidates = 32, rs_capture = 0;
-    bool rs_pending = false, rs_rendered = false;
+    bool rs_rendered = false;
     bool rs_captured = false, rs_last_own_motion = false;      // the last frame wrote the stage buffers / used rs_motion_own
-    DevEvent rs_ev;     // the last frame's reuse passes are done with the sets (the next frame's shade waits for it)
+    FrameFence rs_fence;        // the last frame's reuse passes are done with the sets (the next frame's shade waits for it)
     FrameMatrices rs_mtx;
 
     int restir_set_options(int32_t mode, int32_t n_candidates)
@@ -2610,14 +2673,10 @@ public:
         if (compute_motion) ATN_HIP(rs_motion_own.resize(n));
         if (geo_motion) ATN_HIP(gm_rs_ids.resize(n));
         gm_rs_has_ids = geo_motion;
-        if (!rs_ev) ATN_HIP(hipEventCreateWithFlags(&rs_ev.h, hipEventDisableTiming));
         const bool prof = d->profile != 0;
         rs_mtx.advance(camera);
 
-        FrameParams fp = frame_params(*d);
-        PathBuffers pb = buffers(false);
-        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
-        fp.chunk_items = plan.shade_items;
+        auto [fp, pb, plan] = serial_frame(*d);
         const int32_t cur = rs_pos, oth = 1 - rs_pos;
         RestirArgs ra{};
         for (int k = 0; k < kRestirResPlanes; k++) { ra.cur.res[k] = rs_res[cur][k].p; ra.other.res[k] = rs_res[oth][k].p; }
@@ -2651,14 +2710,13 @@ public:
                 if (rs_mode == 1 || rs_mode == 2) restir_launch_spatial(scene.material_set, stream, pb, scene, fp, ra);
                 else restir_launch_color(scene.material_set, stream, pb, scene, fp, ra);
                 prof_end(prof);
-                ATN_HIP(hipEventRecord(rs_ev, stream));
-                rs_pending = true;
+                ATN_HIP(rs_fence.record(stream));
             }
             if (b == d->maxDepth) break;
             prof_begin(prof, ATN_K_SHADE);
             if (b == 0) {
                 // the previous frame's reuse passes read the sets, AOVs and visibility plane this frame's bounce 0 overwrites
-                if (rs_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, rs_ev, 0));
+                if (frames_in_flight > 1) ATN_HIP(rs_fence.wait(stream));
                 rc = taa_before_write(stream);      // (the motion plane a display tail may still read: atn_taa_resolve, source 1)
                 if (rc) return rc;
                 restir_launch_shade(scene.material_set, plan.shade_grid, stream, pb, scene, fp, camera, ra);
@@ -2682,13 +2740,8 @@ public:
         rs_rendered = true;
         rs_captured = rs_capture != 0;
         rs_last_own_motion = compute_motion != 0;
-        rc = wait_film();
-        if (rc) return rc;
-        prof_begin(prof, ATN_K_GATHER);
-        hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
-        prof_end(prof);
-        ATN_HIP(hipGetLastError());
-        return end_film_frame(*d, out_host);
+        rc = gather_film(*d, pb, fp);       // (one sample per pixel: k_gather<true>)
+        return rc ? rc : end_film_frame(*d, out_host);
     }
 
     // stage buffers of the last frame (tests): 0 / 1 / 2 the reservoirs after the shade, temporal (visibility) and spatial passes as
@@ -2734,7 +2787,7 @@ public:
     // ------------------------------------------------------------------------------------------------
     // The display tail (aten::TAA + aten::GammaCorrection, device/taa.hpp; docs/TAA.md): frame-persistent state = the history ping-pong
     // (taa.cpp:33-60).  One launch per frame, enqueued on the stream that produced its source and ordered against the next frame's
-    // writers by ta_ev (taa_before_write).
+    // writers by ta_fence (taa_before_write).
     // ------------------------------------------------------------------------------------------------
     DevBuf<float4> ta_hist[2], ta_gamma, ta_up_color, ta_up_motion;
     DevBuf<uint32_t> ta_rgba8;
@@ -2742,20 +2795,19 @@ public:
     int32_t ta_up_w[2] = { 0, 0 }, ta_up_h[2] = { 0, 0 };       // sizes of the uploaded colour / motion planes (source 2)
     bool ta_valid = false;          // a history exists (false: the next frame takes the pass-through rule for every pixel)
     bool ta_resolved = false, ta_has_gamma = false;     // a frame has been resolved at ta_w x ta_h / and it wrote the float gamma plane
-    bool ta_pending = false;
-    DevEvent ta_ev;     // the last display tail has finished (its reads of the source planes and of the history)
+    FrameFence ta_fence;        // the last display tail has finished (its reads of the source planes and of the history)
     hipStream_t ta_last_stream = nullptr;
     static constexpr int32_t kTaaMaxSide = 16384;
 
     // in front of a pass that overwrites a plane the last display tail reads
     int taa_before_write(hipStream_t st)
     {
-        if (ta_pending) ATN_HIP(hipStreamWaitEvent(st, ta_ev, 0));
+        ATN_HIP(ta_fence.wait(st));
         return ATN_OK;
     }
     int taa_idle()
     {
-        if (ta_pending) { ATN_HIP(hipStreamSynchronize(ta_last_stream)); ta_pending = false; }
+        if (ta_fence.pending) { ATN_HIP(hipStreamSynchronize(ta_last_stream)); ta_fence.pending = false; }
         return ATN_OK;
     }
     // a size change forgets the history
@@ -2853,18 +2905,17 @@ public:
             if (rc) return rc;
             ATN_HIP(ta_gamma.resize(n));
         }
-        if (!ta_ev) ATN_HIP(hipEventCreateWithFlags(&ta_ev.h, hipEventDisableTiming));
         // behind the previous display tail (it wrote this frame's history), whatever stream that ran on
-        if (ta_pending && ta_last_stream != st) ATN_HIP(hipStreamWaitEvent(st, ta_ev, 0));
+        if (ta_last_stream != st) ATN_HIP(ta_fence.wait(st));
         a.hist = ta_hist[ta_pos].p; a.out = ta_hist[1 - ta_pos].p;
         a.gamma_f = out_f ? ta_gamma.p : nullptr; a.rgba8 = ta_rgba8.p;
         a.width = w; a.height = h;
         a.enable = (enable != 0 && ta_valid) ? 1 : 0;       // no history: the frame passes through (docs/TAA.md, first frame)
         a.inv_gamma = 1.0F / gamma;
-        taa_launch_resolve(taa_launch(w, h), st, a);
+        taa_launch_resolve(tile_launch(w, h), st, a);
         ATN_HIP(hipGetLastError());
-        ATN_HIP(hipEventRecord(ta_ev, st));
-        ta_pending = true; ta_last_stream = st;
+        ATN_HIP(ta_fence.record(st));
+        ta_last_stream = st;
         ta_pos = 1 - ta_pos;
         ta_valid = true; ta_resolved = true; ta_has_gamma = out_f != nullptr;
         if (out_f) ATN_HIP(hipMemcpyAsync(out_f, ta_gamma.p, n * sizeof(float4), hipMemcpyDeviceToHost, st));
@@ -2887,8 +2938,8 @@ public:
     bool maybe_alpha = false;       // a material has kAttrMaybeAlpha (np_alpha / vl_alpha = that and the config's enable_alpha_blending)
     uint32_t np_slots = 0;
     int32_t np_w = 0, np_h = 0, np_capture = 0, np_depth = 0;
-    bool np_captured = false, np_pending = false;
-    DevEvent np_ev;     // the last NPR frame's kernels are done with the sample-ray state (the next frame waits for it)
+    bool np_captured = false;
+    FrameFence np_fence;        // the last NPR frame's kernels are done with the sample-ray state (the next frame waits for it)
 
     // (of src, the editable scene data as last uploaded or edited; `mats` = the device form of src.materials)
     int npr_decode(const std::vector<DevMaterial>& mats)
@@ -2971,12 +3022,8 @@ public:
         if (rc) return rc;
         // atn_npr_shadow_set_mode(1): the same pre-pass as with lines off (docs/NPR_SHADOW.md)
         if (ns_frame()) { rc = ns_prepass(d); if (rc) return rc; }
-        if (!np_ev) ATN_HIP(hipEventCreateWithFlags(&np_ev.h, hipEventDisableTiming));
         const bool prof = d->profile != 0;
-        FrameParams fp = frame_params(*d);
-        PathBuffers pb = buffers(false);
-        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
-        fp.chunk_items = plan.shade_items;
+        auto [fp, pb, plan] = serial_frame(*d);
         NprArgs na{};
         na.disc_c = np_disc_c.p; na.disc_n = np_disc_n.p; na.desc_p = np_desc_p.p; na.desc_n = np_desc_n.p;
         na.live = np_live.p; na.work = np_work.p; na.hpd = np_hpd.p;
@@ -2987,16 +3034,11 @@ public:
         na.pixel_width = pixel_width_at(camera, 1.0F);
         if (np_capture) { na.st_line = np_st_line.p; na.st_desc = np_st_desc.p; na.st_disc = np_st_disc.p; na.st_dims = np_st_dims.p; }
         // the walk of the sample rays: the frame's walk, LDS copy and block, 8 rays per path
-        NprLaunch nl{};
-        nl.grid = grid_for(n_slots);
-        nl.refill = plan.refill;
-        nl.lds_bytes = plan.lds_bytes;
-        nl.trace_block = plan.refill ? (uint32_t)kTraceBlock : plan.block;
-        nl.trace_grid = plan.refill ? trace_grid(kNprRays * n_slots, true) : grid_for(kNprRays * n_slots) * (256u / plan.block);
+        const RayLaunch nl = ray_launch(plan, n_slots, kNprRays * n_slots, trace_grid(kNprRays * n_slots, true));
 
         const uint32_t g_slots = grid_for(n_slots), g_all = (n_slots + 255u) / 256u;
         // the previous NPR frame (another bank's stream) still reads and writes the sample-ray state
-        if (np_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, np_ev, 0));
+        if (frames_in_flight > 1) ATN_HIP(np_fence.wait(stream));
         if (np_capture) ATN_HIP(hipMemsetAsync(np_st_line.p, 0, (size_t)d->width * d->height * sizeof(float4), stream));
         ATN_HIP(hipMemsetAsync(counters.p, 0, (size_t)4 * counters_depth * 4, stream));
         for (int32_t s = 0; s < d->sample; s++) {
@@ -3028,19 +3070,12 @@ public:
                 prof_end(prof);
             }
         }
-        ATN_HIP(hipEventRecord(np_ev, stream));
-        np_pending = true;
+        ATN_HIP(np_fence.record(stream));
         np_captured = np_capture != 0;
         rc = ns_end_frame();
         if (rc) return rc;
-        rc = wait_film();
-        if (rc) return rc;
-        prof_begin(prof, ATN_K_GATHER);
-        if (d->sample == 1) hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
-        else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
-        prof_end(prof);
-        ATN_HIP(hipGetLastError());
-        return end_film_frame(*d, out_host);
+        rc = gather_film(*d, pb, fp);
+        return rc ? rc : end_film_frame(*d, out_host);
     }
 
     // the film and the sample-ray state of a fresh context
@@ -3060,15 +3095,10 @@ public:
     {
         if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
         if (!np_captured) return fail(ATN_ERR_INVALID_ARG, "the last NPR frame kept no stage buffers: atn_npr_capture(ctx, 1) before the frame");
-        { const int s = settle(); if (s) return s; }
         const size_t n = (size_t)np_w * np_h;
-        switch (which) {
-        case 0: ATN_HIP(hipMemcpy(out, np_st_line.p, n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 1: ATN_HIP(hipMemcpy(out, np_st_desc.p, kNprRays * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 2: ATN_HIP(hipMemcpy(out, np_st_disc.p, 2 * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 3: ATN_HIP(hipMemcpy(out, np_st_dims.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
-        }
-        return fail(ATN_ERR_INVALID_ARG, "no such NPR buffer");
+        const StageBuf bufs[] = { { np_st_line.p, n * sizeof(float4) }, { np_st_desc.p, kNprRays * n * sizeof(float4) },
+                                  { np_st_disc.p, 2 * n * sizeof(float4) }, { np_st_dims.p, n * sizeof(uint32_t) } };
+        return download_stage(bufs, which, out, "no such NPR buffer");
     }
 
     // ------------------------------------------------------------------------------------------------
@@ -3084,10 +3114,9 @@ public:
     std::string vl_refuse;          // why the uploaded scene's media cannot be rendered ("" = they can)
     bool vl_stencil = false, vl_alpha = false, vl_carpaint = false, vl_toon = false;
     float vl_eps_bias = 0.0F;
-    uint32_t vl_slots = 0;
     int32_t vl_w = 0, vl_h = 0, vl_capture = -1, vl_captured = -1;
-    bool vl_rendered = false, vl_pending = false;
-    DevEvent vl_ev;     // the last volume frame's kernels are done with the per-slot state (the next frame waits for it)
+    bool vl_rendered = false;
+    FrameFence vl_fence;        // the last volume frame's kernels are done with the per-slot state (the next frame waits for it)
 
     int vol_decode(const std::vector<DevMaterial>& mats)
     {
@@ -3123,13 +3152,10 @@ public:
 
     int vol_ensure(int32_t w, int32_t h)
     {
-        if (n_slots != vl_slots) {
-            const size_t n = n_slots;
-            ATN_HIP(vl_stack.resize(n)); ATN_HIP(vl_meta.resize(n)); ATN_HIP(vl_hit_t.resize(n)); ATN_HIP(vl_ev_o.resize(n)); ATN_HIP(vl_ev_d.resize(n));
-            ATN_HIP(vl_c_o.resize(n)); ATN_HIP(vl_c_d.resize(n)); ATN_HIP(vl_c_w.resize(n)); ATN_HIP(vl_c_a.resize(n)); ATN_HIP(vl_c_b.resize(n));
-            ATN_HIP(vl_c_c.resize(n)); ATN_HIP(vl_c_stack.resize(n)); ATN_HIP(vl_conn_q.resize(n)); ATN_HIP(vl_segs.resize(n));
-            vl_slots = n_slots;
-        }
+        const size_t ns = n_slots;
+        ATN_HIP(vl_stack.resize(ns)); ATN_HIP(vl_meta.resize(ns)); ATN_HIP(vl_hit_t.resize(ns)); ATN_HIP(vl_ev_o.resize(ns)); ATN_HIP(vl_ev_d.resize(ns));
+        ATN_HIP(vl_c_o.resize(ns)); ATN_HIP(vl_c_d.resize(ns)); ATN_HIP(vl_c_w.resize(ns)); ATN_HIP(vl_c_a.resize(ns)); ATN_HIP(vl_c_b.resize(ns));
+        ATN_HIP(vl_c_c.resize(ns)); ATN_HIP(vl_c_stack.resize(ns)); ATN_HIP(vl_conn_q.resize(ns)); ATN_HIP(vl_segs.resize(ns));
         ATN_HIP(vl_counters.resize(kVolCounters));
         if (vl_capture >= 0) {
             const size_t n = (size_t)w * h;
@@ -3160,12 +3186,11 @@ public:
         if (rc) return rc;
         rc = vol_ensure(d->width, d->height);
         if (rc) return rc;
-        if (!vl_ev) ATN_HIP(hipEventCreateWithFlags(&vl_ev.h, hipEventDisableTiming));
         const bool prof = d->profile != 0;
         FrameParams fp = frame_params(*d);
         PathBuffers pb = buffers(false);
         const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
-        const VolLaunch vlc = vol_launch(plan, n_slots, grid_for(n_slots), grid_for(n_slots));
+        const RayLaunch vlc = ray_launch(plan, n_slots, n_slots, plan.trace_grid);
         VolArgs va{};
         va.med = vl_med.p; va.stack = vl_stack.p; va.meta = vl_meta.p; va.hit_t = vl_hit_t.p; va.ev_o = vl_ev_o.p; va.ev_d = vl_ev_d.p;
         va.c_o = vl_c_o.p; va.c_d = vl_c_d.p; va.c_w = vl_c_w.p; va.c_a = vl_c_a.p; va.c_b = vl_c_b.p; va.c_c = vl_c_c.p; va.c_stack = vl_c_stack.p;
@@ -3177,7 +3202,7 @@ public:
 
         const uint32_t g_slots = grid_for(n_slots), g_all = (n_slots + 255u) / 256u;
         // the previous volume frame (another bank's stream) still reads and writes the per-slot state
-        if (vl_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, vl_ev, 0));
+        if (frames_in_flight > 1) ATN_HIP(vl_fence.wait(stream));
         if (vl_capture >= 0) {
             const size_t n = (size_t)d->width * d->height;
             ATN_HIP(hipMemsetAsync(vl_st_state.p, 0, n * sizeof(uint4), stream)); ATN_HIP(hipMemsetAsync(vl_st_stack.p, 0, n * sizeof(uint4), stream));
@@ -3209,18 +3234,11 @@ public:
             }
         }
         vol_launch_reduce(vlc, stream, fp, va);
-        ATN_HIP(hipEventRecord(vl_ev, stream));
-        vl_pending = true;
+        ATN_HIP(vl_fence.record(stream));
         vl_captured = vl_capture;
         vl_rendered = true;
-        rc = wait_film();
-        if (rc) return rc;
-        prof_begin(prof, ATN_K_GATHER);
-        if (d->sample == 1) hipLaunchKernelGGL((k_gather<true>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
-        else hipLaunchKernelGGL((k_gather<false>), dim3(g_all), dim3(256), 0, stream, pb, fp, film.p, tile_out.p);
-        prof_end(prof);
-        ATN_HIP(hipGetLastError());
-        return end_film_frame(*d, out_host);
+        rc = gather_film(*d, pb, fp);
+        return rc ? rc : end_film_frame(*d, out_host);
     }
 
     int volume_reset()
@@ -3236,16 +3254,10 @@ public:
         if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
         if (!vl_rendered) return fail(ATN_ERR_INVALID_ARG, "no volume frame has been rendered");
         if (which != 4 && vl_captured < 0) return fail(ATN_ERR_INVALID_ARG, "the last volume frame kept no stage buffers: atn_volume_capture(ctx, iteration) before the frame");
-        { const int s = settle(); if (s) return s; }
         const size_t n = (size_t)vl_w * vl_h;
-        switch (which) {
-        case 0: ATN_HIP(hipMemcpy(out, vl_st_state.p, n * sizeof(uint4), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 1: ATN_HIP(hipMemcpy(out, vl_st_stack.p, n * sizeof(uint4), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 2: ATN_HIP(hipMemcpy(out, vl_st_ray.p, 2 * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 3: ATN_HIP(hipMemcpy(out, vl_st_conn.p, 3 * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 4: ATN_HIP(hipMemcpy(out, vl_counters.p + kVolCntFrame, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
-        }
-        return fail(ATN_ERR_INVALID_ARG, "no such volume buffer");
+        const StageBuf bufs[] = { { vl_st_state.p, n * sizeof(uint4) }, { vl_st_stack.p, n * sizeof(uint4) }, { vl_st_ray.p, 2 * n * sizeof(float4) },
+                                  { vl_st_conn.p, 3 * n * sizeof(float4) }, { vl_counters.p + kVolCntFrame, 4 * sizeof(uint32_t) } };
+        return download_stage(bufs, which, out, "no such volume buffer");
     }
 
     int volume_phase_table(float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo, float* out_dir, float* out_eval)
@@ -3271,16 +3283,14 @@ public:
     // Ambient occlusion (aten::AORenderer / idaten::AORenderer, device/ao.hpp; docs/AO.md): the ray list, the per-slot and per-pixel
     // planes.  The state is shared by the banks: an event orders consecutive AO frames.
     // ------------------------------------------------------------------------------------------------
-    DevBuf<float4> ao_ray_o, ao_ray_d, ao_ray_n, ao_ray_res, ao_st_ray, ao_st_ans;
-    DevBuf<uint32_t> ao_work, ao_row_min, ao_counters, ao_state;
+    AoRayList ao_list;
+    DevBuf<float4> ao_st_ray, ao_st_ans;
     DevBuf<float> ao_depth_s, ao_value, ao_depth;
     int32_t ao_num_rays = 1, ao_filter = 0;     // AORenderer's member defaults (aorenderer.h) and its active branch
     float ao_radius = 1.0F;
-    size_t ao_rays_cap = 0;
-    uint32_t ao_slots = 0;
     int32_t ao_w = 0, ao_h = 0, ao_capture = 0;
-    bool ao_captured = false, ao_pending = false, ao_rendered = false;
-    DevEvent ao_ev;     // the last AO frame's kernels are done with the AO state (the next frame waits for it)
+    bool ao_captured = false, ao_rendered = false;
+    FrameFence ao_fence;        // the last AO frame's kernels are done with the AO state (the next frame waits for it)
 
     int ao_set_params(int32_t num_rays, float radius, int32_t filter)
     {
@@ -3296,16 +3306,12 @@ public:
     {
         const size_t r = (size_t)ao_num_rays * n_slots;
         if (r > (size_t)kAoRayMask) return fail(ATN_ERR_UNSUPPORTED, "AO frames list at most 2^28 rays (fewer rays per pixel, or a smaller frame)");
-        if (r > ao_rays_cap) {
-            ATN_HIP(ao_ray_o.resize(r)); ATN_HIP(ao_ray_d.resize(r)); ATN_HIP(ao_ray_n.resize(r)); ATN_HIP(ao_ray_res.resize(r));
-            ao_rays_cap = r;
-        }
-        if (n_slots != ao_slots) { ATN_HIP(ao_work.resize(n_slots)); ATN_HIP(ao_depth_s.resize(n_slots)); ao_slots = n_slots; }
-        if (!ao_counters.p) ATN_HIP(ao_counters.resize(kAoCounters));
+        ATN_HIP(ao_list.ensure(r, n_slots, w, h));
+        ATN_HIP(ao_depth_s.resize(n_slots));
         const size_t n = (size_t)w * h;
         if (w != ao_w || h != ao_h) {
-            ATN_HIP(ao_state.resize(n)); ATN_HIP(ao_value.resize(n)); ATN_HIP(ao_depth.resize(n)); ATN_HIP(ao_row_min.resize((size_t)h));
-            ATN_HIP(hipMemsetAsync(ao_state.p, 0, n * sizeof(uint32_t), stream));
+            ATN_HIP(ao_value.resize(n)); ATN_HIP(ao_depth.resize(n));
+            ATN_HIP(hipMemsetAsync(ao_list.state.p, 0, n * sizeof(uint32_t), stream));
             ATN_HIP(hipMemsetAsync(ao_value.p, 0, n * sizeof(float), stream));
             ATN_HIP(hipMemsetAsync(ao_depth.p, 0, n * sizeof(float), stream));
             ao_w = w; ao_h = h;
@@ -3331,42 +3337,32 @@ public:
         if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "AO frames do not count rays (count_stats must be 0)");
         if (ao_filter && d->break_on_terminate) return fail(ATN_ERR_UNSUPPORTED, "AO: the bilateral filter over rows the CPU renderer leaves unwritten would filter earlier frames' planes: filter = 1 needs break_on_terminate = 0");
         ATN_HIP(hipSetDevice(device));
-        if (frames_in_flight > 1 && (d->width != ao_w || d->height != ao_h || (size_t)ao_num_rays * n_slots > ao_rays_cap || (ao_capture && !ao_st_ans.p))) { rc = quiesce(); if (rc) return rc; }
+        if (frames_in_flight > 1 && (d->width != ao_w || d->height != ao_h || ao_list.would_grow((size_t)ao_num_rays * n_slots, n_slots, d->width, d->height) || (ao_capture && !ao_st_ans.p))) { rc = quiesce(); if (rc) return rc; }
         rc = begin_frame(*d, frames_in_flight > 1);
         if (rc) return rc;
-        if (frames_in_flight > 1 && (size_t)ao_num_rays * n_slots > ao_rays_cap) { rc = quiesce(); if (rc) return rc; }
+        if (frames_in_flight > 1 && ao_list.would_grow((size_t)ao_num_rays * n_slots, n_slots, d->width, d->height)) { rc = quiesce(); if (rc) return rc; }
         rc = ao_ensure(d->width, d->height);
         if (rc) return rc;
-        if (!ao_ev) ATN_HIP(hipEventCreateWithFlags(&ao_ev.h, hipEventDisableTiming));
         const bool prof = d->profile != 0;
-        FrameParams fp = frame_params(*d);
-        PathBuffers pb = buffers(false);
-        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
-        fp.chunk_items = plan.shade_items;
-        AoArgs aa{};
-        aa.ray_o = ao_ray_o.p; aa.ray_d = ao_ray_d.p; aa.ray_n = ao_ray_n.p; aa.ray_res = ao_ray_res.p;
-        aa.work = ao_work.p; aa.depth_s = ao_depth_s.p; aa.row_min = ao_row_min.p; aa.counters = ao_counters.p;
-        aa.state = ao_state.p; aa.value = ao_value.p; aa.depth = ao_depth.p;
+        auto [fp, pb, plan] = serial_frame(*d);
+        AoArgs aa = ao_list.args();
+        aa.depth_s = ao_depth_s.p; aa.value = ao_value.p; aa.depth = ao_depth.p;
         aa.num_rays = ao_num_rays; aa.radius = ao_radius; aa.literal = d->break_on_terminate ? 1 : 0; aa.filter = ao_filter;
         if (ao_capture) { aa.st_ray = ao_st_ray.p; aa.st_ans = ao_st_ans.p; }
         // the walk of the AO rays: the frame's walk, LDS copy and block, num_rays rays per path
         const uint32_t n_rays = (uint32_t)ao_num_rays * n_slots;
-        AoLaunch al{};
-        al.grid = grid_for(n_slots); al.slot_grid = (n_slots + 255u) / 256u;
-        al.refill = plan.refill; al.lds_bytes = plan.lds_bytes;
-        al.trace_block = plan.refill ? (uint32_t)kTraceBlock : plan.block;
-        al.trace_grid = plan.refill ? trace_grid(n_rays, true) : grid_for(n_rays) * (256u / plan.block);
+        const RayLaunch al = ray_launch(plan, n_slots, n_rays, trace_grid(n_rays, true));
 
         // the previous AO frame (another bank's stream) still reads and writes the AO state
-        if (ao_pending && frames_in_flight > 1) ATN_HIP(hipStreamWaitEvent(stream, ao_ev, 0));
+        if (frames_in_flight > 1) ATN_HIP(ao_fence.wait(stream));
         if (ao_capture) {
             const size_t n = (size_t)d->width * d->height;
             ATN_HIP(hipMemsetAsync(ao_st_ray.p, 0, 2 * n * sizeof(float4), stream));
             ATN_HIP(hipMemsetAsync(ao_st_ans.p, 0, n * sizeof(float4), stream));
         }
         ATN_HIP(hipMemsetAsync(counters.p, 0, (size_t)4 * counters_depth * 4, stream));
-        ATN_HIP(hipMemsetAsync(ao_counters.p, 0, (size_t)kAoCounters * sizeof(uint32_t), stream));
-        ATN_HIP(hipMemsetAsync(ao_row_min.p, 0xff, (size_t)d->height * sizeof(uint32_t), stream));
+        ATN_HIP(hipMemsetAsync(ao_list.counters.p, 0, (size_t)kAoCounters * sizeof(uint32_t), stream));
+        ATN_HIP(hipMemsetAsync(ao_list.row_min.p, 0xff, (size_t)d->height * sizeof(uint32_t), stream));
         prof_begin(prof, ATN_K_GEN);
         hipLaunchKernelGGL(k_gen_path, dim3(grid_for(n_slots)), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
         prof_end(prof);
@@ -3382,8 +3378,7 @@ public:
         ao_launch_resolve(al, stream, fp, aa, film.p, tile_out.p);
         prof_end(prof);
         ATN_HIP(hipGetLastError());
-        ATN_HIP(hipEventRecord(ao_ev, stream));
-        ao_pending = true;
+        ATN_HIP(ao_fence.record(stream));
         ao_captured = ao_capture != 0;
         ao_rendered = true;
         return end_film_frame(*d, out_host);
@@ -3394,9 +3389,9 @@ public:
     {
         ATN_HIP(hipSetDevice(device));
         { int q = quiesce(); if (q) return q; }
-        if (ao_state.p) {
+        if (ao_list.state.p) {
             const size_t n = (size_t)ao_w * ao_h;
-            ATN_HIP(hipMemsetAsync(ao_state.p, 0, n * sizeof(uint32_t), stream));
+            ATN_HIP(hipMemsetAsync(ao_list.state.p, 0, n * sizeof(uint32_t), stream));
             ATN_HIP(hipMemsetAsync(ao_value.p, 0, n * sizeof(float), stream));
             ATN_HIP(hipMemsetAsync(ao_depth.p, 0, n * sizeof(float), stream));
         }
@@ -3409,17 +3404,10 @@ public:
         if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
         if (!ao_rendered) return fail(ATN_ERR_INVALID_ARG, "no AO frame has been rendered");
         if (which >= 4 && !ao_captured) return fail(ATN_ERR_INVALID_ARG, "the last AO frame kept no stage buffers: atn_ao_capture(ctx, 1) before the frame");
-        { const int s = settle(); if (s) return s; }
         const size_t n = (size_t)ao_w * ao_h;
-        switch (which) {
-        case 0: ATN_HIP(hipMemcpy(out, ao_state.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 1: ATN_HIP(hipMemcpy(out, ao_value.p, n * sizeof(float), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 2: ATN_HIP(hipMemcpy(out, ao_depth.p, n * sizeof(float), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 3: ATN_HIP(hipMemcpy(out, ao_row_min.p, (size_t)ao_h * sizeof(uint32_t), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 4: ATN_HIP(hipMemcpy(out, ao_st_ray.p, 2 * n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
-        case 5: ATN_HIP(hipMemcpy(out, ao_st_ans.p, n * sizeof(float4), hipMemcpyDeviceToHost)); return ATN_OK;
-        }
-        return fail(ATN_ERR_INVALID_ARG, "no such AO buffer");
+        const StageBuf bufs[] = { { ao_list.state.p, n * sizeof(uint32_t) }, { ao_value.p, n * sizeof(float) }, { ao_depth.p, n * sizeof(float) },
+                                  { ao_list.row_min.p, (size_t)ao_h * sizeof(uint32_t) }, { ao_st_ray.p, 2 * n * sizeof(float4) }, { ao_st_ans.p, n * sizeof(float4) } };
+        return download_stage(bufs, which, out, "no such AO buffer");
     }
 
     // ------------------------------------------------------------------------------------------------
@@ -3471,7 +3459,7 @@ public:
         const size_t n = (size_t)w * h;
         if (nh_dir >= kHatchCross && n > nh_first.n) return true;
         if (nh_base != 0) return false;
-        return (size_t)nh_num_rays * n_slots > nh_ray_o.n || n_slots > nh_work.n || n > nh_state.n || (size_t)h > nh_row_min.n || !nh_counters.p;
+        return nh_list.would_grow((size_t)nh_num_rays * n_slots, n_slots, w, h);
     }
 
     int nh_ensure(int32_t w, int32_t h)
@@ -3481,9 +3469,7 @@ public:
         if (nh_base != 0) return ATN_OK;
         const size_t r = (size_t)nh_num_rays * n_slots;
         if (r > (size_t)kAoRayMask) return fail(ATN_ERR_UNSUPPORTED, "NPR hatching: the AO base lists at most 2^28 rays per frame (fewer rays per pixel, or a smaller frame)");
-        ATN_HIP(nh_ray_o.resize(r)); ATN_HIP(nh_ray_d.resize(r)); ATN_HIP(nh_ray_n.resize(r)); ATN_HIP(nh_ray_res.resize(r));
-        ATN_HIP(nh_work.resize(n_slots)); ATN_HIP(nh_state.resize(n)); ATN_HIP(nh_row_min.resize((size_t)h));
-        ATN_HIP(nh_counters.resize(kAoCounters));
+        ATN_HIP(nh_list.ensure(r, n_slots, w, h));
         return ATN_OK;
     }
 
@@ -3534,44 +3520,30 @@ public:
         rc = nh_ensure(d->width, d->height);
         if (rc) return rc;
         const bool prof = d->profile != 0;
-        FrameParams fp = frame_params(*d);
-        PathBuffers pb = buffers(false);
-        const PassPlan plan = plan_pass(PassKind::Serial, n_slots);
-        fp.chunk_items = plan.shade_items;
-        NsArgs na{};
-        na.depth_s = ns_depth_s.p; na.lit = ns_lit.p; na.depth = ns_depth.p; na.plane = ns_plane.p;
-        NsLaunch nl{};
-        nl.grid = grid_for(n_slots);
-        nl.refill = plan.refill; nl.lds_bytes = plan.lds_bytes;
-        nl.trace_block = plan.refill ? (uint32_t)kTraceBlock : plan.block;
-        nl.trace_grid = plan.refill ? trace_grid(n_slots, true) : grid_for(n_slots) * (256u / plan.block);
+        auto [fp, pb, plan] = serial_frame(*d);
         ATN_HIP(hipMemsetAsync(counters.p, 0, (size_t)4 * counters_depth * 4, stream));
         prof_begin(prof, ATN_K_GEN);
         hipLaunchKernelGGL(k_gen_path, dim3(grid_for(n_slots)), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
         prof_end(prof);
         if (nh_base != 0) {
+            NsArgs na{};
+            na.depth_s = ns_depth_s.p; na.lit = ns_lit.p; na.depth = ns_depth.p; na.plane = ns_plane.p;
             prof_begin(prof, ATN_K_TRACE_CLOSEST);
             ns_launch_primary(trace_launch(plan, 0), stream, pb, scene, na);
             prof_end(prof);
             prof_begin(prof, ATN_K_SHADE);
-            ns_launch_rays(nl, stream, pb, scene, fp, na);
+            ns_launch_rays(ray_launch(plan, n_slots, n_slots, trace_grid(n_slots, true)), stream, pb, scene, fp, na);
         }
         else {
             // the AO base: ShandeByAO at every primary hit through the AO renderer's own kernels and sampler (docs/NPR_HATCHING.md), over
             // this bank's ray list; the source plane (ns_lit) then holds AO values, and there is no lit bit
-            AoArgs aa{};
-            aa.ray_o = nh_ray_o.p; aa.ray_d = nh_ray_d.p; aa.ray_n = nh_ray_n.p; aa.ray_res = nh_ray_res.p;
-            aa.work = nh_work.p; aa.depth_s = ns_depth_s.p; aa.row_min = nh_row_min.p; aa.counters = nh_counters.p;
-            aa.state = nh_state.p; aa.value = ns_lit.p; aa.depth = ns_depth.p;
+            AoArgs aa = nh_list.args();
+            aa.depth_s = ns_depth_s.p; aa.value = ns_lit.p; aa.depth = ns_depth.p;
             aa.num_rays = nh_num_rays; aa.radius = nh_radius;
             const uint32_t n_rays = (uint32_t)nh_num_rays * n_slots;
-            AoLaunch al{};
-            al.grid = nl.grid; al.slot_grid = (n_slots + 255u) / 256u;
-            al.refill = plan.refill; al.lds_bytes = plan.lds_bytes;
-            al.trace_block = nl.trace_block;
-            al.trace_grid = plan.refill ? trace_grid(n_rays, true) : grid_for(n_rays) * (256u / plan.block);
-            ATN_HIP(hipMemsetAsync(nh_counters.p, 0, (size_t)kAoCounters * sizeof(uint32_t), stream));
-            ATN_HIP(hipMemsetAsync(nh_row_min.p, 0xff, (size_t)d->height * sizeof(uint32_t), stream));
+            const RayLaunch al = ray_launch(plan, n_slots, n_rays, trace_grid(n_rays, true));
+            ATN_HIP(hipMemsetAsync(nh_list.counters.p, 0, (size_t)kAoCounters * sizeof(uint32_t), stream));
+            ATN_HIP(hipMemsetAsync(nh_list.row_min.p, 0xff, (size_t)d->height * sizeof(uint32_t), stream));
             prof_begin(prof, ATN_K_TRACE_CLOSEST);
             ao_launch_primary(trace_launch(plan, 0), stream, pb, scene, aa);
             prof_end(prof);
@@ -3614,22 +3586,31 @@ public:
         return ATN_OK;
     }
 
+    // the two filter stage entries behind their argument checks: the planes up, one launch (direction < 0: the pre-pass's own row filter,
+    // else the hatching filter of that direction), the result down
+    int filter_planes(const float* src, const float* depth, int32_t w, int32_t h, int32_t direction, float* out)
+    {
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        const size_t n = (size_t)w * h;
+        ATN_HIP(ns_f_lit.resize(n)); ATN_HIP(ns_f_depth.resize(n)); ATN_HIP(ns_f_out.resize(n));
+        if (direction >= 0) ATN_HIP(nh_f_first.resize(n));
+        ATN_HIP(hipMemcpyAsync(ns_f_lit.p, src, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        ATN_HIP(hipMemcpyAsync(ns_f_depth.p, depth, n * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (direction < 0) ns_launch_filter(stream, ns_f_lit.p, ns_f_depth.p, ns_f_out.p, w, h);
+        else nh_launch_filter(direction, stream, ns_f_lit.p, ns_f_depth.p, nh_f_first.p, ns_f_out.p, w, h);
+        ATN_HIP(hipGetLastError());
+        ATN_HIP(hipMemcpyAsync(out, ns_f_out.p, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        return ATN_OK;
+    }
+
     // the row filter alone over uploaded planes (a stage entry for tests)
     int ns_filter(const float* lit, const float* depth, int32_t w, int32_t h, float* out)
     {
         if (!lit || !depth || !out) return fail(ATN_ERR_INVALID_ARG, "null plane");
         if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(ATN_ERR_INVALID_ARG, "NPR shadow filter: sizes are 1..16384 per side");
-        ATN_HIP(hipSetDevice(device));
-        { int q = quiesce(); if (q) return q; }
-        const size_t n = (size_t)w * h;
-        ATN_HIP(ns_f_lit.resize(n)); ATN_HIP(ns_f_depth.resize(n)); ATN_HIP(ns_f_out.resize(n));
-        ATN_HIP(hipMemcpyAsync(ns_f_lit.p, lit, n * sizeof(float), hipMemcpyHostToDevice, stream));
-        ATN_HIP(hipMemcpyAsync(ns_f_depth.p, depth, n * sizeof(float), hipMemcpyHostToDevice, stream));
-        ns_launch_filter(stream, ns_f_lit.p, ns_f_depth.p, ns_f_out.p, w, h);
-        ATN_HIP(hipGetLastError());
-        ATN_HIP(hipMemcpyAsync(out, ns_f_out.p, n * sizeof(float), hipMemcpyDeviceToHost, stream));
-        ATN_HIP(hipStreamSynchronize(stream));
-        return ATN_OK;
+        return filter_planes(lit, depth, w, h, -1, out);
     }
 
     // 0 the unfiltered source plane of the last pre-pass (AO values / the bit as 0.0 / 1.0), 1 its first step's plane
@@ -3650,17 +3631,7 @@ public:
         if (!src || !depth || !out) return fail(ATN_ERR_INVALID_ARG, "null plane");
         if (w < 1 || h < 1 || w > 16384 || h > 16384) return fail(ATN_ERR_INVALID_ARG, "NPR hatching filter: sizes are 1..16384 per side");
         if (direction < kHatchNone || direction > kHatchOrthogonalCross) return fail(ATN_ERR_INVALID_ARG, "NPR hatching filter: direction is 0..5");
-        ATN_HIP(hipSetDevice(device));
-        { int q = quiesce(); if (q) return q; }
-        const size_t n = (size_t)w * h;
-        ATN_HIP(ns_f_lit.resize(n)); ATN_HIP(ns_f_depth.resize(n)); ATN_HIP(ns_f_out.resize(n)); ATN_HIP(nh_f_first.resize(n));
-        ATN_HIP(hipMemcpyAsync(ns_f_lit.p, src, n * sizeof(float), hipMemcpyHostToDevice, stream));
-        ATN_HIP(hipMemcpyAsync(ns_f_depth.p, depth, n * sizeof(float), hipMemcpyHostToDevice, stream));
-        nh_launch_filter(direction, stream, ns_f_lit.p, ns_f_depth.p, nh_f_first.p, ns_f_out.p, w, h);
-        ATN_HIP(hipGetLastError());
-        ATN_HIP(hipMemcpyAsync(out, ns_f_out.p, n * sizeof(float), hipMemcpyDeviceToHost, stream));
-        ATN_HIP(hipStreamSynchronize(stream));
-        return ATN_OK;
+        return filter_planes(src, depth, w, h, direction, out);
     }
 
     // ≙ idaten::Renderer::reset, renderer.h:40-43
@@ -4441,7 +4412,7 @@ int atn_generate_paths(atn_ctx* ctx, int32_t width, int32_t height, int32_t samp
     C_HIP(r, out.resize((size_t)width * height));
     C_HIP(r, hipMemsetAsync(r.counters.p, 0, (size_t)4 * r.counters_depth * 4, r.stream));
     if (sample > 0) C_HIP(r, hipMemsetAsync(r.done.p, 0, (size_t)r.n_slots * 4, r.stream));
-    hipLaunchKernelGGL(atn::k_gen_path, dim3(PathTracing::grid_for(r.n_slots)), dim3(256), 0, r.stream, pb, fp, r.camera, (const uint32_t*)r.seeds.p);
+    hipLaunchKernelGGL(atn::k_gen_path, dim3(atn::grid_for(r.n_slots)), dim3(256), 0, r.stream, pb, fp, r.camera, (const uint32_t*)r.seeds.p);
     hipLaunchKernelGGL(atn::k_export_rays, dim3((r.n_slots + 255) / 256), dim3(256), 0, r.stream, pb, fp, out.p);
     C_HIP(r, hipMemcpyAsync(out_host, out.p, (size_t)width * height * sizeof(atn_ray), hipMemcpyDeviceToHost, r.stream));
     C_HIP(r, hipStreamSynchronize(r.stream));
@@ -4620,7 +4591,7 @@ int atn_compact2(atn_ctx* ctx, const int32_t* flags_a_host, const int32_t* flags
             C_HIP(r, hipMemcpyAsync(fb.p, flags_b_host, 4 * (size_t)n, hipMemcpyHostToDevice, r.stream));
         }
         C_HIP(r, hipMemsetAsync(c.p, 0, 8, r.stream));
-        uint32_t grid = grid_blocks ? grid_blocks : PathTracing::grid_for((n + (uint32_t)atn::kChunkItems - 1u) / (uint32_t)atn::kChunkItems);
+        uint32_t grid = grid_blocks ? grid_blocks : atn::grid_for((n + (uint32_t)atn::kChunkItems - 1u) / (uint32_t)atn::kChunkItems);
         hipLaunchKernelGGL(atn::k_compact_append, dim3(grid), dim3(256), 0, r.stream, (const int32_t*)fa.p, (const int32_t*)fb.p, n,
                            oa.p, c.p, ob.p, c.p + 1);
         C_HIP(r, hipGetLastError());

@@ -33,6 +33,14 @@ void with_shade_flavour(int material_set, int waves, F&& f)
     }
 }
 
+// launch geometry: enough waves to fill 256 CUs several times over; grid-stride loops do the rest
+inline uint32_t grid_for(uint32_t n, uint32_t cap_blocks = 256u * 16u)
+{
+    uint32_t b = (n + 255u) / 256u;
+    if (b == 0) b = 1;
+    return b < cap_blocks ? b : cap_blocks;
+}
+
 enum class PassKind { Serial, Svgf, Regen };
 
 // What one pass over n paths launches: the serial sample loop of a batch, the SVGF path pass of a batch, or a regenerated burst.
@@ -83,6 +91,35 @@ void launch_trace_fused(const TraceLaunch& l, hipStream_t st, const PathBuffers&
     }, l.refill, sc.any_alpha != 0, l.lds);
 }
 
+// The launches of a renderer that walks a ray list of its own beside the pass (NPR's sample rays, the AO rays, the shadow pre-pass's
+// shadow rays, the volume walks): shade-like kernels over the queue, per-slot kernels, and the list's rays through the frame's walk
+// (the plan's walk, LDS copy and block).
+struct RayLaunch {
+    uint32_t grid;              // blocks of 256, grid-stride over the queue (prep / eval / shade)
+    uint32_t slot_grid;         // blocks of 256 over all slots (begin, resolve, reduce)
+    bool refill;
+    uint32_t trace_grid, trace_block, lds_bytes;
+};
+// `refill_grid`: the refill walk's blocks for the list's n_rays jobs -- PathTracing::trace_grid(n_rays, true), which follows the frames
+// in flight; the volume walks (one job per path) take the plan's own trace_grid
+inline RayLaunch ray_launch(const PassPlan& p, uint32_t n_slots, uint32_t n_rays, uint32_t refill_grid)
+{
+    RayLaunch l{};
+    l.grid = grid_for(n_slots); l.slot_grid = (n_slots + 255u) / 256u;
+    l.refill = p.refill; l.lds_bytes = p.lds_bytes;
+    l.trace_block = p.refill ? (uint32_t)kTraceBlock : p.block;
+    l.trace_grid = p.refill ? refill_grid : grid_for(n_rays) * (256u / p.block);
+    return l;
+}
+
+// svgf_pixel's tiles over a frame (8 x 32 pixels per block of 256; x rounded up to a multiple of 8, one strip per XCD): the motion pass
+// and the display tail; a ragged frame's last tiles are partly outside it
+struct TileLaunch { uint32_t grid_x, grid_y; };
+inline TileLaunch tile_launch(int32_t width, int32_t height)
+{
+    return TileLaunch{ (uint32_t)((((width + 7) / 8) + 7) / 8 * 8), (uint32_t)((height + 31) / 32) };
+}
+
 // ---- regen.hip (PathTracing::render_regen) ----
 void regen_launch_begin(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const atn_camera_param& cam);
 // shadow rays of stage bs (< 0: none) + closest-hit rays of stage bc (< 0: none); `launch` indexes the job-fetch cursor
@@ -112,43 +149,26 @@ void restir_launch_motion(hipStream_t st, const FrameParams& fp, const RestirArg
 
 // ---- npr.hip (device/npr.hpp) ----
 struct NprArgs;
-// one bounce's NPR launches: prep and eval over the bounce's queue, the sample rays through the frame's walk (the plan's walk, LDS copy
-// and block; the grid for 8 rays per path)
-struct NprLaunch {
-    uint32_t grid;              // prep / eval blocks of 256 (grid-stride over the bounce's queue)
-    bool refill;
-    uint32_t trace_grid, trace_block, lds_bytes;
-};
+// one bounce's NPR launches: prep and eval over the bounce's queue, the sample rays through the frame's walk (8 rays per path)
 void npr_launch_gen(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const NprArgs& na);
-void npr_launch_bounce(const NprLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+void npr_launch_bounce(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
                        const atn_camera_param& cam, const NprArgs& na, int32_t bounce);
 void npr_launch_capture0(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const NprArgs& na);
 
 // ---- ao.hip (device/ao.hpp) ----
 struct AoArgs;
 // one AO frame's launches after k_gen_path: the primary rays (the pass's first trace launch, with the AO job), shade over the queue,
-// the AO rays through the frame's walk (the plan's walk, LDS copy and block; the grid for num_rays rays per path), resolve per slot
-struct AoLaunch {
-    uint32_t grid;              // shade blocks of 256 (grid-stride over the queue)
-    uint32_t slot_grid;         // blocks of 256 over all slots (resolve, filter)
-    bool refill;
-    uint32_t trace_grid, trace_block, lds_bytes;
-};
+// the AO rays through the frame's walk (num_rays rays per path), resolve per slot
 void ao_launch_primary(const TraceLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const AoArgs& aa);
-void ao_launch_rays(const AoLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const AoArgs& aa);
-void ao_launch_resolve(const AoLaunch& l, hipStream_t st, const FrameParams& fp, const AoArgs& aa, float4* film, float4* tile_out);
+void ao_launch_rays(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const AoArgs& aa);
+void ao_launch_resolve(const RayLaunch& l, hipStream_t st, const FrameParams& fp, const AoArgs& aa, float4* film, float4* tile_out);
 
 // ---- npr_shadow.hip (device/npr_shadow.hpp) ----
 struct NsArgs;
 // the shadow pre-pass's launches after k_gen_path: the primary rays (the pass's first trace launch, with a job that keeps t), shade over
-// the queue, the shadow rays through the frame's walk (the plan's walk, LDS copy and block), the row filter over w x h pixels
-struct NsLaunch {
-    uint32_t grid;              // shade blocks of 256 (grid-stride over the queue)
-    bool refill;
-    uint32_t trace_grid, trace_block, lds_bytes;
-};
+// the queue, the shadow rays through the frame's walk (one per path), the row filter over w x h pixels
 void ns_launch_primary(const TraceLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const NsArgs& na);
-void ns_launch_rays(const NsLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const NsArgs& na);
+void ns_launch_rays(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const NsArgs& na);
 void ns_launch_filter(hipStream_t st, const float* lit, const float* depth, float* out, int32_t width, int32_t height);
 
 // ---- npr_hatching.hip (device/npr_hatching.hpp) ----
@@ -159,29 +179,14 @@ void nh_launch_filter(int32_t direction, hipStream_t st, const float* src, const
 
 // ---- volume.hip (device/volume.hpp) ----
 struct VolArgs;
-// one iteration's volume launches: the closest-hit walk and the connection walk through the frame's walk (the plan's walk, LDS copy and
-// block; one job per path), the shade over the iteration's queue
-struct VolLaunch {
-    uint32_t grid;              // shade blocks of 256 (grid-stride over the iteration's queue)
-    uint32_t slot_grid;         // blocks of 256 over all slots (begin, reduce)
-    bool refill;
-    uint32_t trace_grid, trace_block, lds_bytes;
-};
-inline VolLaunch vol_launch(const PassPlan& p, uint32_t n_slots, uint32_t shade_grid, uint32_t plain_trace_grid)
-{
-    VolLaunch l{};
-    l.grid = shade_grid; l.slot_grid = (n_slots + 255u) / 256u;
-    l.refill = p.refill; l.lds_bytes = p.lds_bytes;
-    l.trace_block = p.refill ? (uint32_t)kTraceBlock : p.block;
-    l.trace_grid = p.refill ? p.trace_grid : plain_trace_grid * (256u / p.block);
-    return l;
-}
-void vol_launch_begin(const VolLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va);
-void vol_launch_closest(const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it);
-void vol_launch_shade(int material_set, const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+// one iteration's volume launches: the closest-hit walk and the connection walk through the frame's walk (one job per path), the shade
+// over the iteration's queue
+void vol_launch_begin(const RayLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va);
+void vol_launch_closest(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it);
+void vol_launch_shade(int material_set, const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
                       const atn_camera_param& cam, const VolArgs& va, int32_t it);
-void vol_launch_transmit(const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it);
-void vol_launch_reduce(const VolLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va);
+void vol_launch_transmit(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it);
+void vol_launch_reduce(const RayLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va);
 void vol_launch_phase_table(hipStream_t st, float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo, float* out_dir, float* out_eval);
 
 // ---- skinning.hip (device/skinning.hpp) ----
@@ -209,26 +214,15 @@ void skin_launch_morton(hipStream_t st, const atn_triangle_param* tris, const fl
 
 // ---- motion.hip (device/motion.hpp) ----
 struct MotionArgs;
-// the motion pass over a frame: svgf_pixel's tiles (8 x 32 pixels per block of 256; x rounded up to a multiple of 8, one strip per XCD)
-struct MotionLaunch { uint32_t grid_x, grid_y; };
-inline MotionLaunch motion_launch(int32_t width, int32_t height)
-{
-    return MotionLaunch{ (uint32_t)((((width + 7) / 8) + 7) / 8 * 8), (uint32_t)((height + 31) / 32) };
-}
 // the primary hit records of slots [fp.slot_begin, fp.slot_end) -> the ids plane; `grid` blocks of 256 over those slots
 void motion_launch_capture(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, float4* ids);
-void motion_launch_geometry(const MotionLaunch& l, hipStream_t st, const MotionArgs& a);
+// the motion pass over a frame's tiles
+void motion_launch_geometry(const TileLaunch& l, hipStream_t st, const MotionArgs& a);
 void motion_launch_copy(hipStream_t st, float4* dst, const float4* src, uint32_t n_quads);
 
 // ---- taa.hip (device/taa.hpp) ----
 struct TaaArgs;
-// the display tail over a frame: svgf_pixel's tiles like the motion pass (8 x 32 pixels per block of 256; x rounded up to a multiple of
-// 8, one strip per XCD); a ragged frame's last tiles are partly outside it
-struct TaaLaunch { uint32_t grid_x, grid_y; };
-inline TaaLaunch taa_launch(int32_t width, int32_t height)
-{
-    return TaaLaunch{ (uint32_t)((((width + 7) / 8) + 7) / 8 * 8), (uint32_t)((height + 31) / 32) };
-}
-void taa_launch_resolve(const TaaLaunch& l, hipStream_t st, const TaaArgs& a);
+// the display tail over a frame's tiles
+void taa_launch_resolve(const TileLaunch& l, hipStream_t st, const TaaArgs& a);
 
 } // namespace atn

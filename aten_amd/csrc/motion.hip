@@ -16,7 +16,7 @@ void motion_launch_capture(uint32_t grid, hipStream_t st, const PathBuffers& pb,
     hipLaunchKernelGGL(k_motion_capture_ids, dim3(grid), dim3(256), 0, st, pb, fp, ids);
 }
 
-void motion_launch_geometry(const MotionLaunch& l, hipStream_t st, const MotionArgs& a)
+void motion_launch_geometry(const TileLaunch& l, hipStream_t st, const MotionArgs& a)
 {
     hipLaunchKernelGGL(k_motion_geometry, dim3(l.grid_x, l.grid_y), dim3(256), 0, st, a);
 }

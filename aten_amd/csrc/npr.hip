@@ -15,7 +15,7 @@ void npr_launch_gen(uint32_t grid, hipStream_t st, const PathBuffers& pb, const 
     hipLaunchKernelGGL(k_npr_gen, dim3(grid), dim3(256), 0, st, pb, fp, na);
 }
 
-void npr_launch_bounce(const NprLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+void npr_launch_bounce(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
                        const atn_camera_param& cam, const NprArgs& na, int32_t bounce)
 {
     hipLaunchKernelGGL(k_npr_prep, dim3(l.grid), dim3(256), 0, st, pb, sc, na, bounce);

@@ -16,7 +16,7 @@ void ns_launch_primary(const TraceLaunch& l, hipStream_t st, const PathBuffers& 
     else hipLaunchKernelGGL((k_ns_primary<false>), dim3(l.grid), dim3(l.block), 0, st, pb, sc, na);
 }
 
-void ns_launch_rays(const NsLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const NsArgs& na)
+void ns_launch_rays(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const NsArgs& na)
 {
     hipLaunchKernelGGL(k_ns_shade, dim3(l.grid), dim3(256), 0, st, pb, sc, fp, na);
     // (the refill walk over an LDS copy -- only ever forced on a small scene -- walks global memory here, as the AO rays do)

@@ -10,7 +10,7 @@
 
 namespace atn {
 
-void taa_launch_resolve(const TaaLaunch& l, hipStream_t st, const TaaArgs& a)
+void taa_launch_resolve(const TileLaunch& l, hipStream_t st, const TaaArgs& a)
 {
     hipLaunchKernelGGL(k_taa, dim3(l.grid_x, l.grid_y), dim3(256), 0, st, a);
 }

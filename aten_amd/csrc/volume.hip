@@ -10,20 +10,20 @@
 
 namespace atn {
 
-void vol_launch_begin(const VolLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va)
+void vol_launch_begin(const RayLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va)
 {
     hipLaunchKernelGGL(k_vol_begin, dim3(l.slot_grid), dim3(256), 0, st, fp, va);
 }
 
 // (the refill walk over an LDS copy is never planned: PassPlan picks the LDS copy for small trees, the refill walk for deep ones)
-void vol_launch_closest(const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it)
+void vol_launch_closest(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it)
 {
     if (l.refill) hipLaunchKernelGGL((k_vol_closest<true, false>), dim3(l.trace_grid), dim3(l.trace_block), 0, st, pb, sc, va, it);
     else if (l.lds_bytes) hipLaunchKernelGGL((k_vol_closest<false, true>), dim3(l.trace_grid), dim3(l.trace_block), l.lds_bytes, st, pb, sc, va, it);
     else hipLaunchKernelGGL((k_vol_closest<false, false>), dim3(l.trace_grid), dim3(l.trace_block), 0, st, pb, sc, va, it);
 }
 
-void vol_launch_shade(int material_set, const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+void vol_launch_shade(int material_set, const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
                       const atn_camera_param& cam, const VolArgs& va, int32_t it)
 {
     const dim3 g(l.grid), t(256);
@@ -34,14 +34,14 @@ void vol_launch_shade(int material_set, const VolLaunch& l, hipStream_t st, cons
     }
 }
 
-void vol_launch_transmit(const VolLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it)
+void vol_launch_transmit(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it)
 {
     if (l.refill) hipLaunchKernelGGL((k_vol_transmit<true, false>), dim3(l.trace_grid), dim3(l.trace_block), 0, st, pb, sc, va, it);
     else if (l.lds_bytes) hipLaunchKernelGGL((k_vol_transmit<false, true>), dim3(l.trace_grid), dim3(l.trace_block), l.lds_bytes, st, pb, sc, va, it);
     else hipLaunchKernelGGL((k_vol_transmit<false, false>), dim3(l.trace_grid), dim3(l.trace_block), 0, st, pb, sc, va, it);
 }
 
-void vol_launch_reduce(const VolLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va)
+void vol_launch_reduce(const RayLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va)
 {
     hipLaunchKernelGGL(k_vol_reduce, dim3(l.slot_grid < 1024u ? l.slot_grid : 1024u), dim3(256), 0, st, fp, va);
 }

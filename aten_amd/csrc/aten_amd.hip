@@ -4451,6 +4451,75 @@ int atn_trace_closest(atn_ctx* ctx, const atn_ray* rays_host, uint32_t n, float 
     return ATN_OK;
 }
 
+int atn_trace_shadow(atn_ctx* ctx, const atn_shadow_query* queries_host, uint32_t n, int32_t flavour, uint8_t* out_visible)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    PathTracing& r = ctx->r;
+    if (!r.has_scene) return r.fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+    if (flavour < atn::kShadowProbeFused || flavour > atn::kShadowProbeRegen) return r.fail(ATN_ERR_INVALID_ARG, "atn_trace_shadow: unknown flavour");
+    if (n == 0) return ATN_OK;
+    if (!queries_host || !out_visible) return r.fail(ATN_ERR_INVALID_ARG, "null queries / output");
+    if (r.scene.n_lights <= 0) return r.fail(ATN_ERR_UNSUPPORTED, "atn_trace_shadow: the scene has no lights");
+    for (uint32_t i = 0; i < n; i++)
+        if (queries_host[i].light < 0 || queries_host[i].light >= r.scene.n_lights) return r.fail(ATN_ERR_INVALID_ARG, "atn_trace_shadow: light index outside the scene's lights");
+    const uint64_t slots64 = 2ull * n + atn::kShadowProbePad;
+    if (slots64 > atn::kShadowSlotMask) return r.fail(ATN_ERR_UNSUPPORTED, "atn_trace_shadow: more than 2^25 queries");
+    const uint32_t n_slots = (uint32_t)slots64;
+    C_HIP(r, hipSetDevice(r.device));
+    // the queue: every used slot once, in a fixed shuffled order (Fisher-Yates over a 64-bit LCG)
+    std::vector<uint32_t> queue(n);
+    for (uint32_t i = 0; i < n; i++) queue[i] = 2u * i + 1u;
+    uint64_t lcg = 0x9e3779b97f4a7c15ull;
+    for (uint32_t i = n - 1u; i > 0u; i--) {
+        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+        std::swap(queue[i], queue[(uint32_t)((lcg >> 33) % (uint64_t)(i + 1u))]);
+    }
+    const bool deferred = flavour == atn::kShadowProbeDeferred, regen = flavour == atn::kShadowProbeRegen, counted = flavour == atn::kShadowProbeCounted;
+    atn::DevBuf<atn_shadow_query> dq; atn::DevBuf<float4> sh_o, sh_d, sh_c, contrib, pend; atn::DevBuf<uint32_t> shadow_q, flags, counters, errs;
+    atn::DevBuf<unsigned long long> stats; atn::DevBuf<uint8_t> out;
+    C_HIP(r, dq.resize(n)); C_HIP(r, sh_o.resize(n_slots)); C_HIP(r, sh_d.resize(n_slots)); C_HIP(r, sh_c.resize(n_slots)); C_HIP(r, contrib.resize(n_slots));
+    C_HIP(r, shadow_q.resize(n_slots)); C_HIP(r, counters.resize(4)); C_HIP(r, errs.resize(4)); C_HIP(r, out.resize(n));
+    if (regen) C_HIP(r, pend.resize(n_slots));
+    if (deferred) C_HIP(r, flags.resize(n_slots));
+    if (counted) { C_HIP(r, stats.resize(16)); C_HIP(r, hipMemsetAsync(stats.p, 0, 128, r.stream)); }
+    C_HIP(r, hipMemcpyAsync(dq.p, queries_host, (size_t)n * sizeof(atn_shadow_query), hipMemcpyHostToDevice, r.stream));
+    C_HIP(r, hipMemcpyAsync(shadow_q.p, queue.data(), (size_t)n * 4, hipMemcpyHostToDevice, r.stream));
+    const uint32_t hc[4] = { 0u, n, 0u, 0u };       // q_count[0], sh_count[0] = n, the two fetch cursors cleared
+    C_HIP(r, hipMemcpyAsync(counters.p, hc, 16, hipMemcpyHostToDevice, r.stream));
+    C_HIP(r, hipMemsetAsync(errs.p, 0, 16, r.stream));
+    atn::PathBuffers pb{};
+    pb.sh_o = sh_o.p; pb.sh_d = sh_d.p; pb.sh_c = sh_c.p; pb.contrib = contrib.p; pb.shadow_q = shadow_q.p;
+    pb.q_count = counters.p; pb.sh_count = counters.p + 1; pb.fetch_closest = counters.p + 2; pb.fetch_shadow = counters.p + 3;
+    pb.pend = pend.p; pb.nee_reached = flags.p; pb.stats = stats.p;
+    const dim3 g_slots((n_slots + 255u) / 256u), t256(256);
+    hipLaunchKernelGGL(atn::k_shadow_probe_fill, g_slots, t256, 0, r.stream, pb, (const atn_shadow_query*)dq.p, n, n_slots, flavour);
+    {
+        // the walk the scene's tree calls for (or the forced one), whatever n is -- as atn_trace_closest picks it; everything else of the
+        // launch is the pass's own plan
+        atn::PassPlan plan = r.plan_pass(regen ? atn::PassKind::Regen : atn::PassKind::Serial, n);
+        plan.refill = r.refill_walk(false);
+        plan.trace_grid = r.trace_grid(n, plan.refill);
+        plan.fused_grid = r.trace_grid(2u * n, plan.refill);
+        if (counted) r.launch_trace<true>(plan, pb, true, 0, r.stream);
+        else {
+            const atn::TraceLaunch tl = atn::trace_launch(plan, 1);     // (a stage behind the first: the launch that carries shadow rays)
+            if (regen) atn::regen_launch_trace(tl, r.stream, pb, r.scene, 0, -1, 0);
+            else atn::launch_trace_fused<false>(tl, r.stream, pb, r.scene, 0, -1, 0);
+        }
+    }
+    C_HIP(r, hipGetLastError());
+    hipLaunchKernelGGL(atn::k_shadow_probe_check, g_slots, t256, 0, r.stream, pb, (const atn_shadow_query*)dq.p, n, n_slots, flavour, out.p, errs.p);
+    C_HIP(r, hipGetLastError());
+    uint32_t he[4] = {};
+    C_HIP(r, hipMemcpyAsync(out_visible, out.p, n, hipMemcpyDeviceToHost, r.stream));
+    C_HIP(r, hipMemcpyAsync(he, errs.p, 16, hipMemcpyDeviceToHost, r.stream));
+    C_HIP(r, hipStreamSynchronize(r.stream));
+    if (he[0] || he[1] || he[2])
+        return r.fail(ATN_ERR_HIP, "atn_trace_shadow: " + std::to_string(he[0]) + " unused slots changed, " + std::to_string(he[1]) + " ray records changed, "
+                                   + std::to_string(he[2]) + " result records hold neither verdict");
+    return ATN_OK;
+}
+
 int atn_cmj_samples(atn_ctx* ctx, uint32_t index, uint32_t dimension, uint32_t scramble, int32_t n, float* out_host)
 {
     CTX_QUIET_OR_FAIL(ctx);

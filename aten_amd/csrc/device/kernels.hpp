@@ -1716,6 +1716,97 @@ __global__ void __launch_bounds__(256) k_ray_offset(uint32_t n, const float* __r
     out[3 * k] = r.x; out[3 * k + 1] = r.y; out[3 * k + 2] = r.z;
 }
 
+// ---- the shadow-ray probe (atn_trace_shadow): n caller-given queries through the production shadow kernels --------------------------------
+// Query i lives in slot 2 i + 1 of planes 2 n + kShadowProbePad slots wide; the host hands over a shuffled shadow queue, so neither a
+// slot nor a queue index is ever its own query's number.  Every other slot carries a pattern no kernel writes (shadow_probe_mark) in
+// every plane: k_shadow_probe_check holds the unused slots -- and the used slots' ray planes -- against what k_shadow_probe_fill wrote,
+// and reads each verdict from the plane the flavour's finish() adds to.
+constexpr uint32_t kShadowProbePad = 64u;
+constexpr int32_t kShadowProbeFused = 0, kShadowProbeCounted = 1, kShadowProbeDeferred = 2, kShadowProbeRegen = 3;
+constexpr uint32_t kShadowProbeItem = 0x00abcdefu;       // contrib.w / pend.w of the regenerated flavour: "the item the sample belongs to", kept by finish()
+ATN_DEV float4 shadow_probe_mark(uint32_t slot, uint32_t plane)
+{
+    const uint32_t m = 0x7fa00000u | (plane << 16) | (slot & 0xffffu);     // (NaN patterns: compared as bits)
+    return make_float4(__uint_as_float(m), __uint_as_float(m ^ 0x1111u), __uint_as_float(m ^ 0x2222u), __uint_as_float(m ^ 0x4444u));
+}
+ATN_DEV bool same_bits(const float4& a, const float4& b)
+{
+    return __float_as_uint(a.x) == __float_as_uint(b.x) && __float_as_uint(a.y) == __float_as_uint(b.y)
+        && __float_as_uint(a.z) == __float_as_uint(b.z) && __float_as_uint(a.w) == __float_as_uint(b.w);
+}
+// what k_shade leaves for query q: {sh_o, sh_d, sh_c}
+ATN_DEV void shadow_probe_ray(const atn_shadow_query& q, int32_t flavour, float4& so, float4& sd, float4& lc)
+{
+    uint32_t lbits = (uint32_t)q.light | ((q.flags & 1u) ? kShadowStencilFlag : 0u);
+    if (flavour == kShadowProbeRegen && (q.flags & 2u)) lbits |= kShadowFinalFlag;
+    so = make_float4(q.org[0], q.org[1], q.org[2], q.dist_to_light);
+    sd = make_float4(q.dir[0], q.dir[1], q.dir[2], __uint_as_float(lbits));
+    lc = make_float4(1.0F, 2.0F, 4.0F, __uint_as_float(lbits));
+}
+__global__ void __launch_bounds__(256) k_shadow_probe_fill(PathBuffers pb, const atn_shadow_query* __restrict__ queries, uint32_t n, uint32_t n_slots, int32_t flavour)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_slots) return;
+    const bool used = (slot & 1u) && (slot >> 1) < n;
+    const bool regen = flavour == kShadowProbeRegen;
+    if (!used) {
+        pb.sh_o[slot] = shadow_probe_mark(slot, 0u); pb.sh_d[slot] = shadow_probe_mark(slot, 1u); pb.sh_c[slot] = shadow_probe_mark(slot, 2u);
+        pb.contrib[slot] = shadow_probe_mark(slot, 3u);
+        if (pb.pend) pb.pend[slot] = shadow_probe_mark(slot, 4u);
+        if (pb.nee_reached) pb.nee_reached[slot] = 0x5a5a0000u | (slot & 0xffffu);
+        return;
+    }
+    float4 so, sd, lc;
+    shadow_probe_ray(queries[slot >> 1], flavour, so, sd, lc);
+    pb.sh_o[slot] = so; pb.sh_d[slot] = sd; pb.sh_c[slot] = lc;
+    const float w = regen ? __uint_as_float(kShadowProbeItem) : 0.0F;
+    pb.contrib[slot] = make_float4(0.0F, 0.0F, 0.0F, w);
+    if (pb.pend) pb.pend[slot] = make_float4(0.0F, 0.0F, 0.0F, w);
+    if (pb.nee_reached) pb.nee_reached[slot] = 0u;
+}
+// errs: [0] an unused slot changed, [1] a used slot's ray planes changed, [2] a used slot's result planes hold neither "visible" nor "blocked"
+__global__ void __launch_bounds__(256) k_shadow_probe_check(PathBuffers pb, const atn_shadow_query* __restrict__ queries, uint32_t n, uint32_t n_slots, int32_t flavour,
+                                                            uint8_t* __restrict__ out, uint32_t* errs)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_slots) return;
+    const bool used = (slot & 1u) && (slot >> 1) < n;
+    const bool regen = flavour == kShadowProbeRegen;
+    if (!used) {
+        bool ok = same_bits(pb.sh_o[slot], shadow_probe_mark(slot, 0u)) && same_bits(pb.sh_d[slot], shadow_probe_mark(slot, 1u))
+               && same_bits(pb.sh_c[slot], shadow_probe_mark(slot, 2u)) && same_bits(pb.contrib[slot], shadow_probe_mark(slot, 3u));
+        if (pb.pend) ok = ok && same_bits(pb.pend[slot], shadow_probe_mark(slot, 4u));
+        if (pb.nee_reached) ok = ok && pb.nee_reached[slot] == (0x5a5a0000u | (slot & 0xffffu));
+        if (!ok) atomicAdd(&errs[0], 1u);
+        return;
+    }
+    const atn_shadow_query q = queries[slot >> 1];
+    float4 so, sd, lc;
+    shadow_probe_ray(q, flavour, so, sd, lc);
+    if (!(same_bits(pb.sh_o[slot], so) && same_bits(pb.sh_d[slot], sd) && same_bits(pb.sh_c[slot], lc))) atomicAdd(&errs[1], 1u);
+    const float w = regen ? __uint_as_float(kShadowProbeItem) : 0.0F;
+    const float4 zero = make_float4(0.0F, 0.0F, 0.0F, w), lit = make_float4(lc.x, lc.y, lc.z, w);
+    const float4 c = pb.contrib[slot];
+    bool ok = true, visible = false;
+    if (flavour == kShadowProbeDeferred) {
+        const uint32_t f = pb.nee_reached[slot];
+        ok = same_bits(c, zero) && f <= 1u;
+        visible = f == 1u;
+    }
+    else if (regen && (q.flags & 2u)) {
+        const float4 pd = pb.pend[slot];
+        visible = same_bits(pd, lit);
+        ok = same_bits(c, zero) && (visible || same_bits(pd, zero));
+    }
+    else {
+        visible = same_bits(c, lit);
+        ok = visible || same_bits(c, zero);
+        if (pb.pend) ok = ok && same_bits(pb.pend[slot], zero);
+    }
+    if (!ok) atomicAdd(&errs[2], 1u);
+    out[slot >> 1] = visible ? 1u : 0u;
+}
+
 // one thread per (index, dimension, scramble) triple: `draws` successive nextSample()
 __global__ void __launch_bounds__(256) k_cmj_batch(uint32_t n, const uint32_t* __restrict__ index, const uint32_t* __restrict__ dim,
                                                    const uint32_t* __restrict__ scramble, int draws, float* __restrict__ out)

@@ -73,6 +73,9 @@ INTERSECTION = np.dtype([
 
 RAY = np.dtype([("org", f4, 3), ("dir", f4, 3)])
 
+# atn_shadow_query, 36 B: one query of the shadow-ray probe (flags: bit 0 stencil ALWAYS at the shaded surface, bit 1 last vertex)
+SHADOW_QUERY = np.dtype([("org", f4, 3), ("dir", f4, 3), ("dist_to_light", f4), ("light", i4), ("flags", np.uint32)])
+
 # aten::SkinningVertex, 72 B (src/libaten/deformable/SkinningVertex.h:7-14)
 SKINNING_VERTEX = np.dtype([
     ("position", f4, 4), ("normal", f4, 3), ("clr", np.uint8, 4), ("uv", f4, 2),

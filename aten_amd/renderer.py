@@ -759,6 +759,30 @@ class PathTracing:
                                               out.ctypes.data, st.ctypes.data if stats else None))
         return (out, st) if stats else out
 
+    SHADOW_FLAVOURS = {"fused": 0, "counted": 1, "deferred": 2, "regen": 3}
+
+    def trace_shadow(self, origins, directions, dist_to_light, light, stencil_always=False, flavour="fused", final=None):
+        """HitShadowRay's verdict for n caller-given shadow rays through the production shadow kernels (atn_trace_shadow): origins and
+        directions [n, 3] (directions need not be unit length), dist_to_light [n], light [n] or one index, stencil_always [n] or one flag
+        (the shaded surface's material is StencilType::ALWAYS).  flavour: a name from SHADOW_FLAVOURS; `final` (flavour "regen" only):
+        [n] flags, the rays of a path's last vertex.  Returns uint8 [n], 1 = the light is visible."""
+        if flavour not in self.SHADOW_FLAVOURS:
+            raise ValueError("unknown shadow flavour %r" % (flavour,))
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        n = len(o)
+        q = np.zeros(n, L.SHADOW_QUERY)
+        q["org"] = o
+        q["dir"] = np.ascontiguousarray(directions, np.float32).reshape(n, 3)
+        q["dist_to_light"] = np.broadcast_to(np.asarray(dist_to_light, np.float32), (n,))
+        q["light"] = np.broadcast_to(np.asarray(light, np.int32), (n,))
+        flags = np.broadcast_to(np.asarray(stencil_always, bool), (n,)).astype(np.uint32)
+        if final is not None:
+            flags = flags | (np.broadcast_to(np.asarray(final, bool), (n,)).astype(np.uint32) << 1)
+        q["flags"] = flags
+        out = np.zeros(n, np.uint8)
+        self._check(self._l.atn_trace_shadow(self._ctx, q.ctypes.data, n, self.SHADOW_FLAVOURS[flavour], out.ctypes.data))
+        return out
+
     def cmj_samples(self, index, dimension, scramble, n):
         out = np.zeros(n, np.float32)
         self._check(self._l.atn_cmj_samples(self._ctx, index, dimension, scramble, n, out.ctypes.data))

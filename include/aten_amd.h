@@ -635,6 +635,18 @@ int atn_generate_paths(atn_ctx* ctx, int32_t width, int32_t height, int32_t samp
  * stats_out (optional): {node visits, triangle tests}. */
 int atn_trace_closest(atn_ctx* ctx, const atn_ray* rays_host, uint32_t n, float t_min, float t_max,
                       atn_intersection* out_host, uint64_t* stats_out);
+/* HitShadowRay -> HitTestToTargetLight -> scene::hitLight (pathtracing_impl.h:266-393, scene/scene.h:64-134) for n caller-given shadow
+ * rays, through the PRODUCTION shadow kernels: the probe fills path buffers of its own as the shade stage leaves them (sh_o, sh_d, sh_c
+ * with a known contribution, the shadow queue and its count), launches through the launchers the renderers use, on the walk the uploaded
+ * scene calls for (ATEN_AMD_TRACE forces one), and reads each verdict back from the plane the flavour adds to.  Query i lives in slot
+ * 2 i + 1 and the queue is shuffled; the slots in between must come back untouched (checked on the device: ATN_ERR_HIP otherwise).
+ *   flavour 0 "fused":    the shadow half of the fused trace launch (no closest-hit rays beside it)
+ *           1 "counted":  the unfused shadow kernel of counted frames
+ *           2 "deferred": as 0 in a deferred-NEE frame: the verdict is the slot's flag word, `contrib` stays zero
+ *           3 "regen":    the regenerated pool's launch; a query with flags bit 1 adds to `pend`, every other to `contrib`
+ * out_visible[i] = 1 when query i's contribution was added.  ATN_ERR_NO_SCENE without a scene, ATN_ERR_INVALID_ARG for null pointers,
+ * an unknown flavour or a light index outside the scene's lights, ATN_ERR_UNSUPPORTED for a scene without lights; n == 0 is a no-op. */
+int atn_trace_shadow(atn_ctx* ctx, const atn_shadow_query* queries_host, uint32_t n, int32_t flavour, uint8_t* out_visible);
 /* n successive CMJ::nextSample() (src/libaten/sampler/cmj.h:32-37). */
 int atn_cmj_samples(atn_ctx* ctx, uint32_t index, uint32_t dimension, uint32_t scramble, int32_t n, float* out_host);
 /* For each of n (index, dimension, scramble) triples: CMJ::init then `draws` x nextSample()

@@ -253,6 +253,17 @@ typedef struct atn_intersection {
 /* ---- aten::ray, 24 B (src/libaten/math/ray.h) */
 typedef struct atn_ray { float org[3]; float dir[3]; } atn_ray;
 
+/* ---- one query of the shadow-ray probe (atn_trace_shadow), 36 B: what the shade stage stores of a shadow ray
+ *      (ShadowRay, src/libaten/renderer/pathtracing/pathtracing_impl.h:178-264).  flags: bit 0 = the shaded surface's material is
+ *      StencilType::ALWAYS; bit 1 = the ray of a path's last vertex (read by the regenerated flavour only). */
+typedef struct atn_shadow_query {
+    float org[3];
+    float dir[3];           /* need not be unit length: the shadow kernels re-normalise, as aten::ray's constructor does */
+    float dist_to_light;
+    int32_t light;          /* target light index */
+    uint32_t flags;
+} atn_shadow_query;
+
 /* ---- one texture: aten::texture::colors() is vec4[w*h] (src/libaten/image/texture.h:104-122) */
 typedef struct atn_texture_desc {
     const atn_vec4* texels;

@@ -147,6 +147,28 @@ void orc_trace_closest(const atn_scene_desc* scene, const atn_ray* rays, uint32_
     if (stats_out) { stats_out[0] = nodes; stats_out[1] = tris; }
 }
 
+// HitTestToTargetLight for a batch of shadow rays, with Ray(org, dir) re-normalising as HitShadowRay does.  visible[i] = the verdict;
+// lookups_out (optional) = the lookups made; last_out (optional) = the last lookup's closest hit (objid < 0: a miss).
+// surface_stencil_always[i] != 0: the shaded surface's material is StencilType::ALWAYS.
+void orc_shadow_visible(const atn_scene_desc* scene, const atn_shadow_query* q, uint32_t n, uint8_t* visible,
+    int32_t* lookups_out, atn_intersection* last_out)
+{
+    Scene ctxt(scene);
+#pragma omp parallel for
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        const Ray original_ray(ld3(q[i].org), ld3(q[i].dir));
+        ShadowTrace tr;
+        visible[i] = HitTestToTargetLight(ctxt, original_ray, ctxt.GetLight(q[i].light), q[i].dist_to_light, (q[i].flags & 1u) ? 1 : 0, nullptr, &tr) ? 1 : 0;
+        if (lookups_out) lookups_out[i] = tr.lookups;
+        if (last_out) {
+            atn_intersection& o = last_out[i];
+            const Isect& is = tr.last;
+            o.t = is.t; o.objid = tr.last_is_hit ? is.objid : -1; o.mtrlid = is.mtrlid; o.meshid = is.meshid;
+            o.tri_id = is.tri_id; o.a = is.a; o.b = is.b; o.isVoxel = is.isVoxel;
+        }
+    }
+}
+
 // evaluate_hit_result for a batch of (ray, intersection): out = {p.xyz, area, n.xyz, u, v} (9 floats)
 void orc_evaluate_hits(const atn_scene_desc* scene, const atn_ray* rays, const atn_intersection* isects,
     uint32_t n, float* out)

@@ -116,6 +116,33 @@ def trace_closest(scene, rays, t_min=1e-9, t_max=np.finfo(np.float32).max):
     return out, stats
 
 
+def shadow_queries(origins, directions, dist_to_light, light, stencil_always=False):
+    """atn_shadow_query[n] (aten_amd.layout.SHADOW_QUERY) from arrays; light and stencil_always may be one value for all."""
+    from aten_amd import layout as L
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    q = np.zeros(len(o), L.SHADOW_QUERY)
+    q["org"] = o
+    q["dir"] = np.ascontiguousarray(directions, np.float32).reshape(len(o), 3)
+    q["dist_to_light"] = np.broadcast_to(np.asarray(dist_to_light, np.float32), (len(o),))
+    q["light"] = np.broadcast_to(np.asarray(light, np.int32), (len(o),))
+    q["flags"] = np.broadcast_to(np.asarray(stencil_always, bool), (len(o),)).astype(np.uint32)
+    return q
+
+
+def shadow_visible(scene, queries, details=False):
+    """HitTestToTargetLight per query (shadow_queries): uint8 [n], 1 = the light is visible.  details=True also returns the lookups
+    made [n] and the last lookup's closest hit (INTERSECTION [n], objid < 0 = a miss)."""
+    from aten_amd import layout as L
+    q = np.ascontiguousarray(queries, L.SHADOW_QUERY)
+    n_lights = int(scene.desc.n_lights) if hasattr(scene, "desc") else None
+    if n_lights is not None and len(q) and (q["light"].min() < 0 or q["light"].max() >= n_lights):
+        raise ValueError("light index outside the scene's lights")
+    vis = np.zeros(len(q), np.uint8); lookups = np.zeros(len(q), np.int32); last = np.zeros(len(q), L.INTERSECTION)
+    lib().orc_shadow_visible(scene.ref(), C.c_void_p(q.ctypes.data), C.c_uint32(len(q)), C.c_void_p(vis.ctypes.data),
+                             C.c_void_p(lookups.ctypes.data), C.c_void_p(last.ctypes.data))
+    return (vis, lookups, last) if details else vis
+
+
 def evaluate_hits(scene, rays, isects):
     out = np.zeros((len(rays), 9), np.float32)
     lib().orc_evaluate_hits(scene.ref(), C.c_void_p(rays.ctypes.data), C.c_void_p(isects.ctypes.data),

@@ -1638,8 +1638,10 @@ inline void FillShadowRay(ShadowRay& shadow_ray, const Scene& ctxt, PathState& p
 // ctxt.GetMaterial(isect.mtrlid)); ALWAYS raises the lookup budget to 10 and makes STENCIL surfaces transparent to
 // the shadow ray; scene_rendering_config.enable_alpha_blending raises it to 10 as well.
 // HitTestToTargetLight, pathtracing_impl.h:266-365
+// `trace` (optional, not in the reference): how the verdict came about -- the lookups made and the last lookup's closest hit
+struct ShadowTrace { int32_t lookups{ 0 }; bool last_is_hit{ false }; Isect last; };
 inline bool HitTestToTargetLight(const Scene& ctxt, const Ray& original_ray, const atn_light_param& light, float distToLight,
-    int32_t surface_stencil_type, PathCounters* cnt)
+    int32_t surface_stencil_type, PathCounters* cnt, ShadowTrace* trace = nullptr)
 {
     const bool valid_obj = (light.type == ATN_LIGHT_AREA) && light.arealight_objid >= 0;
     const int32_t lightobj = valid_obj ? light.arealight_objid : -1;
@@ -1655,6 +1657,7 @@ inline bool HitTestToTargetLight(const Scene& ctxt, const Ray& original_ray, con
     for (size_t i = 0; i < max_lookups; i++) {
         Isect isect;
         bool isHit = TraverseClosest(isect, ctxt, r, EPS, distToLight - EPS, cnt ? &cnt->trav : nullptr);
+        if (trace) { trace->lookups = (int32_t)i + 1; trace->last_is_hit = isHit; trace->last = isect; }
         if (isHit) {
             hitobj = isect.objid;
             const auto& hobj = ctxt.GetObject(static_cast<uint32_t>(isect.objid));

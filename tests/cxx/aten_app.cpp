@@ -278,6 +278,13 @@ int main(int argc, char** argv)
         if (is.objid != a.insts[2].obj || (is.tri_id != (int32_t)t0 && is.tri_id != (int32_t)t0 + 1)) {
             std::fprintf(stderr, "after the tick the ray hits object %d triangle %d\n", is.objid, is.tri_id); return 1;
         }
+        // the same ray as a shadow ray towards the lamp, 10 units away: the panel is not the lamp, so the ray is blocked
+        atn_shadow_query q{};
+        std::memcpy(q.org, r.org, sizeof(q.org)); std::memcpy(q.dir, r.dir, sizeof(q.dir));
+        q.dist_to_light = 10.0F; q.light = 0; q.flags = 0;
+        uint8_t visible = 2;
+        CHECK(atn_trace_shadow(ctx, &q, 1, 0, &visible));
+        if (visible != 0) { std::fprintf(stderr, "the shadow ray through the panel reports %d\n", (int)visible); return 1; }
         for (uint32_t v = v0; v < v0 + 6; v++) { a.pos[v].x -= 0.25F; a.pos[v].y -= 0.1F; }       // the dump below is the scene as rendered
     }
     atn_destroy(ctx);

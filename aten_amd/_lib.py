@@ -12,6 +12,8 @@ _lib = None
 
 K_NAMES = ["gen_path", "trace_closest", "shade", "trace_shadow", "accumulate_sample", "gather",
            "svgf_prepare", "svgf_temporal", "svgf_variance", "svgf_atrous", "trace_fused"]
+# atn_mgpu_get_kernel_times: the same classes and the two of node-wide SVGF's exchange (ATN_K_MGPU_COUNT entries)
+MGPU_K_NAMES = K_NAMES + ["svgf_pack", "svgf_unpack"]
 
 SYMBOLS = [
     "atn_create", "atn_destroy", "atn_last_error", "atn_upload_scene", "atn_update_camera", "atn_update_tlas",
@@ -46,6 +48,9 @@ SYMBOLS = [
     "atn_set_nee_deferral", "atn_nee_deferral_active", "atn_nee_deferral_stats",
     "atn_update_materials", "atn_update_lights", "atn_update_texture", "atn_update_rendering_config",
     "atn_mgpu_update_materials", "atn_mgpu_update_lights", "atn_mgpu_update_texture", "atn_mgpu_update_rendering_config",
+    "atn_mgpu_svgf_render", "atn_mgpu_svgf_set_motion_depth", "atn_mgpu_svgf_reset", "atn_mgpu_svgf_set_atrous_iterations",
+    "atn_mgpu_svgf_set_dilate_temporal_weight", "atn_mgpu_svgf_download", "atn_mgpu_svgf_output_device",
+    "atn_mgpu_get_kernel_times", "atn_mgpu_reset_kernel_times",
 ]
 
 
@@ -205,6 +210,15 @@ def lib():
         l.atn_mgpu_synchronize.argtypes = [vp]
         l.atn_mgpu_film_device.argtypes = [vp]; l.atn_mgpu_film_device.restype = vp
         l.atn_mgpu_download_film.argtypes = [vp, vp]
+        l.atn_mgpu_svgf_render.argtypes = [vp, vp, C.c_int32, vp, vp]
+        l.atn_mgpu_svgf_set_motion_depth.argtypes = [vp, vp, C.c_uint32]
+        l.atn_mgpu_svgf_reset.argtypes = [vp]
+        l.atn_mgpu_svgf_set_atrous_iterations.argtypes = [vp, C.c_int32]
+        l.atn_mgpu_svgf_set_dilate_temporal_weight.argtypes = [vp, C.c_int32]
+        l.atn_mgpu_svgf_download.argtypes = [vp, C.c_int32, vp]
+        l.atn_mgpu_svgf_output_device.argtypes = [vp]; l.atn_mgpu_svgf_output_device.restype = vp
+        l.atn_mgpu_get_kernel_times.argtypes = [vp, C.c_int32, vp, vp]
+        l.atn_mgpu_reset_kernel_times.argtypes = [vp]
         l.atn_build_id.argtypes = []; l.atn_build_id.restype = C.c_char_p
         for n in ("atn_sizeof_scene_desc", "atn_sizeof_destination", "atn_abi_version"):
             getattr(l, n).restype = C.c_uint32

@@ -20,6 +20,7 @@
 #include "device/kernels.hpp"
 #include "device/launch.hpp"
 #include "device/svgf.hpp"
+#include "device/svgf_gather.hpp"
 #include "device/restir.hpp"
 #include "device/npr.hpp"
 #include "device/ao.hpp"
@@ -832,8 +833,8 @@ public:
     }
 
     // profiling
-    float k_ms[ATN_K_COUNT] = {};
-    uint32_t k_launches[ATN_K_COUNT] = {};
+    float k_ms[ATN_K_MGPU_COUNT] = {};       // (atn_get_kernel_times reports the first ATN_K_COUNT)
+    uint32_t k_launches[ATN_K_MGPU_COUNT] = {};
     std::vector<DevEvent> ev_pool;
     struct Span { int kind; size_t e0, e1; };
     static constexpr size_t kMaxSpans = 8192;
@@ -2404,6 +2405,18 @@ public:
     int svgf_ensure(int32_t w, int32_t h, bool stages)
     {
         const size_t n = (size_t)w * h;
+        if (sv_handover_only) {
+            // the hand-over planes as below (same initial values: a pixel the path pass does not write keeps them), and nothing else
+            if (w != sv_w || h != sv_h) {
+                for (int k = 0; k < 2; k++) {
+                    ATN_HIP(sv_primary[k].resize(n)); fill4(sv_primary[k].p, n, make_float4(0, 0, 0, 0));
+                    ATN_HIP(sv_contribs[k].resize(n)); ATN_HIP(sv_gnd[k].resize(n)); ATN_HIP(sv_gam[k].resize(n));
+                }
+                sv_w = w; sv_h = h; sv_curr = 0; sv_slot = 0; sv_last_slot = 0;
+                sv_frame_done = false;
+            }
+            return ATN_OK;
+        }
         if (w != sv_w || h != sv_h) {
             const float4 init = make_float4(0.0F, 0.0F, 0.0F, 1.0F);
             for (auto& set : sv_aov) for (auto& b : set) { ATN_HIP(b.resize(n)); fill4(b.p, n, init); }
@@ -2448,13 +2461,39 @@ public:
         return nullptr;
     }
 
-    // ≙ aten::SVGFRenderer::OnRender (svgf.cpp:452-637)
+    // ≙ aten::SVGFRenderer::OnRender (svgf.cpp:452-637): the two halves below, back to back
     int svgf_render(const atn_destination* d, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host, bool path_pass = true)
     {
         int rc = check_ready(d);
         if (rc) return rc;
+        // (a shard of a node-wide frame goes through the halves: MultiGpu::svgf_render gathers the hand-over planes in between)
         if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "SVGF needs the whole frame on one GPU (filter footprints cross tiles)");
+        rc = svgf_path_half(d, compute_motion, stages_host != nullptr, path_pass);
+        return rc ? rc : svgf_filter_half(d, out_host, stages_host);
+    }
+
+    // What the path half of an SVGF frame leaves for its filter half: the frame's planes and matrices, the hand-over slot, the stream
+    // the filters run on.
+    struct SvgfPass {
+        SvgfFrame sf{};
+        hipStream_t fs = nullptr;
+        int32_t slot = 0, cur = 0;
+        bool pipelined = false, path_pass = false, prof = false;
+    } sv_pass;
+    // A shard other than the first of a node-wide frame (MultiGpu::svgf_render) only ever runs the path half: it keeps the hand-over
+    // planes and nothing the filters own (AOV sets, moments, a-trous, output, motion, the filter stream).
+    bool sv_handover_only = false;
+    DevBuf<float4> sv_packed[2];        // ... and, per hand-over slot, its pixels of the four planes packed for the push (k_svgf_pack_tiles)
+
+    // The path half: everything of OnRender up to PrepareForDenoise -- the frame's bank, the planes, the camera matrices, the sample
+    // loop into slot sv_slot of the hand-over planes.  Every plane is addressed by pixel (k_shade<SVGF>, k_svgf_sample_end through
+    // slot_to_pixel), so on a screen shard (world > 1) it fills exactly the shard's pixels of them.
+    int svgf_path_half(const atn_destination* d, int32_t compute_motion, bool want_stages, bool path_pass)
+    {
+        int rc = check_ready(d);
+        if (rc) return rc;
         const bool geo_motion = compute_motion == 2;
+        if (geo_motion && world != 1) return fail(ATN_ERR_UNSUPPORTED, "compute_motion = 2 on a screen shard: the geometry history has no node-wide form");
         if (geo_motion) {
             if (!path_pass) return fail(ATN_ERR_UNSUPPORTED, "compute_motion = 2 needs the frame's primary hits: atn_svgf_denoise has no path pass");
             if (!gm_on) return fail(ATN_ERR_INVALID_ARG, "compute_motion = 2 needs geometry motion tracking: atn_set_geometry_motion(ctx, 1)");
@@ -2471,16 +2510,14 @@ public:
         const bool pipelined = frames_in_flight > 1 && path_pass;
         if (!pipelined && frames_in_flight > 1) { rc = quiesce(); if (rc) return rc; }
         else if (w_or_h_changed(d->width, d->height)) { rc = quiesce(); if (rc) return rc; }
-        if (pipelined && !sv_stream) {
-            ATN_HIP(hipStreamCreateWithFlags(&sv_stream.h, hipStreamNonBlocking));
-            for (auto& e : sv_ev_prepare) ATN_HIP(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
-        }
+        if (pipelined && !sv_stream && !sv_handover_only) ATN_HIP(hipStreamCreateWithFlags(&sv_stream.h, hipStreamNonBlocking));
+        if (pipelined && !sv_ev_prepare[0]) for (auto& e : sv_ev_prepare) ATN_HIP(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
         rc = begin_frame(*d, pipelined);
         if (rc) return rc;
-        hipStream_t fs = pipelined ? sv_stream : stream;       // the stream the filter passes run on
-        rc = svgf_ensure(d->width, d->height, stages_host != nullptr);
+        hipStream_t fs = (pipelined && sv_stream) ? sv_stream : stream;       // the stream the filter passes run on
+        rc = svgf_ensure(d->width, d->height, want_stages);
         if (rc) return rc;
-        if (!compute_motion && (!sv_motion.is_set || sv_motion.count < (size_t)d->width * d->height))
+        if (!compute_motion && !sv_handover_only && (!sv_motion.is_set || sv_motion.count < (size_t)d->width * d->height))
             return fail(ATN_ERR_INVALID_ARG, "no motion/depth buffer: call atn_svgf_set_motion_depth or pass compute_motion = 1");
         const bool prof = d->profile != 0;
         PathBuffers pb = buffers(false);
@@ -2498,7 +2535,7 @@ public:
         sv_last_slot = slot;
         sf.tmp = sv_tmp.p; sf.motion = sv_motion.buf.p; sf.primary = sv_primary[slot].p; sf.contribs = sv_contribs[slot].p;
         sf.g_nd = path_pass ? sv_gnd[slot].p : nullptr; sf.g_am = path_pass ? sv_gam[slot].p : nullptr;
-        sf.out = sv_out.p; sf.stages = stages_host ? sv_stages.p : nullptr;
+        sf.out = sv_out.p; sf.stages = want_stages ? sv_stages.p : nullptr;
         mat_mul(sv_mtx.V2C, sv_mtx.W2V, sf.w2c);
         mat_mul(sv_mtx.V2C, sv_mtx.prevW2V, sf.prev_w2c);
         sf.width = d->width; sf.height = d->height; sf.frame = d->frame; sf.atrous_iter_cnt = sv_atrous_iters;
@@ -2531,18 +2568,31 @@ public:
                 if (rc) return rc;
             }
             if (pipelined) {
-                rc = record_scene_read();       // (this bank's "path pass done")
+                rc = record_scene_read();       // (this bank's "path pass done": ev_gather, which the filter half waits for)
                 if (rc) return rc;
-                ATN_HIP(hipStreamWaitEvent(fs, ev_gather, 0));
             }
+            sv_slot = 1 - sv_slot;      // (the next path pass fills the other slot)
         }
+        sv_pass.sf = sf; sv_pass.fs = fs; sv_pass.slot = slot; sv_pass.cur = cur;
+        sv_pass.pipelined = pipelined; sv_pass.path_pass = path_pass; sv_pass.prof = prof;
+        return ATN_OK;
+    }
+
+    // The filter half: everything of OnRender from PrepareForDenoise on, over the planes the path half (or atn_svgf_upload) left, on
+    // the frame's filter stream.  Needs the WHOLE frame in the hand-over planes: on a node that is shard 0 behind the gather.
+    int svgf_filter_half(const atn_destination* d, atn_vec4* out_host, atn_vec4* stages_host)
+    {
+        SvgfFrame sf = sv_pass.sf;
+        hipStream_t fs = sv_pass.fs;
+        const int32_t slot = sv_pass.slot, cur = sv_pass.cur;
+        const bool pipelined = sv_pass.pipelined, prof = sv_pass.prof;
+        if (pipelined && sv_pass.path_pass) ATN_HIP(hipStreamWaitEvent(fs, ev_gather, 0));
         const dim3 gp((((d->width + 7) / 8) + 7) / 8 * 8, (d->height + 31) / 32), tp(256);     // x: multiple of 8 (XCD strips)
-        rc = taa_before_write(fs);      // the prepare pass overwrites the output and motion planes a display tail may still read
+        int rc = taa_before_write(fs);      // the prepare pass overwrites the output and motion planes a display tail may still read
         if (rc) return rc;
         prof_begin(prof, ATN_K_SVGF_PREPARE, fs);
         hipLaunchKernelGGL(k_svgf_prepare, gp, tp, 0, fs, sf);
         prof_end(prof);
-        if (path_pass) sv_slot = 1 - sv_slot;
         if (d->frame > 0) {
             prof_begin(prof, ATN_K_SVGF_TEMPORAL, fs);
             hipLaunchKernelGGL(k_svgf_temporal, gp, tp, 0, fs, sf, 0.98f, 0.05f);
@@ -4253,7 +4303,7 @@ int atn_reset_kernel_times(atn_ctx* ctx)
     CTX_QUIET_OR_FAIL(ctx);
     C_HIP(ctx->r, hipStreamSynchronize(ctx->r.stream));
     ctx->r.prof_collect();
-    for (int i = 0; i < ATN_K_COUNT; i++) { ctx->r.k_ms[i] = 0; ctx->r.k_launches[i] = 0; }
+    for (int i = 0; i < ATN_K_MGPU_COUNT; i++) { ctx->r.k_ms[i] = 0; ctx->r.k_launches[i] = 0; }
     return ATN_OK;
 }
 
@@ -4380,6 +4430,84 @@ int atn_mgpu_set_frames_in_flight(atn_mgpu* mg, int32_t n)
 {
     MG_OR_FAIL(mg);
     return mg_guarded(mg, [&] { return mg->m.on_all([&](int i) { return mg->m.shard[i]->set_frames_in_flight(n); }); });
+}
+// node-wide SVGF (MultiGpu::svgf_render): the filters, their settings and their planes live on shard 0
+int atn_mgpu_svgf_render(atn_mgpu* mg, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&] { return mg->m.svgf_render(dst, compute_motion, out_host, stages_host); });
+}
+int atn_mgpu_svgf_set_motion_depth(atn_mgpu* mg, const atn_vec4* motion_depth, uint32_t n)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&]() -> int {
+        int rc = mg->m.synchronize();
+        if (rc) return rc;
+        PathTracing& r = *mg->m.shard[0];
+        rc = r.set_motion_depth(r.sv_motion, motion_depth, n);
+        return rc ? mg->m.fail(rc, "shard 0: " + r.last_error) : (int)ATN_OK;
+    });
+}
+int atn_mgpu_svgf_reset(atn_mgpu* mg) { MG_OR_FAIL(mg); return mg_guarded(mg, [&] { return mg->m.svgf_reset(); }); }
+int atn_mgpu_svgf_set_atrous_iterations(atn_mgpu* mg, int32_t n)
+{
+    MG_OR_FAIL(mg);
+    if (n < 1 || n > 8) return mg->m.fail(ATN_ERR_INVALID_ARG, "a-trous iteration count out of range");
+    mg->m.shard[0]->sv_atrous_iters = n;
+    return ATN_OK;
+}
+int atn_mgpu_svgf_set_dilate_temporal_weight(atn_mgpu* mg, int32_t on)
+{
+    MG_OR_FAIL(mg);
+    mg->m.shard[0]->sv_dilate_weight = on ? 1 : 0;
+    return ATN_OK;
+}
+int atn_mgpu_svgf_download(atn_mgpu* mg, int32_t which, atn_vec4* out_host)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&]() -> int {
+        atn::MultiGpu& m = mg->m;
+        int rc = m.synchronize();
+        if (rc) return rc;
+        PathTracing& r = *m.shard[0];
+        float4* p = r.sv_w > 0 ? r.svgf_buffer(which) : nullptr;
+        if (!p || !out_host) return m.fail(ATN_ERR_INVALID_ARG, "no such SVGF buffer (or atn_mgpu_svgf_render has not run)");
+        if (hipSetDevice(r.device) != hipSuccess
+            || hipMemcpyAsync(out_host, p, (size_t)r.sv_w * r.sv_h * sizeof(float4), hipMemcpyDeviceToHost, r.stream) != hipSuccess
+            || hipStreamSynchronize(r.stream) != hipSuccess) return m.fail(ATN_ERR_HIP, "SVGF plane download failed");
+        return ATN_OK;
+    });
+}
+void* atn_mgpu_svgf_output_device(atn_mgpu* mg) { return mg ? (void*)mg->m.shard[0]->sv_out.p : nullptr; }
+int atn_mgpu_get_kernel_times(atn_mgpu* mg, int32_t shard, float ms[ATN_K_MGPU_COUNT], uint32_t launches[ATN_K_MGPU_COUNT])
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&]() -> int {
+        atn::MultiGpu& m = mg->m;
+        if (shard < 0 || shard >= m.n || !ms || !launches) return m.fail(ATN_ERR_INVALID_ARG, "atn_mgpu_get_kernel_times: no such shard");
+        int rc = m.synchronize();
+        if (rc) return rc;
+        PathTracing& r = *m.shard[shard];
+        if (hipSetDevice(r.device) != hipSuccess) return m.fail(ATN_ERR_HIP, "hipSetDevice");
+        r.prof_collect();
+        for (int i = 0; i < ATN_K_MGPU_COUNT; i++) { ms[i] = r.k_ms[i]; launches[i] = r.k_launches[i]; }
+        return ATN_OK;
+    });
+}
+int atn_mgpu_reset_kernel_times(atn_mgpu* mg)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&]() -> int {
+        atn::MultiGpu& m = mg->m;
+        int rc = m.synchronize();
+        if (rc) return rc;
+        for (auto& s : m.shard) {
+            if (hipSetDevice(s->device) != hipSuccess) return m.fail(ATN_ERR_HIP, "hipSetDevice");
+            s->prof_collect();
+            for (int i = 0; i < ATN_K_MGPU_COUNT; i++) { s->k_ms[i] = 0; s->k_launches[i] = 0; }
+        }
+        return ATN_OK;
+    });
 }
 void* atn_mgpu_film_device(atn_mgpu* mg) { return mg ? (void*)mg->m.full.p : nullptr; }
 int atn_mgpu_download_film(atn_mgpu* mg, atn_vec4* out_host)

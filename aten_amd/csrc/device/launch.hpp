@@ -120,6 +120,15 @@ inline TileLaunch tile_launch(int32_t width, int32_t height)
     return TileLaunch{ (uint32_t)((((width + 7) / 8) + 7) / 8 * 8), (uint32_t)((height + 31) / 32) };
 }
 
+// Node-wide SVGF's two data movers (device/svgf_gather.hpp), one thread per slot in blocks of 256: the pack over a shard's slots, the
+// unpack over the slots of every shard but the first (0 blocks with one shard: nothing to launch)
+struct GatherLaunch { uint32_t pack_grid, unpack_grid; };
+inline GatherLaunch svgf_gather_launch(uint32_t n_slots, int32_t world)
+{
+    const uint64_t gathered = (uint64_t)(world > 1 ? world - 1 : 0) * n_slots;
+    return GatherLaunch{ (n_slots + 255u) / 256u, (uint32_t)((gathered + 255u) / 256u) };
+}
+
 // ---- regen.hip (PathTracing::render_regen) ----
 void regen_launch_begin(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const atn_camera_param& cam);
 // shadow rays of stage bs (< 0: none) + closest-hit rays of stage bc (< 0: none); `launch` indexes the job-fetch cursor

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import layout as L
-from ._lib import Destination, K_NAMES, lib
+from ._lib import Destination, K_NAMES, MGPU_K_NAMES, lib
 
 
 class AtenAmdError(RuntimeError):
@@ -992,6 +992,53 @@ class MultiGpuPathTracing:
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(self._l.atn_mgpu_download_film(self._mg, out.ctypes.data))
         return out
+
+    # ---- node-wide SVGF (docs/MGPU_SVGF.md): the path pass on every shard, the hand-over planes gathered to shard 0, the filters there
+    SVGF_BUFFERS = PathTracing.SVGF_BUFFERS
+
+    def svgf_render(self, width, height, max_depth=5, rr_depth=3, spp=1, frame=0, compute_motion=False, stages=False,
+                    download=True, profile=False):
+        """PathTracing.svgf_render for the whole node: the filtered frame [h, w, 4] (and the three intermediate puts), byte-equal to
+        one context's whatever the shard count.  After a failure call svgf_reset() before the next frame."""
+        d = Destination(width, height, max_depth, rr_depth, spp, frame, 0, 1, 0, int(profile))
+        out = np.empty((height, width, 4), np.float32) if download else None
+        st = np.empty((3, height, width, 4), np.float32) if stages else None
+        self._check(self._l.atn_mgpu_svgf_render(self._mg, C.byref(d), int(compute_motion),
+                                                 out.ctypes.data if download else None, st.ctypes.data if stages else None))
+        self.width, self.height = width, height
+        return (out, st) if stages else out
+
+    def svgf_set_motion_depth(self, md):
+        md = np.ascontiguousarray(md, np.float32).reshape(-1, 4)
+        self._check(self._l.atn_mgpu_svgf_set_motion_depth(self._mg, md.ctypes.data, len(md)))
+
+    def svgf_reset(self):
+        self._check(self._l.atn_mgpu_svgf_reset(self._mg))
+
+    def svgf_set_dilate_temporal_weight(self, on):
+        self._check(self._l.atn_mgpu_svgf_set_dilate_temporal_weight(self._mg, int(on)))
+
+    def svgf_set_atrous_iterations(self, n):
+        self._check(self._l.atn_mgpu_svgf_set_atrous_iterations(self._mg, n))
+
+    def svgf_buffer(self, name):
+        """A buffer of the last node-wide SVGF frame (shard 0's planes), float32 [h, w, 4]; names as PathTracing.svgf_buffer."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(self._l.atn_mgpu_svgf_download(self._mg, self.SVGF_BUFFERS[name], out.ctypes.data))
+        return out
+
+    def svgf_output_device_ptr(self):
+        return self._l.atn_mgpu_svgf_output_device(self._mg)
+
+    def kernel_times(self, shard=0):
+        """HIP-event time and launch count per kernel class of one shard's profiled frames (MGPU_K_NAMES: 'svgf_pack' on shards
+        1 .. N-1, 'svgf_unpack' on shard 0)."""
+        ms = np.zeros(len(MGPU_K_NAMES), np.float32); n = np.zeros(len(MGPU_K_NAMES), np.uint32)
+        self._check(self._l.atn_mgpu_get_kernel_times(self._mg, shard, ms.ctypes.data, n.ctypes.data))
+        return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(MGPU_K_NAMES)}
+
+    def reset_kernel_times(self):
+        self._check(self._l.atn_mgpu_reset_kernel_times(self._mg))
 
 
 VOLUME_STATE_FLAGS = dict(processed=1, hit=2, sampled=4, absorbed=8, scattered=16, passed=32, connection=64, terminated=256)

@@ -301,7 +301,10 @@ enum { ATN_K_GEN = 0, ATN_K_TRACE_CLOSEST = 1, ATN_K_SHADE = 2, ATN_K_TRACE_SHAD
        ATN_K_ACCUM = 4, ATN_K_GATHER = 5,
        ATN_K_SVGF_PREPARE = 6, ATN_K_SVGF_TEMPORAL = 7, ATN_K_SVGF_VARIANCE = 8, ATN_K_SVGF_ATROUS = 9,
        ATN_K_TRACE_FUSED = 10,      /* shadow rays of bounce b + closest-hit rays of bounce b+1 in one launch */
-       ATN_K_COUNT = 11 };
+       ATN_K_COUNT = 11,
+       /* node-wide SVGF's two data movers (atn_mgpu_get_kernel_times only: atn_get_kernel_times keeps its ATN_K_COUNT entries) */
+       ATN_K_SVGF_PACK = 11, ATN_K_SVGF_UNPACK = 12,
+       ATN_K_MGPU_COUNT = 13 };
 /* HIP-event time (ms) and launch count per kernel class, accumulated over every atn_render with
  * profile = 1 since the last atn_reset_kernel_times. */
 int atn_get_kernel_times(atn_ctx* ctx, float ms[ATN_K_COUNT], uint32_t launches[ATN_K_COUNT]);
@@ -393,6 +396,32 @@ int atn_mgpu_set_frames_in_flight(atn_mgpu* mg, int32_t n);
  * looked at after the burst: its tiles travel once per burst, not once per frame). */
 int atn_mgpu_set_regeneration(atn_mgpu* mg, int32_t mode);
 int atn_mgpu_render_burst(atn_mgpu* mg, const atn_destination* dst, int32_t n_frames, atn_vec4* out_host);
+/* Node-wide SVGF (docs/MGPU_SVGF.md): atn_svgf_render (below) with the path pass -- most of the frame -- spread over the shards.  Every
+ * shard runs the path pass on its tiles; shards 1 .. N-1 pack their pixels of the four planes the path pass hands to the filters
+ * (contributions, normal+depth, albedo+id, primary hit positions: 64 B per pixel) and push them to shard 0's device in one peer copy
+ * each; shard 0 scatters them into its own planes and runs the filter passes there.  The result -- out_host, stages_host, every
+ * plane of atn_mgpu_svgf_download -- is byte-equal to atn_svgf_render on one unsharded context given the same calls in the same
+ * order, whatever N is.  compute_motion 0 (the plane of atn_mgpu_svgf_set_motion_depth) and != 0 (computed from the primary hits),
+ * destination.sample >= 1, and frame == 0 taking the first-frame path, as atn_svgf_render; compute_motion = 2 is
+ * ATN_ERR_UNSUPPORTED (the geometry history has no node-wide form yet).  Regeneration does not apply.  Returns once everything is
+ * enqueued unless a host pointer is given; ordered by events only, so with atn_mgpu_set_frames_in_flight > 1 frame f + 1's path
+ * pass and exchange overlap frame f's filters.  On a failure atn_mgpu_last_error names the shard; the shards may then disagree about
+ * the frame they are at, so the caller must atn_mgpu_svgf_reset before the next atn_mgpu_svgf_render.  May be mixed with
+ * atn_mgpu_render / atn_mgpu_render_burst on one atn_mgpu as atn_svgf_render with atn_render on one context.  The display tail
+ * (atn_taa_resolve) has no node-wide form. */
+int atn_mgpu_svgf_render(atn_mgpu* mg, const atn_destination* dst, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host);
+/* atn_svgf_set_motion_depth / _set_atrous_iterations / _set_dilate_temporal_weight on shard 0 (the filters run there); atn_svgf_reset
+ * on every shard; atn_svgf_download and atn_svgf_output_device of shard 0's planes (`which` as atn_svgf_download). */
+int atn_mgpu_svgf_set_motion_depth(atn_mgpu* mg, const atn_vec4* motion_depth, uint32_t n);
+int atn_mgpu_svgf_reset(atn_mgpu* mg);
+int atn_mgpu_svgf_set_atrous_iterations(atn_mgpu* mg, int32_t n);
+int atn_mgpu_svgf_set_dilate_temporal_weight(atn_mgpu* mg, int32_t on);
+int atn_mgpu_svgf_download(atn_mgpu* mg, int32_t which, atn_vec4* out_host);
+void* atn_mgpu_svgf_output_device(atn_mgpu* mg);
+/* atn_get_kernel_times / atn_reset_kernel_times of one shard / of every shard, with the two classes of the exchange: ATN_K_SVGF_PACK
+ * on shards 1 .. N-1, ATN_K_SVGF_UNPACK on shard 0 (frames rendered with destination.profile = 1).  Waits for the frames in flight. */
+int atn_mgpu_get_kernel_times(atn_mgpu* mg, int32_t shard, float ms[ATN_K_MGPU_COUNT], uint32_t launches[ATN_K_MGPU_COUNT]);
+int atn_mgpu_reset_kernel_times(atn_mgpu* mg);
 
 /* ---- SVGF (next tier, BASELINE config 5) -------------------------------------------------------
  * ≙ aten::SVGFRenderer (src/libaten/renderer/svgf/svgf.{h,cpp}): the path pass with AOV outputs
@@ -400,7 +429,8 @@ int atn_mgpu_render_burst(atn_mgpu* mg, const atn_destination* dst, int32_t n_fr
  * PrepareForDenoise, TemporalReprojection + AccumulateMoments (frame > 0), EstimateVariance,
  * atrous_iter_cnt x (3x3 Gauss of the variance + ExecAtrousWaveletFilter + PostProcessForAtrousFilter),
  * CopyFromTeporaryColorBufferToAov -- with the AOV / moment buffers of two frames resident in HBM.
- * `dst->frame == 0` takes the first-frame path (svgf.cpp:519-525,543-551).  One GPU only.
+ * `dst->frame == 0` takes the first-frame path (svgf.cpp:519-525,543-551).  One context renders the whole frame (a context with
+ * a screen shard is refused: the filters' footprints cross tiles); the node-wide form is atn_mgpu_svgf_render, above.
  *
  * out_host (may be NULL): what dst.buffer holds when OnRender returns (the last a-trous iteration's
  * albedo-multiplied colour), vec4[w*h], row 0 = bottom.  stages_host (may be NULL): 3 x vec4[w*h], the

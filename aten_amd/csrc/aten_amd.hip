@@ -4648,6 +4648,113 @@ int atn_trace_shadow(atn_ctx* ctx, const atn_shadow_query* queries_host, uint32_
     return ATN_OK;
 }
 
+int atn_shade_stage(atn_ctx* ctx, const atn_shade_call* call, const atn_shade_vertex* records_host, uint32_t n, atn_shade_result* out_host)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    PathTracing& r = ctx->r;
+    if (!r.has_scene) return r.fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+    if (!call) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: null call");
+    if (call->flavour != 0 && call->flavour != 1) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: unknown flavour");
+    const bool svgf = call->flavour == 1;
+    if (call->chunk_items < 0 || call->chunk_items > atn::kChunkItems) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: chunk_items outside 0..4");
+    if (call->queue_order < 0 || call->queue_order > 1) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: unknown queue order");
+    if (call->width <= 0 || call->height <= 0 || call->max_depth <= 0 || call->sample < 0) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: bad frame");
+    if (call->bounce < 0 || call->bounce >= call->max_depth) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: bounce outside 0 .. max_depth - 1");
+    if (!r.has_camera || r.n_seeds == 0) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: camera / sampler missing");
+    if (r.shade_math_relaxed) return r.fail(ATN_ERR_UNSUPPORTED, "atn_shade_stage: the relaxed-math kernel is not the parity path: atn_set_shade_math(0)");
+    if (n == 0) return ATN_OK;
+    if (!records_host || !out_host) return r.fail(ATN_ERR_INVALID_ARG, "null records / output");
+    C_HIP(r, hipSetDevice(r.device));
+    const int32_t sr = r.rank, sw = r.world;
+    r.rank = 0; r.world = 1;        // (the whole frame's slots, as atn_generate_paths)
+    struct Restore { PathTracing& r; int32_t rank, world; ~Restore() { r.rank = rank; r.world = world; } } restore{ r, sr, sw };
+    int rc = r.ensure_frame(call->width, call->height, call->max_depth);
+    if (rc) return rc;
+    const uint32_t n_slots = r.n_slots;
+    // record -> the slot its pixel owns (slot_to_pixel's inverse: 8 x 8 tiles); pixels distinct and inside the frame, hit records inside the scene
+    const int32_t tiles_x = (call->width + 7) / 8;
+    std::vector<int32_t> rec_of(n_slots, -1);
+    std::vector<uint32_t> queue(n);
+    const uint32_t known = atn::F_TERMINATED | atn::F_SINGULAR | atn::F_HIT | atn::F_LAST_SPECULAR;
+    const size_t n_tris = r.n_scene_tris < r.tris.n ? r.n_scene_tris : r.tris.n;
+    for (uint32_t i = 0; i < n; i++) {
+        const atn_shade_vertex& v = records_host[i];
+        if (v.pixel < 0 || (int64_t)v.pixel >= (int64_t)call->width * call->height) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: a pixel outside the frame");
+        if ((v.flags & ~known) || (v.flags & atn::F_TERMINATED)) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: a record that is terminated or carries unknown flag bits");
+        if (v.objid >= 0 && ((size_t)v.objid >= r.objects.n || v.tri_id < 0 || (size_t)v.tri_id >= n_tris
+                             || !(v.a >= -1.0F && v.a <= 2.0F && v.b >= -1.0F && v.b <= 2.0F)))
+            return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: a hit record outside the scene");
+        const int32_t x = v.pixel % call->width, y = v.pixel / call->width;
+        const uint32_t slot = (uint32_t)((y / 8) * tiles_x + x / 8) * 64u + (uint32_t)((y & 7) * 8 + (x & 7));
+        if (slot >= n_slots) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: a pixel outside the frame");
+        if (rec_of[slot] >= 0) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: two records share a pixel");
+        rec_of[slot] = (int32_t)i;
+        queue[i] = slot;
+    }
+    if (call->queue_order == 0) {       // a fixed shuffle (Fisher-Yates over a 64-bit LCG), as atn_trace_shadow's
+        uint64_t lcg = 0x9e3779b97f4a7c15ull;
+        for (uint32_t i = n - 1u; i > 0u; i--) {
+            lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+            std::swap(queue[i], queue[(uint32_t)((lcg >> 33) % (uint64_t)(i + 1u))]);
+        }
+    }
+    atn_destination d{}; d.width = call->width; d.height = call->height; d.maxDepth = call->max_depth; d.russianRouletteDepth = call->rr_depth;
+    d.sample = 1; d.frame = call->frame;
+    atn::FrameParams fp = r.frame_params(d);
+    fp.sample = call->sample;
+    atn::PathBuffers pb = r.buffers(false);
+    // the launch the renderer would make for n live paths: its plan, its flavour; chunk_items forced where the caller asks
+    atn::PassPlan plan = r.plan_pass(svgf ? atn::PassKind::Svgf : atn::PassKind::Serial, n);
+    if (call->chunk_items) {
+        plan.shade_items = call->chunk_items;
+        plan.shade_grid = atn::grid_for((n + (uint32_t)plan.shade_items - 1u) / (uint32_t)plan.shade_items);
+    }
+    fp.chunk_items = plan.shade_items;
+    atn::DevBuf<atn_shade_vertex> drec; atn::DevBuf<atn_shade_result> dout; atn::DevBuf<int32_t> drec_of; atn::DevBuf<uint32_t> dqueue, seen, errs;
+    C_HIP(r, drec.resize(n)); C_HIP(r, dout.resize(n)); C_HIP(r, drec_of.resize(n_slots)); C_HIP(r, dqueue.resize(n)); C_HIP(r, seen.resize(n_slots)); C_HIP(r, errs.resize(4));
+    // "svgf": three AOV planes of the probe's own, a texel per pixel -- the context needs no SVGF frame behind it -- and the fourth row
+    // of W2C as SVGFRenderer's frame computes it from the camera (FrameMatrices::advance on a fresh pair of matrices)
+    atn::DevBuf<float4> aov_nd, aov_am, aov_primary;
+    atn::SvgfShade sv{};
+    const uint32_t n_pixels = (uint32_t)call->width * (uint32_t)call->height;
+    if (svgf) {
+        C_HIP(r, aov_nd.resize(n_pixels)); C_HIP(r, aov_am.resize(n_pixels)); C_HIP(r, aov_primary.resize(n_pixels));
+        sv.nd = aov_nd.p; sv.am = aov_am.p; sv.primary = aov_primary.p;
+        atn::FrameMatrices fm; float w2c[16];
+        fm.advance(r.camera);
+        atn::mat_mul(fm.V2C, fm.W2V, w2c);
+        sv.w2c3[0] = w2c[12]; sv.w2c3[1] = w2c[13]; sv.w2c3[2] = w2c[14]; sv.w2c3[3] = w2c[15];
+    }
+    C_HIP(r, hipMemcpyAsync(drec.p, records_host, (size_t)n * sizeof(atn_shade_vertex), hipMemcpyHostToDevice, r.stream));
+    C_HIP(r, hipMemcpyAsync(drec_of.p, rec_of.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, r.stream));
+    C_HIP(r, hipMemcpyAsync(dqueue.p, queue.data(), (size_t)n * 4, hipMemcpyHostToDevice, r.stream));
+    C_HIP(r, hipMemsetAsync(seen.p, 0, (size_t)n_slots * 4, r.stream));
+    C_HIP(r, hipMemsetAsync(errs.p, 0, 16, r.stream));
+    C_HIP(r, hipMemsetAsync(r.counters.p, 0, (size_t)4 * r.counters_depth * 4, r.stream));
+    C_HIP(r, hipMemcpyAsync(pb.q_count + call->bounce, &n, 4, hipMemcpyHostToDevice, r.stream));
+    const dim3 g_slots((n_slots + 255u) / 256u), t256(256);
+    hipLaunchKernelGGL(atn::k_shade_probe_fill, g_slots, t256, 0, r.stream, pb, (const atn_shade_vertex*)drec.p, (const int32_t*)drec_of.p,
+                       (const uint32_t*)dqueue.p, n, n_slots, call->bounce, sv, n_pixels);
+    C_HIP(r, hipGetLastError());
+    if (svgf) r.launch_shade<true>(plan, r.stream, pb, fp, call->bounce, sv);
+    else r.launch_shade<false>(plan, r.stream, pb, fp, call->bounce, atn::SvgfShade{});
+    C_HIP(r, hipGetLastError());
+    hipLaunchKernelGGL(atn::k_shade_probe_queues, g_slots, t256, 0, r.stream, pb, (const int32_t*)drec_of.p, (const uint32_t*)dqueue.p, n, n_slots,
+                       call->bounce, (int32_t)r.counters_depth, seen.p, errs.p);
+    hipLaunchKernelGGL(atn::k_shade_probe_check, g_slots, t256, 0, r.stream, pb, (const atn_shade_vertex*)drec.p, (const int32_t*)drec_of.p, n_slots,
+                       (const uint32_t*)seen.p, dout.p, errs.p, sv, n_pixels, call->width);
+    C_HIP(r, hipGetLastError());
+    uint32_t he[4] = {};
+    C_HIP(r, hipMemcpyAsync(out_host, dout.p, (size_t)n * sizeof(atn_shade_result), hipMemcpyDeviceToHost, r.stream));
+    C_HIP(r, hipMemcpyAsync(he, errs.p, 16, hipMemcpyDeviceToHost, r.stream));
+    C_HIP(r, hipStreamSynchronize(r.stream));
+    if (he[0] || he[1] || he[2] || he[3])
+        return r.fail(ATN_ERR_HIP, "atn_shade_stage: " + std::to_string(he[0]) + " unused slots changed, " + std::to_string(he[1])
+                                   + " planes changed that a vertex leaves alone, " + std::to_string(he[2]) + " slots queued twice, "
+                                   + std::to_string(he[3]) + " queue entries that were not handed in");
+    return ATN_OK;
+}
+
 int atn_cmj_samples(atn_ctx* ctx, uint32_t index, uint32_t dimension, uint32_t scramble, int32_t n, float* out_host)
 {
     CTX_QUIET_OR_FAIL(ctx);

@@ -1807,6 +1807,135 @@ __global__ void __launch_bounds__(256) k_shadow_probe_check(PathBuffers pb, cons
     out[slot >> 1] = visible ? 1u : 0u;
 }
 
+// ---- the shade-stage probe (atn_shade_stage): caller-given vertices through ONE launch of the renderer's own shade kernel ---------------
+// Record i lives in the slot its pixel owns (rec_of[slot] = i, -1 for every other slot); the live queue comes from the host.  Every
+// other slot, every plane a vertex does not read, the next queue and the shadow queue carry patterns no kernel writes.  After the
+// launch k_shade_probe_queues walks the two queues the kernel appended to (seen[slot]: bit 0 = in the next queue, bit 1 = in the shadow
+// queue) and k_shade_probe_check reads the results and holds everything else against what the fill wrote.
+// errs: [0] an unused slot changed, [1] a plane changed that a vertex leaves alone (the hit record, accum, done; the shadow record of a
+// slot that is not in the shadow queue; the live queue; a queue entry behind its counter; a counter of another depth), [2] a slot appears
+// in a queue twice, [3] a queue holds a slot that was not handed in
+constexpr uint32_t kShadeProbeQueueMark = 0xffffffffu;
+ATN_DEV uint32_t shade_probe_done_mark(uint32_t slot) { return 0x5a5a0000u | (slot & 0xffffu); }
+ATN_DEV float4 shade_probe_isect(const atn_shade_vertex& v)
+{
+    return make_float4(__int_as_float(v.objid), v.a, v.b, __int_as_float(v.tri_id));
+}
+__global__ void __launch_bounds__(256) k_shade_probe_fill(PathBuffers pb, const atn_shade_vertex* __restrict__ recs, const int32_t* __restrict__ rec_of,
+                                                          const uint32_t* __restrict__ queue_in, uint32_t n, uint32_t n_slots, int32_t bounce,
+                                                          SvgfShade sv, uint32_t n_pixels)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_slots) return;
+    // the "svgf" flavour's AOV planes are indexed by pixel (n_pixels <= n_slots): thread k marks texel k of each
+    if (sv.nd && slot < n_pixels) { sv.nd[slot] = shadow_probe_mark(slot, 17u); sv.am[slot] = shadow_probe_mark(slot, 18u); sv.primary[slot] = shadow_probe_mark(slot, 19u); }
+    pb.queue[bounce & 1][slot] = slot < n ? queue_in[slot] : kShadeProbeQueueMark;
+    pb.queue[(bounce + 1) & 1][slot] = kShadeProbeQueueMark;
+    pb.shadow_q[slot] = kShadeProbeQueueMark;
+    pb.sh_o[slot] = shadow_probe_mark(slot, 13u); pb.sh_d[slot] = shadow_probe_mark(slot, 14u); pb.sh_c[slot] = shadow_probe_mark(slot, 15u);
+    pb.accum[slot] = shadow_probe_mark(slot, 16u);
+    pb.done[slot] = shade_probe_done_mark(slot);
+    const int32_t i = rec_of[slot];
+    if (i < 0) {
+        pb.ray_o[slot] = shadow_probe_mark(slot, 8u); pb.ray_d[slot] = shadow_probe_mark(slot, 9u); pb.thr[slot] = shadow_probe_mark(slot, 10u);
+        pb.contrib[slot] = shadow_probe_mark(slot, 11u); pb.isect[slot] = shadow_probe_mark(slot, 12u);
+        return;
+    }
+    const atn_shade_vertex v = recs[i];
+    pb.ray_o[slot] = make_float4(v.org[0], v.org[1], v.org[2], v.pdfb);
+    pb.ray_d[slot] = make_float4(v.dir[0], v.dir[1], v.dir[2], __uint_as_float(v.flags));
+    pb.thr[slot] = make_float4(v.throughput[0], v.throughput[1], v.throughput[2], __uint_as_float(v.dimension));
+    pb.contrib[slot] = make_float4(v.contrib[0], v.contrib[1], v.contrib[2], 0.0F);
+    pb.isect[slot] = shade_probe_isect(v);
+}
+__global__ void __launch_bounds__(256) k_shade_probe_queues(PathBuffers pb, const int32_t* __restrict__ rec_of, const uint32_t* __restrict__ queue_in,
+                                                            uint32_t n, uint32_t n_slots, int32_t bounce, int32_t counters_depth,
+                                                            uint32_t* __restrict__ seen, uint32_t* errs)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_slots) return;
+    const uint32_t n_next = pb.q_count[bounce + 1], n_shadow = pb.sh_count[bounce];
+    if (j == 0u && (n_next > n_slots || n_shadow > n_slots)) atomicAdd(&errs[3], 1u);
+    const uint32_t* qn = pb.queue[(bounce + 1) & 1];
+    // what the launch only reads, or must not reach: the live queue as handed over, the entries behind both counters, the counters of
+    // every other depth (q_count[bounce] = n; the four counter rows are counters_depth entries each, in one block)
+    if (pb.queue[bounce & 1][j] != (j < n ? queue_in[j] : kShadeProbeQueueMark)) atomicAdd(&errs[1], 1u);
+    if (j >= n_next && qn[j] != kShadeProbeQueueMark) atomicAdd(&errs[1], 1u);
+    if (j >= n_shadow && pb.shadow_q[j] != kShadeProbeQueueMark) atomicAdd(&errs[1], 1u);
+    if (j == 0u) {      // (one thread: a small frame has fewer slots than counters)
+        for (uint32_t k = 0; k < (uint32_t)(4 * counters_depth); k++) {
+            const uint32_t c = pb.q_count[k];       // (q_count is the block's first row)
+            const bool mine = k == (uint32_t)bounce || k == (uint32_t)(bounce + 1) || k == (uint32_t)(counters_depth + bounce);
+            if (k == (uint32_t)bounce ? c != n : (!mine && c != 0u)) atomicAdd(&errs[1], 1u);
+        }
+    }
+    if (j < n_next) {
+        const uint32_t s = qn[j];
+        if (s >= n_slots || rec_of[s] < 0) atomicAdd(&errs[3], 1u);
+        else if (atomicOr(&seen[s], 1u) & 1u) atomicAdd(&errs[2], 1u);
+    }
+    if (j < n_shadow) {
+        const uint32_t s = pb.shadow_q[j];
+        if (s >= n_slots || rec_of[s] < 0) atomicAdd(&errs[3], 1u);
+        else if (atomicOr(&seen[s], 2u) & 2u) atomicAdd(&errs[2], 1u);
+    }
+}
+__global__ void __launch_bounds__(256) k_shade_probe_check(PathBuffers pb, const atn_shade_vertex* __restrict__ recs, const int32_t* __restrict__ rec_of,
+                                                           uint32_t n_slots, const uint32_t* __restrict__ seen, atn_shade_result* __restrict__ out, uint32_t* errs,
+                                                           SvgfShade sv, uint32_t n_pixels, int32_t width)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_slots) return;
+    if (sv.nd && slot < n_pixels) {
+        // texel `slot` of the AOV planes: unless the pixel's own slot carries a record it still holds its marks
+        const int32_t x = (int32_t)slot % width, y = (int32_t)slot / width;
+        const uint32_t own = (uint32_t)((y / 8) * ((width + 7) / 8) + x / 8) * 64u + (uint32_t)((y & 7) * 8 + (x & 7));
+        if ((own >= n_slots || rec_of[own] < 0)
+            && !(same_bits(sv.nd[slot], shadow_probe_mark(slot, 17u)) && same_bits(sv.am[slot], shadow_probe_mark(slot, 18u))
+                 && same_bits(sv.primary[slot], shadow_probe_mark(slot, 19u)))) atomicAdd(&errs[0], 1u);
+    }
+    const int32_t i = rec_of[slot];
+    const bool aside = same_bits(pb.accum[slot], shadow_probe_mark(slot, 16u)) && pb.done[slot] == shade_probe_done_mark(slot);
+    const bool shadow_untouched = same_bits(pb.sh_o[slot], shadow_probe_mark(slot, 13u)) && same_bits(pb.sh_d[slot], shadow_probe_mark(slot, 14u))
+                               && same_bits(pb.sh_c[slot], shadow_probe_mark(slot, 15u));
+    if (i < 0) {
+        const bool ok = aside && shadow_untouched && same_bits(pb.ray_o[slot], shadow_probe_mark(slot, 8u)) && same_bits(pb.ray_d[slot], shadow_probe_mark(slot, 9u))
+                     && same_bits(pb.thr[slot], shadow_probe_mark(slot, 10u)) && same_bits(pb.contrib[slot], shadow_probe_mark(slot, 11u))
+                     && same_bits(pb.isect[slot], shadow_probe_mark(slot, 12u));
+        if (!ok) atomicAdd(&errs[0], 1u);
+        return;
+    }
+    const uint32_t sn = seen[slot];
+    const bool goes_on = (sn & 1u) != 0u, has_shadow = (sn & 2u) != 0u;
+    if (!(aside && same_bits(pb.isect[slot], shade_probe_isect(recs[i])) && (has_shadow || shadow_untouched))) atomicAdd(&errs[1], 1u);
+    atn_shade_result r{};
+    const float4 ro = pb.ray_o[slot], rd = pb.ray_d[slot], th = pb.thr[slot], c = pb.contrib[slot];
+    r.flags = __float_as_uint(rd.w);
+    r.goes_on = goes_on ? 1u : 0u; r.has_shadow = has_shadow ? 1u : 0u;
+    r.contrib[0] = c.x; r.contrib[1] = c.y; r.contrib[2] = c.z;
+    if (goes_on) {
+        r.dimension = __float_as_uint(th.w); r.pdfb = ro.w;
+        r.org[0] = ro.x; r.org[1] = ro.y; r.org[2] = ro.z;
+        r.dir[0] = rd.x; r.dir[1] = rd.y; r.dir[2] = rd.z;
+        r.throughput[0] = th.x; r.throughput[1] = th.y; r.throughput[2] = th.z;
+    }
+    if (has_shadow) {
+        const float4 so = pb.sh_o[slot], sd = pb.sh_d[slot], sc = pb.sh_c[slot];
+        r.light_bits = __float_as_uint(sd.w); r.sh_c_w = __float_as_uint(sc.w); r.sh_dist = so.w;
+        r.sh_o[0] = so.x; r.sh_o[1] = so.y; r.sh_o[2] = so.z;
+        r.sh_d[0] = sd.x; r.sh_d[1] = sd.y; r.sh_d[2] = sd.z;
+        r.sh_c[0] = sc.x; r.sh_c[1] = sc.y; r.sh_c[2] = sc.z;
+    }
+    if (sv.nd) {
+        const uint32_t px = (uint32_t)recs[i].pixel;
+        const float4 nd = sv.nd[px], am = sv.am[px], pr = sv.primary[px];
+        if (!same_bits(nd, shadow_probe_mark(px, 17u))) { r.aov_written |= 1u; r.aov_nd[0] = nd.x; r.aov_nd[1] = nd.y; r.aov_nd[2] = nd.z; r.aov_nd[3] = nd.w; }
+        if (!same_bits(am, shadow_probe_mark(px, 18u))) { r.aov_written |= 2u; r.aov_am[0] = am.x; r.aov_am[1] = am.y; r.aov_am[2] = am.z; r.aov_am[3] = am.w; }
+        if (!same_bits(pr, shadow_probe_mark(px, 19u))) { r.aov_written |= 4u; r.aov_primary[0] = pr.x; r.aov_primary[1] = pr.y; r.aov_primary[2] = pr.z; r.aov_primary[3] = pr.w; }
+    }
+    out[i] = r;
+}
+
 // one thread per (index, dimension, scramble) triple: `draws` successive nextSample()
 __global__ void __launch_bounds__(256) k_cmj_batch(uint32_t n, const uint32_t* __restrict__ index, const uint32_t* __restrict__ dim,
                                                    const uint32_t* __restrict__ scramble, int draws, float* __restrict__ out)

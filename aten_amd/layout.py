@@ -76,6 +76,39 @@ RAY = np.dtype([("org", f4, 3), ("dir", f4, 3)])
 # atn_shadow_query, 36 B: one query of the shadow-ray probe (flags: bit 0 stencil ALWAYS at the shaded surface, bit 1 last vertex)
 SHADOW_QUERY = np.dtype([("org", f4, 3), ("dir", f4, 3), ("dist_to_light", f4), ("light", i4), ("flags", np.uint32)])
 
+# atn_shade_vertex, 80 B / atn_shade_result, 168 B / atn_shade_call: the shade-stage probe (atn_shade_stage and its CPU twin)
+SHADE_VERTEX = np.dtype([
+    ("org", f4, 3), ("pdfb", f4), ("dir", f4, 3), ("flags", np.uint32), ("throughput", f4, 3), ("dimension", np.uint32),
+    ("contrib", f4, 3), ("objid", i4), ("a", f4), ("b", f4), ("tri_id", i4), ("pixel", i4),
+])
+SHADE_RESULT = np.dtype([
+    ("flags", np.uint32), ("goes_on", np.uint32), ("has_shadow", np.uint32), ("dimension", np.uint32),
+    ("contrib", f4, 3), ("pdfb", f4), ("org", f4, 3), ("light_bits", np.uint32), ("dir", f4, 3), ("sh_c_w", np.uint32),
+    ("throughput", f4, 3), ("sh_dist", f4), ("sh_o", f4, 3), ("sh_d", f4, 3), ("sh_c", f4, 3),
+    ("aov_written", np.uint32), ("aov_nd", f4, 4), ("aov_am", f4, 4), ("aov_primary", f4, 4),
+])
+SHADE_CALL = np.dtype([
+    ("width", i4), ("height", i4), ("frame", np.uint32), ("sample", i4), ("bounce", i4), ("max_depth", i4), ("rr_depth", i4),
+    ("flavour", i4), ("chunk_items", i4), ("queue_order", i4),
+])
+SHADE_FLAVOURS = {"plain": 0, "svgf": 1}
+SHADE_QUEUE_ORDERS = {"shuffled": 0, "given": 1}
+assert SHADE_VERTEX.itemsize == 80 and SHADE_RESULT.itemsize == 168 and SHADE_CALL.itemsize == 40
+
+
+def shade_call(width, height, bounce, max_depth, rr_depth, frame=0, sample=0, flavour="plain", chunk_items=0, queue_order="shuffled"):
+    """atn_shade_call from names; an unknown flavour or queue order is a ValueError."""
+    if flavour not in SHADE_FLAVOURS:
+        raise ValueError("unknown shade flavour %r" % (flavour,))
+    if queue_order not in SHADE_QUEUE_ORDERS:
+        raise ValueError("unknown queue order %r" % (queue_order,))
+    c = np.zeros((), SHADE_CALL)
+    c["width"] = width; c["height"] = height; c["frame"] = frame; c["sample"] = sample; c["bounce"] = bounce
+    c["max_depth"] = max_depth; c["rr_depth"] = rr_depth; c["flavour"] = SHADE_FLAVOURS[flavour]; c["chunk_items"] = chunk_items
+    c["queue_order"] = SHADE_QUEUE_ORDERS[queue_order]
+    return c
+
+
 # aten::SkinningVertex, 72 B (src/libaten/deformable/SkinningVertex.h:7-14)
 SKINNING_VERTEX = np.dtype([
     ("position", f4, 4), ("normal", f4, 3), ("clr", np.uint8, 4), ("uv", f4, 2),

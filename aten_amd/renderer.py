@@ -783,6 +783,19 @@ class PathTracing:
         self._check(self._l.atn_trace_shadow(self._ctx, q.ctypes.data, n, self.SHADOW_FLAVOURS[flavour], out.ctypes.data))
         return out
 
+    def shade_stage(self, records, width, height, bounce, max_depth, rr_depth, frame=0, sample=0, flavour="plain", chunk_items=0,
+                    queue_order="shuffled"):
+        """PathTracing::shade / ShadeMiss for n caller-given vertices (layout.SHADE_VERTEX) through ONE launch of the production shade
+        kernel (atn_shade_stage): the instantiation render() picks for the uploaded scene, at this context's wave setting.  Returns
+        layout.SHADE_RESULT [n]: what the next stages can observe -- flags, contrib, membership in the next queue and the shadow queue as
+        the kernel appended them, the next ray / pdf / throughput / dimension of a path that goes on, the shadow record of a path that
+        has one; everything else zero.  chunk_items 0 = the launch plan's, 1..4 forced; queue_order 'shuffled' or 'given'."""
+        rec = np.ascontiguousarray(records, L.SHADE_VERTEX)
+        call = L.shade_call(width, height, bounce, max_depth, rr_depth, frame, sample, flavour, chunk_items, queue_order)
+        out = np.zeros(len(rec), L.SHADE_RESULT)
+        self._check(self._l.atn_shade_stage(self._ctx, call.ctypes.data, rec.ctypes.data, len(rec), out.ctypes.data))
+        return out
+
     def cmj_samples(self, index, dimension, scramble, n):
         out = np.zeros(n, np.float32)
         self._check(self._l.atn_cmj_samples(self._ctx, index, dimension, scramble, n, out.ctypes.data))

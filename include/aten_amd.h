@@ -677,6 +677,29 @@ int atn_trace_closest(atn_ctx* ctx, const atn_ray* rays_host, uint32_t n, float 
  * out_visible[i] = 1 when query i's contribution was added.  ATN_ERR_NO_SCENE without a scene, ATN_ERR_INVALID_ARG for null pointers,
  * an unknown flavour or a light index outside the scene's lights, ATN_ERR_UNSUPPORTED for a scene without lights; n == 0 is a no-op. */
 int atn_trace_shadow(atn_ctx* ctx, const atn_shadow_query* queries_host, uint32_t n, int32_t flavour, uint8_t* out_visible);
+/* PathTracing::shade + ShadeMiss (renderer/pathtracing/pathtracing.cpp:91-236, pathtracing_impl.h:112-264, 353-509, 680-743,
+ * pathtracing_nee_impl.h:23-95) for n caller-given vertices (atn_shade_vertex, aten_layout.h), through ONE launch of the PRODUCTION
+ * shade kernel: a fill kernel writes each record into the context's own path buffers, in the slot its pixel owns, and a pattern no
+ * kernel writes into every other slot, every plane a vertex does not read and both output queues; the live queue is handed over
+ * shuffled (queue_order 0) or in the records' order (1); the launch goes through the renderer's own launcher, so it is the
+ * instantiation atn_render picks for the uploaded scene's material set at the context's wave setting (ATEN_AMD_SHADE_WAVES), with the
+ * chunk size of the launch plan or the forced one.  A check kernel then reads the results.
+ * THE CONTRACT is what the next stages can observe (atn_shade_result): the flags, contrib, membership in the next bounce's queue and in
+ * the shadow queue -- read from the queues the kernel appended to, not recomputed -- and, for a path that goes on, the next ray, pdf,
+ * throughput and sampler dimension; for a path with a shadow ray, sh_o, sh_d and sh_c with their light bits.  What the reference
+ * computes but nobody reads is NOT part of it: the shadow ray of a path that ended in this vertex, and the BSDF sample, throughput and
+ * sampler position of a path that does not go on.  The kernel skips those on purpose; both this entry and its CPU twin report zeros.
+ * Flavour 0 "plain" is k_shade<false, MS>.  Flavour 1 "svgf" is k_shade<true, MS> (SVGFRenderer::Shade, svgf/svgf.cpp:89-229): the
+ * entry allocates three AOV planes of its own, a texel per pixel, and computes W2C from the camera as an SVGF frame does, so the context
+ * needs no SVGF frame behind it; the result reports which of the three texels of its pixel the vertex wrote (aov_written) and their
+ * values.  The look-ahead, deferred-NEE, regenerated and relaxed-math flavours are not served.
+ * ATN_ERR_HIP with counts when an unused slot or AOV texel changed, a plane changed that a vertex leaves alone (hit record, accum,
+ * done, the shadow record of a slot outside the shadow queue, the live queue, a queue entry behind its counter, a counter of another
+ * depth), a slot is queued twice, or a queue holds a slot that was not handed in.
+ * ATN_ERR_NO_SCENE without a scene; ATN_ERR_INVALID_ARG for null pointers, an unknown flavour or queue order, chunk_items > 4, a bounce
+ * at or beyond max_depth, a pixel outside the frame, two records on one pixel, a terminated record, a hit record outside the scene;
+ * ATN_ERR_UNSUPPORTED under atn_set_shade_math(1); n == 0 is a no-op. */
+int atn_shade_stage(atn_ctx* ctx, const atn_shade_call* call, const atn_shade_vertex* records_host, uint32_t n, atn_shade_result* out_host);
 /* n successive CMJ::nextSample() (src/libaten/sampler/cmj.h:32-37). */
 int atn_cmj_samples(atn_ctx* ctx, uint32_t index, uint32_t dimension, uint32_t scramble, int32_t n, float* out_host);
 /* For each of n (index, dimension, scramble) triples: CMJ::init then `draws` x nextSample()

@@ -264,6 +264,41 @@ typedef struct atn_shadow_query {
     uint32_t flags;
 } atn_shadow_query;
 
+/* ---- the shade-stage probe (atn_shade_stage and its CPU twin): what the shade kernel READS for one path, 80 B, and what the next
+ *      stages can OBSERVE of it afterwards, 168 B.  Flag bits: 1 terminated, 2 singular, 4 hit, 8 last hit was Specular (SVGF only). */
+typedef struct atn_shade_vertex {
+    float org[3];  float pdfb;              /*  0: ray origin, the pdf the previous vertex's BSDF sample had */
+    float dir[3];  uint32_t flags;          /* 16 */
+    float throughput[3]; uint32_t dimension;    /* 32: the CMJ dimension counter in front of this vertex */
+    float contrib[3];                       /* 48: what the path has gathered so far */
+    int32_t objid; float a, b; int32_t tri_id;  /* 60: the hit record; objid < 0 = a miss */
+    int32_t pixel;                          /* 76: y * width + x: it selects the slot, the seed and the screen position */
+} atn_shade_vertex;
+
+typedef struct atn_shade_result {
+    uint32_t flags;                         /*  0 */
+    uint32_t goes_on;                       /*  4: the slot is in the next bounce's queue */
+    uint32_t has_shadow;                    /*  8: the slot is in the shadow queue */
+    uint32_t dimension;                     /* 12: goes_on only */
+    float contrib[3]; float pdfb;           /* 16: contrib always; pdfb goes_on only */
+    float org[3];  uint32_t light_bits;     /* 32: the next ray (goes_on only); sh_d.w (has_shadow only): light index, bit 30 = stencil ALWAYS */
+    float dir[3];  uint32_t sh_c_w;         /* 48: sh_c.w, the light bits again (has_shadow only) */
+    float throughput[3]; float sh_dist;     /* 64: goes_on only; distToLight (has_shadow only) */
+    float sh_o[3]; float sh_d[3]; float sh_c[3];    /* 80: the shadow ray and its lightcontrib (has_shadow only) */
+    /* flavour "svgf" only (zero otherwise): what the vertex wrote into the three AOV planes at its pixel */
+    uint32_t aov_written;                   /* 116: bit 0 normal_depth, bit 1 albedo_meshid, bit 2 primary position */
+    float aov_nd[4]; float aov_am[4]; float aov_primary[4];    /* 120: the texels written, zero where the bit is clear */
+} atn_shade_result;
+
+typedef struct atn_shade_call {
+    int32_t width, height;
+    uint32_t frame;
+    int32_t sample, bounce, max_depth, rr_depth;
+    int32_t flavour;        /* 0 "plain": the serial path tracer's shade kernel; 1 "svgf": SVGFRenderer's, with its AOV planes */
+    int32_t chunk_items;    /* 0: what the launch plan picks; 1..4 forces the queue entries per thread and chunk */
+    int32_t queue_order;    /* 0: the live queue is handed over shuffled; 1: in the order of the records */
+} atn_shade_call;
+
 /* ---- one texture: aten::texture::colors() is vec4[w*h] (src/libaten/image/texture.h:104-122) */
 typedef struct atn_texture_desc {
     const atn_vec4* texels;

@@ -332,6 +332,237 @@ void orc_render(const atn_scene_desc* scene, const atn_camera_param* camera,
 int orc_num_procs() { return omp_get_num_procs(); }
 
 // ---------------------------------------------------------------------------------------------------
+// The shade stage, one vertex at a time: the twin of atn_shade_stage (include/aten_amd.h).
+// ---------------------------------------------------------------------------------------------------
+static const uint32_t kFlagTerminated = 1u, kFlagSingular = 2u, kFlagHit = 4u, kFlagLastSpecular = 8u;
+// category bits of orc_shade_stage (tests/shade_vertices.py names them in this order)
+enum : uint32_t {
+    CAT_MISS_B0 = 1u << 0, CAT_MISS_DEEP = 1u << 1, CAT_MISS_B1_SINGULAR = 1u << 2,
+    CAT_EMIT_FRONT_B0 = 1u << 3, CAT_EMIT_FRONT_DEEP = 1u << 4, CAT_EMIT_BACK = 1u << 5, CAT_EMIT_NO_LIGHT = 1u << 6,
+    CAT_TOON_FIRST = 1u << 7, CAT_TOON_DEEP = 1u << 8,
+    CAT_NO_NEE = 1u << 9, CAT_BACKFACE_OPAQUE = 1u << 10, CAT_NORMAL_MAP = 1u << 11, CAT_CARPAINT = 1u << 12, CAT_MTRL_NEG = 1u << 13,
+    CAT_STENCIL_ALWAYS = 1u << 14,
+    CAT_NEE_POINT = 1u << 15, CAT_NEE_SPOT = 1u << 16, CAT_NEE_DIRECTION = 1u << 17, CAT_NEE_AREA = 1u << 18, CAT_NEE_IBL = 1u << 19,
+    CAT_NEE_ONE_LIGHT = 1u << 20, CAT_NEE_MANY_LIGHTS = 1u << 21, CAT_NEE_INVALID = 1u << 22,
+    CAT_RR_SURVIVED = 1u << 23, CAT_RR_LOST = 1u << 24, CAT_RR_ZERO = 1u << 25,
+    CAT_BSDF_REJECTED = 1u << 26, CAT_LAST_VERTEX = 1u << 27
+};
+
+static void path_from_vertex(PathState& path, Ray& ray, const atn_shade_vertex& v, const uint32_t* seeds, uint32_t n_seeds,
+    uint32_t frame, int32_t sample, int32_t width)
+{
+    path.throughput = ld3(v.throughput); path.pdfb = v.pdfb; path.contrib = ld3(v.contrib);
+    path.is_terminated = (v.flags & kFlagTerminated) != 0; path.is_singular = (v.flags & kFlagSingular) != 0;
+    path.screen_space_x = v.pixel % width; path.screen_space_y = v.pixel / width;
+    // GeneratePath's sampler (pathtracing_impl.h:75-81) at the record's dimension
+    const uint32_t rnd = seeds[(uint32_t)v.pixel % n_seeds];
+    const uint32_t fs = frame + (uint32_t)sample;
+    path.sampler.init(fs % (CMJ::CMJ_DIM * CMJ::CMJ_DIM), v.dimension, rnd * 0x1fe3434f * ((fs + 133 * rnd) / (CMJ::CMJ_DIM * CMJ::CMJ_DIM)));
+    ray.org = ld3(v.org); ray.dir = ld3(v.dir);      // (as stored: no constructor, nothing re-normalised)
+}
+
+// PathTracing::shade / ShadeMiss once per record (pathtracing.cpp:91-236, pathtracing_impl.h:112-176), called as PathTracing::radiance
+// calls them, and what the NEXT stages can observe afterwards (atn_shade_result).  Nothing of the formulas is restated: the hit record
+// is completed from the triangle as the traversal fills it, the state goes in, shade runs, the state comes out.  What the reference
+// computes but nobody reads is NOT reported and left zero: the shadow ray of a path that ended in this vertex (HitShadowRay returns
+// before it looks at it), the next ray, pdf, throughput and sampler position of a path that does not go on.
+// cat_out [n] (optional): the branch taken, CAT_* bits.  margins_out [2 n] (optional): per record {the smallest distance from its
+// threshold, in ulps, of a decision that rests on a libm result; the same of the decisions that do not} (orc_pt.h, DecisionLog).
+// Returns 0, or -1 for a null pointer, a bad call, a pixel outside the frame, a record that is already terminated, or a hit record
+// that names no object / triangle of the scene.
+int orc_shade_stage(const atn_scene_desc* scene, const atn_camera_param* camera, const uint32_t* seeds, uint32_t n_seeds,
+    const atn_shade_call* call, const atn_shade_vertex* in, uint32_t n, atn_shade_result* out, uint32_t* cat_out, float* margins_out)
+{
+    if (!scene || !camera || !seeds || !n_seeds || !call) return -1;
+    if (call->width <= 0 || call->height <= 0 || call->max_depth <= 0 || call->bounce < 0 || call->bounce >= call->max_depth) return -1;
+    if ((call->flavour != 0 && call->flavour != 1) || call->chunk_items < 0 || call->chunk_items > 4) return -1;
+    const bool svgf_flavour = call->flavour == 1;
+    if (n == 0) return 0;
+    if (!in || !out) return -1;
+    Scene ctxt(scene);
+    for (uint32_t i = 0; i < n; i++) {
+        if (in[i].pixel < 0 || (int64_t)in[i].pixel >= (int64_t)call->width * call->height || (in[i].flags & kFlagTerminated)) return -1;
+        if (in[i].flags & ~(kFlagTerminated | kFlagSingular | kFlagHit | kFlagLastSpecular)) return -1;
+        // (the same refusals as atn_shade_stage's: ids inside the scene, barycentrics finite and within [-1, 2])
+        if (in[i].objid >= 0 && ((uint32_t)in[i].objid >= scene->n_objects || in[i].tri_id < 0 || (uint32_t)in[i].tri_id >= scene->n_triangles
+                                 || !(in[i].a >= -1.0F && in[i].a <= 2.0F && in[i].b >= -1.0F && in[i].b <= 2.0F))) return -1;
+    }
+    if (sampling_options().ibl_importance && ctxt.cfg().bg.envmap_tex_idx >= 0 && ctxt.cfg().bg.enable_env_map)
+        IBL_preCompute(sampling_options(), ctxt);
+    int32_t rrDepth = call->rr_depth;
+    if (rrDepth > call->max_depth) rrDepth = call->max_depth - 1;      // pathtracing.cpp:282-284
+    const int32_t bounce = call->bounce;
+    // flavour "svgf": SVGFRenderer::Shade / ShadeMiss with AOV spans (svgf.cpp:89-229) under the frame's W2C.  The path's
+    // last_hit_mtrl_idx is carried as one flag bit -- "the last hit's material is Specular", all Shade asks of it -- so a set bit
+    // stands for the scene's first Specular material (refused where the scene has none).
+    svgf::Matrices mtxs;
+    mtxs.Reset(*camera);
+    const m4 W2C = mtxs.GetW2C();
+    int32_t specular_idx = -1;
+    for (uint32_t k = 0; k < scene->n_materials && specular_idx < 0; k++) if (scene->materials[k].type == ATN_MTRL_SPECULAR) specular_idx = (int32_t)k;
+    if (svgf_flavour && specular_idx < 0)
+        for (uint32_t i = 0; i < n; i++) if (in[i].flags & kFlagLastSpecular) return -1;
+    const uint32_t kUnwritten = 0x7fa5a5a5u;        // every component of an AOV texel nobody wrote (a NaN pattern, compared as bits)
+#pragma omp parallel for
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        const atn_shade_vertex& v = in[i];
+        PathState path; Ray ray; ShadowRay shadow_ray;
+        path_from_vertex(path, ray, v, seeds, n_seeds, call->frame, call->sample, call->width);
+        shadow_ray.targetLightId = 0xffffffffu;
+        v4 aov[3];
+        for (v4& t : aov) { float f; std::memcpy(&f, &kUnwritten, 4); t = v4(f, f, f, f); }
+        if (svgf_flavour) path.last_hit_mtrl_idx = (v.flags & kFlagLastSpecular) ? specular_idx : -1;
+        DecisionLog log;
+        decision_log() = &log;
+        const bool is_hit = v.objid >= 0;
+        uint32_t cat = 0;
+        uint32_t lbits = 0;
+        path.isHit = false;
+        if (is_hit) {
+            Isect isect;
+            const auto& prim = ctxt.GetTriangle((uint32_t)v.tri_id);
+            isect.objid = v.objid; isect.tri_id = v.tri_id; isect.a = v.a; isect.b = v.b;
+            isect.mtrlid = (int32_t)prim.mtrlid; isect.meshid = (int32_t)prim.mesh_id;
+            path.isHit = true;
+            const Ray ray_in = ray;
+            if (svgf_flavour) svgf::Shade(path, ctxt, ray, shadow_ray, isect, rrDepth, bounce, W2C, aov[0], aov[1], aov[2], nullptr);
+            else shade(path, ctxt, ray, shadow_ray, isect, rrDepth, bounce, nullptr);
+            const bool stencil_always = isect.mtrlid >= 0 && ctxt.GetMaterial(isect.mtrlid).stencil_type == 1;     // pathtracing.cpp:59-66
+            lbits = shadow_ray.targetLightId | (stencil_always ? 0x40000000u : 0u);
+            // ---- the branch taken, from the material and the log (labels only: no output depends on them)
+            atn_material_param m;
+            FillMaterial(m, ctxt, isect.mtrlid);
+            HitRec rec;
+            evaluate_hit_result(rec, ctxt.GetObject((uint32_t)v.objid), ctxt, ray_in, isect);
+            const bool back = dot(rec.normal, -ray_in.dir) < 0.0F;
+            const bool toon = m.type == ATN_MTRL_TOON || m.type == ATN_MTRL_STYLIZED_BRDF;
+            if (isect.mtrlid < 0) cat |= CAT_MTRL_NEG;
+            if (stencil_always) cat |= CAT_STENCIL_ALWAYS;
+            if (m.type == ATN_MTRL_EMISSIVE) {
+                if (back) cat |= CAT_EMIT_BACK;
+                else cat |= bounce == 0 ? CAT_EMIT_FRONT_B0 : CAT_EMIT_FRONT_DEEP;
+                if (ctxt.GetObject((uint32_t)v.objid).light_id < 0) cat |= CAT_EMIT_NO_LIGHT;
+            }
+            if (toon) cat |= bounce == 0 ? CAT_TOON_FIRST : CAT_TOON_DEEP;
+            const bool reached_nee = log.roulette != 0 || log.nee != 0 || log.bsdf_rejected != 0 || shadow_ray.targetLightId != 0xffffffffu
+                                     || path.sampler.m_dimension != v.dimension || !path.is_terminated;
+            if (reached_nee) {
+                if (!toon && (attr_singular(m) || attr_translucent(m))) cat |= CAT_NO_NEE;
+                if (!attr_translucent(m) && back) cat |= CAT_BACKFACE_OPAQUE;
+                if (m.normalMap >= 0) cat |= CAT_NORMAL_MAP;
+                if (m.type == ATN_MTRL_CARPAINT) cat |= CAT_CARPAINT;
+                if (log.nee) {
+                    const int32_t lt = ctxt.GetLight(shadow_ray.targetLightId).type;
+                    cat |= lt == ATN_LIGHT_POINT ? CAT_NEE_POINT : lt == ATN_LIGHT_SPOT ? CAT_NEE_SPOT : lt == ATN_LIGHT_DIRECTION ? CAT_NEE_DIRECTION
+                         : lt == ATN_LIGHT_AREA ? CAT_NEE_AREA : CAT_NEE_IBL;
+                    cat |= ctxt.GetLightNum() == 1 ? CAT_NEE_ONE_LIGHT : CAT_NEE_MANY_LIGHTS;
+                    if (log.nee == 2) cat |= CAT_NEE_INVALID;
+                }
+                if (log.roulette == 1) cat |= CAT_RR_SURVIVED;
+                if (log.roulette == 2) cat |= CAT_RR_LOST;
+                if (log.roulette == 3) cat |= CAT_RR_ZERO;
+                if (log.bsdf_rejected) cat |= CAT_BSDF_REJECTED;
+                if (!path.is_terminated && bounce + 1 == call->max_depth) cat |= CAT_LAST_VERTEX;
+            }
+        }
+        else {
+            if (svgf_flavour) svgf::ShadeMissAov(path.screen_space_x, path.screen_space_y, call->width, call->height, bounce, ctxt, *camera, path, ray, aov[0], aov[1], aov[2]);
+            else ShadeMiss(path.screen_space_x, path.screen_space_y, call->width, call->height, bounce, ctxt, *camera, path, ray);
+            cat |= bounce == 0 ? CAT_MISS_B0 : (bounce == 1 && (v.flags & kFlagSingular)) ? CAT_MISS_B1_SINGULAR : CAT_MISS_DEEP;
+        }
+        decision_log() = nullptr;
+
+        atn_shade_result& o = out[i];
+        std::memset(&o, 0, sizeof(o));
+        o.flags = (v.flags & ~(kFlagTerminated | kFlagSingular | kFlagHit)) | (path.is_terminated ? kFlagTerminated : 0u)
+                | (path.is_singular ? kFlagSingular : 0u) | (path.isHit ? kFlagHit : 0u);
+        if (svgf_flavour) {
+            const int32_t last = path.last_hit_mtrl_idx;        // (PrepareForNextBounce stores mtrl.id where the path goes on, pathtracing_impl.h:739)
+            const bool spec = last >= 0 && (uint32_t)last < scene->n_materials && scene->materials[last].type == ATN_MTRL_SPECULAR;
+            o.flags = (o.flags & ~kFlagLastSpecular) | (spec ? kFlagLastSpecular : 0u);
+            float* dst[3] = { o.aov_nd, o.aov_am, o.aov_primary };
+            for (int k = 0; k < 3; k++) {
+                const float c[4] = { aov[k].x, aov[k].y, aov[k].z, aov[k].w };
+                uint32_t b[4]; std::memcpy(b, c, 16);
+                if (b[0] != kUnwritten || b[1] != kUnwritten || b[2] != kUnwritten || b[3] != kUnwritten) { o.aov_written |= 1u << k; std::memcpy(dst[k], c, 16); }
+            }
+        }
+        o.contrib[0] = path.contrib.x; o.contrib[1] = path.contrib.y; o.contrib[2] = path.contrib.z;
+        o.goes_on = (is_hit && !path.is_terminated && bounce + 1 < call->max_depth) ? 1u : 0u;      // radiance's `willContinue` and its loop bound
+        o.has_shadow = (is_hit && !path.is_terminated && shadow_ray.isActive) ? 1u : 0u;            // HitShadowRay's two early returns
+        if (o.goes_on) {
+            o.dimension = path.sampler.m_dimension; o.pdfb = path.pdfb;
+            o.org[0] = ray.org.x; o.org[1] = ray.org.y; o.org[2] = ray.org.z;
+            o.dir[0] = ray.dir.x; o.dir[1] = ray.dir.y; o.dir[2] = ray.dir.z;
+            o.throughput[0] = path.throughput.x; o.throughput[1] = path.throughput.y; o.throughput[2] = path.throughput.z;
+        }
+        if (o.has_shadow) {
+            o.light_bits = lbits; o.sh_c_w = lbits; o.sh_dist = shadow_ray.distToLight;
+            o.sh_o[0] = shadow_ray.rayorg.x; o.sh_o[1] = shadow_ray.rayorg.y; o.sh_o[2] = shadow_ray.rayorg.z;
+            o.sh_d[0] = shadow_ray.raydir.x; o.sh_d[1] = shadow_ray.raydir.y; o.sh_d[2] = shadow_ray.raydir.z;
+            o.sh_c[0] = shadow_ray.lightcontrib.x; o.sh_c[1] = shadow_ray.lightcontrib.y; o.sh_c[2] = shadow_ray.lightcontrib.z;
+        }
+        if (cat_out) cat_out[i] = cat;
+        if (margins_out) { margins_out[2 * i] = log.min_libm_ulps; margins_out[2 * i + 1] = log.min_exact_ulps; }
+    }
+    return 0;
+}
+
+// PathTracing::radiance (pathtracing.cpp:22-89) over one sample of a frame, as orc_render runs it, with an observer: one record per
+// (pixel, bounce) in the order visited (pixels in raster order, a pixel's bounces ascending) -- what shade / ShadeMiss START from at
+// every depth.  bounce_out [capacity]: the record's depth.  film (optional): the sample's Path.contrib per pixel, xyz + 1.
+// Returns the number of records (at most width * height * maxDepth), or -1 when `capacity` is too small.
+int64_t orc_record_vertices(const atn_scene_desc* scene, const atn_camera_param* camera, const uint32_t* seeds, uint32_t n_seeds,
+    const orc_destination* dst, int32_t sample, atn_shade_vertex* out, int32_t* bounce_out, uint64_t capacity, atn_vec4* contrib_out)
+{
+    struct Recorder : VertexObserver {
+        std::vector<atn_shade_vertex>* v; std::vector<int32_t>* b; int32_t pixel;
+        void vertex(int32_t depth, const PathState& path, const Ray& ray, const Isect& isect, bool is_hit) override
+        {
+            atn_shade_vertex r{};
+            r.org[0] = ray.org.x; r.org[1] = ray.org.y; r.org[2] = ray.org.z; r.pdfb = path.pdfb;
+            r.dir[0] = ray.dir.x; r.dir[1] = ray.dir.y; r.dir[2] = ray.dir.z;
+            r.flags = (path.is_terminated ? kFlagTerminated : 0u) | (path.is_singular ? kFlagSingular : 0u);
+            r.throughput[0] = path.throughput.x; r.throughput[1] = path.throughput.y; r.throughput[2] = path.throughput.z;
+            r.dimension = path.sampler.m_dimension;
+            r.contrib[0] = path.contrib.x; r.contrib[1] = path.contrib.y; r.contrib[2] = path.contrib.z;
+            r.objid = is_hit ? isect.objid : -1; r.a = is_hit ? isect.a : 0.0F; r.b = is_hit ? isect.b : 0.0F; r.tri_id = is_hit ? isect.tri_id : -1;
+            r.pixel = pixel;
+            v->push_back(r); b->push_back(depth);
+        }
+    };
+    Scene ctxt(scene);
+    if (sampling_options().ibl_importance && ctxt.cfg().bg.envmap_tex_idx >= 0 && ctxt.cfg().bg.enable_env_map)
+        IBL_preCompute(sampling_options(), ctxt);
+    const int32_t width = dst->width, height = dst->height;
+    int32_t maxDepth = dst->maxDepth, rrDepth = dst->russianRouletteDepth;
+    if (rrDepth > maxDepth) rrDepth = maxDepth - 1;
+    std::vector<std::vector<atn_shade_vertex>> rows(height);
+    std::vector<std::vector<int32_t>> row_b(height);
+#pragma omp parallel for
+    for (int32_t y = 0; y < height; y++) {
+        Recorder rec; rec.v = &rows[y]; rec.b = &row_b[y];
+        for (int32_t x = 0; x < width; x++) {
+            const int32_t idx = y * width + x;
+            PathState path; path.samples = 0;
+            Ray ray; ShadowRay shadow_ray;
+            GeneratePath(ray, x, y, sample, dst->frame, path, *camera, seeds[idx % n_seeds]);
+            path.contrib = v3(0);
+            rec.pixel = idx;
+            radiance(path, ray, shadow_ray, x, y, width, height, ctxt, *camera, maxDepth, rrDepth, nullptr, &rec);
+            if (contrib_out) { contrib_out[idx].x = path.contrib.x; contrib_out[idx].y = path.contrib.y; contrib_out[idx].z = path.contrib.z; contrib_out[idx].w = 1.0F; }
+        }
+    }
+    uint64_t total = 0;
+    for (int32_t y = 0; y < height; y++) total += rows[y].size();
+    if (total > capacity) return -1;
+    uint64_t k = 0;
+    for (int32_t y = 0; y < height; y++)
+        for (size_t i = 0; i < rows[y].size(); i++, k++) { out[k] = rows[y][i]; bounce_out[k] = row_b[y][i]; }
+    return (int64_t)total;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // SVGF (next tier): aten::SVGFRenderer, src/libaten/renderer/svgf/svgf.cpp:412-637
 // ---------------------------------------------------------------------------------------------------
 void* orc_svgf_create() { return new svgf::Params(); }

@@ -143,6 +143,48 @@ def shadow_visible(scene, queries, details=False):
     return (vis, lookups, last) if details else vis
 
 
+SHADE_CATEGORIES = [
+    "miss_b0", "miss_deep", "miss_b1_singular", "emit_front_b0", "emit_front_deep", "emit_back", "emit_no_light", "toon_first", "toon_deep",
+    "no_nee", "backface_opaque", "normal_map", "carpaint", "mtrl_neg", "stencil_always",
+    "nee_point", "nee_spot", "nee_direction", "nee_area", "nee_ibl", "nee_one_light", "nee_many_lights", "nee_invalid",
+    "rr_survived", "rr_lost", "rr_zero", "bsdf_rejected", "last_vertex",
+]       # bit k of orc_shade_stage's category word
+
+
+def shade_stage(scene, cam, seeds, records, width, height, bounce, max_depth, rr_depth, frame=0, sample=0, flavour="plain", details=False):
+    """PathTracing::shade / ShadeMiss once per record (aten_amd.layout.SHADE_VERTEX) -> SHADE_RESULT [n]: what the next stages can observe.
+    details=True also returns the category word [n] (bits: SHADE_CATEGORIES) and the margins float32 [n, 2]: the smallest distance of a
+    branch decision from its threshold in ulps, {decisions behind a libm result, the others}."""
+    from aten_amd import layout as L
+    rec = np.ascontiguousarray(records, L.SHADE_VERTEX)
+    call = L.shade_call(width, height, bounce, max_depth, rr_depth, frame, sample, flavour)
+    out = np.zeros(len(rec), L.SHADE_RESULT); cat = np.zeros(len(rec), np.uint32); mg = np.zeros((len(rec), 2), np.float32)
+    seeds = np.ascontiguousarray(seeds, np.uint32)
+    rc = lib().orc_shade_stage(scene.ref(), C.c_void_p(cam.ctypes.data), C.c_void_p(seeds.ctypes.data), C.c_uint32(len(seeds)),
+                               C.c_void_p(call.ctypes.data), C.c_void_p(rec.ctypes.data), C.c_uint32(len(rec)), C.c_void_p(out.ctypes.data),
+                               C.c_void_p(cat.ctypes.data), C.c_void_p(mg.ctypes.data))
+    if rc != 0:
+        raise ValueError("orc_shade_stage: bad call or record")
+    return (out, cat, mg) if details else out
+
+
+def record_vertices(scene, cam, seeds, width, height, max_depth=5, rr_depth=3, frame=0, sample=0):
+    """PathTracing::radiance over one sample of a frame with an observer: (records SHADE_VERTEX [m], bounce int32 [m], contrib [h, w, 4])
+    -- one record per (pixel, bounce) in the order visited, the sample's Path.contrib per pixel."""
+    from aten_amd import layout as L
+    cap = width * height * max_depth
+    rec = np.zeros(cap, L.SHADE_VERTEX); b = np.zeros(cap, np.int32); contrib = np.zeros((height, width, 4), np.float32)
+    seeds = np.ascontiguousarray(seeds, np.uint32)
+    d = Destination(width, height, max_depth, rr_depth, 1, frame, 1, 0)
+    l = lib()
+    l.orc_record_vertices.restype = C.c_int64
+    m = l.orc_record_vertices(scene.ref(), C.c_void_p(cam.ctypes.data), C.c_void_p(seeds.ctypes.data), C.c_uint32(len(seeds)), C.byref(d),
+                              C.c_int32(sample), C.c_void_p(rec.ctypes.data), C.c_void_p(b.ctypes.data), C.c_uint64(cap), C.c_void_p(contrib.ctypes.data))
+    if m < 0:
+        raise ValueError("orc_record_vertices failed")
+    return rec[:m].copy(), b[:m].copy(), contrib
+
+
 def evaluate_hits(scene, rays, isects):
     out = np.zeros((len(rays), 9), np.float32)
     lib().orc_evaluate_hits(scene.ref(), C.c_void_p(rays.ctypes.data), C.c_void_p(isects.ctypes.data),

@@ -8,6 +8,39 @@
 
 namespace orc {
 
+// Not in the reference: how the branches of one shaded vertex were decided, for orc_shade_stage.  While a log is installed (one per
+// thread) the float comparisons that pick a branch report how far their left side sat from the threshold, in ulps of `scale` -- the
+// magnitude of the terms the left side was summed from (1 for a dot product of unit vectors or a probability; the value itself for
+// a product, which rounding cannot carry across zero).  `libm`: the left side depends on a sin / cos / acos / pow / exp result, where
+// the two builds' math libraries may differ in the last bits; the others rest on + - * / sqrt, min / max and CMJ draws, which are exact.
+struct DecisionLog {
+    float min_libm_ulps{ INF }, min_exact_ulps{ INF };
+    int32_t roulette{ 0 };          // 0 not run, 1 survived, 2 lost, 3 zero (or NaN) throughput: no draw
+    int32_t bsdf_rejected{ 0 };     // PrepareForNextBounce refused the sample (pdf <= 0 or c <= 0)
+    int32_t nee{ 0 };               // 0 not attempted, 1 a valid sample, 2 an invalid one
+};
+inline DecisionLog*& decision_log() { static thread_local DecisionLog* p = nullptr; return p; }
+inline void note_decision(float lhs, float threshold, float scale, bool libm)
+{
+    DecisionLog* l = decision_log();
+    if (!l) return;
+    float s = std::fmax(std::fabs(scale), std::fabs(threshold));
+    if (!(s >= std::numeric_limits<float>::min())) s = std::numeric_limits<float>::min();
+    const float ulp = std::nextafter(s, INF) - s;
+    const float d = std::fabs(lhs - threshold) / ulp;      // (NaN: never the minimum)
+    float& m = libm ? l->min_libm_ulps : l->min_exact_ulps;
+    if (d < m) m = d;
+}
+
+// ... with one exception: a positive value below 1e-30 is a product with an exp / pow result at the edge of underflow in it, where one
+// math library returns a denormal and the other zero.  Such a `> 0` test counts as a libm decision on its threshold; an exact 0 (a
+// constant, a cosine clamped away) does not.
+inline void note_positive(float lhs)
+{
+    DecisionLog* l = decision_log();
+    if (l && lhs != 0.0F && std::fabs(lhs) < 1.0e-30F) l->min_libm_ulps = 0.0F;
+}
+
 struct MaterialSampling {   // material/material.h:338-347
     v3 dir; v3 bsdf; float pdf{ 0 };
 };
@@ -434,6 +467,7 @@ inline void sample(MaterialSampling& result, CMJ* sampler, const atn_material_pa
     }
     const float prob = 0.25F + 0.5F * R;
     const float u = sampler->nextSample();
+    note_decision(u, prob, 1.0F, false);        // (Schlick's fresnel: products only)
     if (u < prob) {
         wo = ComputeReflectVector(wi, N);
         const float c = std::abs(dot(wo, N));
@@ -703,6 +737,7 @@ inline void sample(MaterialSampling& result, const atn_material_param& param, co
     float p = 0.0F;
     v3 wo;      // the reference reads it unset in the diffuse branch below (retroreflective.cpp:559-565): (0, 0, 0) here
     float used_E = 0.0F, used_F = 0.0F;
+    note_decision(r3, cdf0, 1.0F, true); note_decision(r3, cdf1, 1.0F, true);
     if (r3 < cdf0) {
         wo = ComputeReflectVector(wi, Beckman::SampleMicrosurfaceNormal(roughness, n, r1, r2));
         f_r = Beckman::ComputeBRDF(roughness, ior, n, wi, wo);
@@ -884,6 +919,7 @@ inline v3 sampleDirection(const atn_material_param& m, const v3& normal, const v
     float fresnel = computeFresnel(float(1), p.clearcoat_ior, V, N);
     float flakes_density = computeFlakeDensity(p.flake_size, float(1));
     v3 dir;
+    note_decision(r0, fresnel, 1.0F, true);
     if (r0 < fresnel) {
         r0 /= fresnel;
         dir = ComputeReflectVector(wi, Beckman::SampleMicrosurfaceNormal(p.clearcoat_roughness, N, r0, r1));
@@ -933,6 +969,7 @@ inline float applyNormalMap(const atn_material_param& m, const v3& orgNml, v3& n
     const v3 N = normalize(orgNml);
     float r0 = sampler->nextSample();
     float fresnel = computeFresnel(float(1), p.clearcoat_ior, V, N);
+    note_decision(r0, fresnel, 1.0F, true);
     if (r0 < fresnel) {
         newNml = N;
     }
@@ -1077,6 +1114,7 @@ inline void sample(MaterialSampling& result, const Scene& ctxt, const atn_materi
     const float R = F, T = 1 - R;
     const float prob = R;
     const float u = sampler->nextSample();
+    note_decision(u, prob, 1.0F, true);     // (the microsurface normal comes from sin / cos)
     if (u < prob) {
         const v3 wo = ComputeReflectVector(wi, m);
         const float VN = dot(V, N), LN = dot(wo, N);
@@ -1502,6 +1540,7 @@ inline void Light_sample(LightSampleResult& result, const atn_light_param& param
         float rho = dot(ldir, dir_to_light);
         float cosHalfInner = std::cos(param.innerAngle * 0.5F);
         float cosHalfOuter = std::cos(param.outerAngle * 0.5F);
+        note_decision(rho, cosHalfOuter, 1.0F, true);
         if (rho > cosHalfOuter) {
             float att = (rho - cosHalfOuter) / (cosHalfInner - cosHalfOuter);
             att = clamp_(att, 0.0f, 1.0f);
@@ -1589,6 +1628,11 @@ inline bool ComputeRadianceNEE(v3& out, const Scene& ctxt, const v3& wi, const v
     const bool is_singular = (ls.attrib & ATN_LIGHT_ATTR_SINGULAR) != 0;
     dist2 = (isInfinite || is_singular) ? 1.0F : dist2;
 
+    // (the two cosines are sums of products of unit vectors that come from sin / cos / acos on most paths: libm decisions at scale 1.
+    // The distance and the two pdfs are products or constants: a last-bit difference cannot carry them across zero, they need no margin)
+    note_decision(cosShadow, 0.0F, 1.0F, true); note_decision(cosLight, 0.0F, 1.0F, true);
+    note_decision(dist2, 0.0F, dist2, false); note_decision(path_pdf, 0.0F, path_pdf, false); note_decision(ls.pdf, 0.0F, ls.pdf, false);
+    note_positive(path_pdf); note_positive(ls.pdf);
     if (cosShadow >= 0 && cosLight >= 0 && dist2 > 0 && path_pdf > 0.0F && ls.pdf > 0.0F) {
         if (!isInfinite) path_pdf = path_pdf * cosLight / dist2;
         float misW = is_singular ? 1.0f : (ls.pdf * light_select_prob) / ((ls.pdf * light_select_prob) + path_pdf);
@@ -1625,7 +1669,9 @@ inline void FillShadowRay(ShadowRay& shadow_ray, const Scene& ctxt, PathState& p
     shadow_ray.lightcontrib = v3(0);
 
     v3 radiance;
+    if (DecisionLog* l = decision_log()) l->nee = 2;
     if (ComputeRadianceNEE(radiance, ctxt, ray.dir, hit_nml, mtrl, hit_u, hit_v, lightSelectPdf, sampleres, pre_sampled_r)) {
+        if (DecisionLog* l = decision_log()) l->nee = 1;
         // vec3 * vec3 * vec4 (component-wise; .w dropped on store)
         shadow_ray.lightcontrib = path.throughput * radiance * external_albedo.xyz();
         shadow_ray.isActive = true;
@@ -1854,7 +1900,10 @@ inline float ComputeRussianProbability(int32_t bounce, int32_t rr_bounce, PathSt
             russian_prob = max_from_vec3(path.throughput);
             float p = path.sampler.nextSample();
             path.is_terminated = (p >= russian_prob);
+            note_decision(p, russian_prob, 1.0F, false);
+            if (DecisionLog* l = decision_log()) l->roulette = path.is_terminated ? 2 : 1;
         }
+        else if (DecisionLog* l = decision_log()) l->roulette = 3;
     }
     return russian_prob;
 }
@@ -1869,6 +1918,8 @@ inline void PrepareForNextBounce(const HitRec& rec, float russian_prob, const v3
     const v3 bsdf = sampling.bsdf;
     v3 ray_along_normal = dot(normal, next_dir) >= 0.0f ? normal : -normal;
     float c = dot(ray_along_normal, next_dir);
+    note_decision(dot(normal, next_dir), 0.0F, 1.0F, true); note_decision(c, 0.0F, 1.0F, true); note_decision(pdfb, 0.0F, pdfb, false); note_positive(pdfb);
+    if (DecisionLog* l = decision_log()) l->bsdf_rejected = (pdfb > 0 && c > 0) ? 0 : 1;
     if (pdfb > 0 && c > 0) {
         path.throughput *= albedo * bsdf * c / pdfb;
         path.throughput /= russian_prob;
@@ -1983,10 +2034,15 @@ inline void ShadeMiss(int32_t ix, int32_t iy, int32_t width, int32_t height, int
     }
 }
 
-// PathTracing::radiance, pathtracing.cpp:22-89
+// PathTracing::radiance, pathtracing.cpp:22-89.  `observer` (optional, not in the reference) sees what every vertex starts from:
+// the state, the ray and the hit record in front of shade / ShadeMiss (orc_record_vertices).
+struct VertexObserver {
+    virtual void vertex(int32_t depth, const PathState& path, const Ray& ray, const Isect& isect, bool is_hit) = 0;
+    virtual ~VertexObserver() = default;
+};
 inline void radiance(PathState& path, Ray& ray, ShadowRay& shadow_ray, int32_t ix, int32_t iy,
     int32_t width, int32_t height, const Scene& ctxt, const atn_camera_param& camera,
-    int32_t maxDepth, int32_t rrDepth, PathCounters* cnt)
+    int32_t maxDepth, int32_t rrDepth, PathCounters* cnt, VertexObserver* observer = nullptr)
 {
     int32_t depth = 0;
     while (depth < maxDepth) {
@@ -1995,6 +2051,7 @@ inline void radiance(PathState& path, Ray& ray, ShadowRay& shadow_ray, int32_t i
         path.isHit = false;
         if (cnt) cnt->closest_rays++;
         bool is_hit = TraverseClosest(isect, ctxt, ray, EPS, INF, cnt ? &cnt->trav : nullptr);
+        if (observer) observer->vertex(depth, path, ray, isect, is_hit);
         if (is_hit) {
             path.isHit = true;
             shade(path, ctxt, ray, shadow_ray, isect, rrDepth, depth, cnt);

@@ -36,7 +36,7 @@ def kernels(lib):
                 name = m.group(1)
                 body[name] = []
                 continue
-            if name is None or not line.strip():
+            if name is None or not line.strip() or line.strip() == "...":      # ("...": objdump's mark for the zero padding behind a kernel)
                 continue
             t = line.split("//")[0].strip()
             t = re.sub(r"<[^>]+>", "<L>", t)                       # branch targets, symbol references

@@ -421,7 +421,11 @@ __global__ void __launch_bounds__(256) k_vol_shade(PathBuffers pb, DevScene sc, 
                         const VolMedium md = va.med[st.bottom];
                         const float sigma_t = md.sigma_a + md.sigma_s;
                         const float r1 = cmj_next(smp);
-                        const float s = -logf(smax(1.0F - r1, 0.0F)) / sigma_t;
+                        // the logarithm in double, rounded once (as the host library's logf evaluates it): at most 1 ulp from the twin's,
+                        // so s stays within 2 ulp behind the division by ANY sigma_t.  With logf (<= 1 ulp, but on the other side of
+                        // the true value at times) the two logarithms lay up to 2 ulp apart, and a sigma_t that is no power of two
+                        // turned that into 3 ulp of s (docs/VOLUME.md, "Parity")
+                        const float s = -(float)log((double)smax(1.0F - r1, 0.0F)) / sigma_t;
                         s_dist = s;
                         sflags |= kVolSampled;
                         if (s >= hit_t) ray_org = ray_org + ray_dir * hit_t;

@@ -36,6 +36,7 @@ SYMBOLS = [
     "atn_mgpu_update_geometry", "atn_mgpu_lbvh_rebuild_list",
     "atn_skin_create", "atn_skin_update", "atn_skin_compute", "atn_lbvh_rebuild_list_skinned", "atn_skin_download",
     "atn_skin_download_list", "atn_skin_destroy",
+    "atn_tlas_rebuild", "atn_tlas_download", "atn_mgpu_tlas_rebuild",
     "atn_set_geometry_motion", "atn_geometry_motion_stats", "atn_geometry_motion_matrices",
     "atn_taa_resolve", "atn_taa_upload", "atn_taa_download", "atn_taa_reset", "atn_taa_output_device", "atn_taa_rgba8_device",
     "atn_mgpu_create", "atn_mgpu_destroy", "atn_mgpu_last_error", "atn_mgpu_shard_count", "atn_mgpu_shard_device",
@@ -94,6 +95,9 @@ def lib():
         l.atn_skin_download.argtypes = [vp, C.c_uint32, C.c_int32, vp]
         l.atn_skin_download_list.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         l.atn_skin_destroy.argtypes = [vp, C.c_uint32]
+        l.atn_tlas_rebuild.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
+        l.atn_mgpu_tlas_rebuild.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]
+        l.atn_tlas_download.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
         l.atn_set_geometry_motion.argtypes = [vp, C.c_int32]
         l.atn_geometry_motion_stats.argtypes = [vp, vp]
         l.atn_geometry_motion_matrices.argtypes = [vp, vp, vp]

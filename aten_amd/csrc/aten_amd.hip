@@ -29,6 +29,7 @@
 #include "device/volume.hpp"
 #include "device/lbvh.hpp"
 #include "device/skinning.hpp"
+#include "device/tlas.hpp"
 #include "device/motion.hpp"
 #include "device/taa.hpp"
 #include "host/scene_upload.hpp"
@@ -312,6 +313,7 @@ public:
     std::vector<HostSceneImage::TlasRef> tlas_refs;     // the top layer's TLAS-leaf records and the lists they enter
     uint32_t top_base = 0, n_host_matrices = 0;
     std::vector<atn_mat4> host_matrices;    // the caller's matrices as last uploaded
+    std::vector<atn_object_param> host_objects;     // ... and the objects (atn_tlas_rebuild without objects reads their mtx_id)
     std::vector<uint32_t> list_base, list_bytes, list_tri_leaves, list_inner;   // region of every list in the node image
     uint32_t n_scene_tris = 0, n_scene_vtx = 0, n_scene_mtrls = 0;
     // What atn_update_materials / _lights / _texture / _rendering_config edit (docs/SCENE_EDITS.md): the caller's editable data as
@@ -957,6 +959,8 @@ public:
         n_bottom_nodes = img.n_nodes - s->bvh_lists[0].count;
         n_host_matrices = s->n_matrices;
         host_matrices.assign(s->matrices, s->matrices + s->n_matrices);     // (update_tlas without matrices still recognises identity instances)
+        host_objects.assign(s->objects, s->objects + s->n_objects);
+        tl.table_current = false;
         tree_is_deep = img.n_nodes >= kRefillMinNodes;
         return ATN_OK;
     }
@@ -1172,6 +1176,27 @@ public:
         return has_scene ? apply_sampling_options() : ATN_OK;
     }
 
+    // A top layer of `need` float4s of node image, n_objs objects and mtx_quads matrix rows: buffers that must grow are replaced
+    // behind a full stop (rare: the usual tick keeps every count); the bottom-level lists are kept, the old top layer is dropped.
+    int grow_for_top_layer(size_t need, size_t n_objs, size_t mtx_quads)
+    {
+        if (!(need > nodes.n || n_objs > objects.n || mtx_quads > matrices.n)) return ATN_OK;
+        { int q = quiesce(); if (q) return q; }
+        drop_alt_set();         // re-cloned from the grown buffers at the next flip
+        if (need > nodes.n) {
+            float4* bigger = nullptr;
+            ATN_HIP(hipMalloc((void**)&bigger, need * sizeof(float4)));
+            hipError_t e = hipMemcpyAsync(bigger, nodes.p, (size_t)top_base, hipMemcpyDeviceToDevice, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) { (void)hipFree(bigger); return fail(ATN_ERR_HIP, hipGetErrorString(e)); }
+            nodes.release();
+            nodes.p = bigger; nodes.n = need;
+        }
+        if (n_objs > objects.n) ATN_HIP(objects.resize(n_objs));
+        if (mtx_quads > matrices.n) ATN_HIP(matrices.resize(mtx_quads));
+        return ATN_OK;
+    }
+
     // ≙ idaten::Renderer::updateBVH, src/libidaten/kernel/renderer.cpp:133-153: new object parameters and matrices
     // plus a rebuilt top layer; the bottom-level lists stay where they are in HBM.
     int updateBVH(const atn_object_param* objs, uint32_t n_objs, const atn_mat4* mtxs, uint32_t n_mtxs,
@@ -1217,25 +1242,9 @@ public:
         }
         const size_t need = ((size_t)top_base + top_bytes + 15) / 16;
         const size_t obj_bytes = (size_t)n_objs * sizeof(atn_object_param), mtx_bytes = mv.size() * sizeof(float4);
-        // Buffers that must grow are replaced behind a full stop (rare: the usual tick keeps every count); otherwise the
-        // update is enqueued behind the frames in flight and the host goes on.
-        const bool grow = need > nodes.n || n_objs > objects.n || mv.size() > matrices.n;
-        if (grow) {
-            { int q = quiesce(); if (q) return q; }
-            drop_alt_set();         // re-cloned from the grown buffers at the next flip
-            if (need > nodes.n) {
-                // keep the bottom-level lists (device-to-device), drop the old top layer
-                float4* bigger = nullptr;
-                ATN_HIP(hipMalloc((void**)&bigger, need * sizeof(float4)));
-                hipError_t e = hipMemcpyAsync(bigger, nodes.p, (size_t)top_base, hipMemcpyDeviceToDevice, stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(stream);
-                if (e != hipSuccess) { (void)hipFree(bigger); return fail(ATN_ERR_HIP, hipGetErrorString(e)); }
-                nodes.release();
-                nodes.p = bigger; nodes.n = need;
-            }
-            if (n_objs > objects.n) ATN_HIP(objects.resize(n_objs));
-            if (mv.size() > matrices.n) ATN_HIP(matrices.resize(mv.size()));
-        }
+        // Buffers that must grow are replaced behind a full stop; otherwise the update is enqueued behind the frames in flight
+        // and the host goes on.
+        { int r = grow_for_top_layer(need, n_objs, mv.size()); if (r) return r; }
         { int r = begin_scene_update(top_bytes + obj_bytes + mtx_bytes + 512); if (r) return r; }
         { int r = stage_copy(reinterpret_cast<char*>(nodes.p) + top_base, rec.data(), top_bytes); if (r) return r; log_range(SB_NODES, top_base, top_bytes); }
         { int r = stage_copy(objects.p, objs, obj_bytes); if (r) return r; log_range(SB_OBJECTS, 0, obj_bytes); }
@@ -1246,6 +1255,8 @@ public:
         // if every planar light's records came back byte for byte
         if (scene.planar_lights && !planar_certs_survive_objects(objs, n_objs, mtxs, n_mtxs)) scene.planar_lights = 0;
         tlas_refs.swap(new_refs);
+        if (objs != host_objects.data()) host_objects.assign(objs, objs + n_objs);
+        tl.table_current = false;       // (atn_tlas_rebuild's leaf table follows the host-given top layer)
         scene.root_link = root;
         fill_root_direct(scene, rec.data(), top_base, n_mtxs ? mtxs : (host_matrices.size() == n_host_matrices ? host_matrices.data() : nullptr), n_mtxs ? n_mtxs : n_host_matrices);
         scene.node_bytes = (uint32_t)(top_base + top_bytes);
@@ -1429,6 +1440,150 @@ public:
         // the root is node 0 = an inner record at the start of the region: the TLAS leaves' root link (and twin word) stay valid
         { int r = end_scene_update(); if (r) return r; }
         if (sync) ATN_HIP(hipStreamSynchronize(upd));
+        return ATN_OK;
+    }
+
+    // ---------------------------------------------------------------------------------------------------------------
+    // The top layer rebuilt on the device (device/tlas.hpp, docs/TLAS.md): an LBVH over the instances' world boxes, enqueued behind
+    // the frames in flight like updateBVH -- no host tree, no host wait, nothing read back.  The leaves are the KIND_TLAS leaves of
+    // the last host-given top layer (tlas_refs, in that layer's walk order: the order that breaks ties between equal Morton codes).
+    struct TlasScratch {
+        DevBuf<TlasLeaf> table;
+        DevBuf<TlasBox> wbox, partial, ubox, nbox;      // the general path's
+        bool table_current = false;                     // `table` holds tlas_refs as they are (upload and updateBVH replace them)
+    } tl;
+
+    int tlas_rebuild(const atn_object_param* objs, uint32_t n_objs, const atn_mat4* mtxs, uint32_t n_mtxs, uint32_t flags)
+    {
+        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+        if ((objs == nullptr) != (n_objs == 0)) return fail(ATN_ERR_INVALID_ARG, "object array and count do not match");
+        if (n_mtxs && !mtxs) return fail(ATN_ERR_INVALID_ARG, "null matrix array");
+        ATN_HIP(hipSetDevice(device));
+        const atn_object_param* O = objs ? objs : host_objects.data();
+        const uint32_t n_o = objs ? n_objs : (uint32_t)host_objects.size();
+        const uint32_t n_m = n_mtxs ? n_mtxs : n_host_matrices;
+        const atn_mat4* M = n_mtxs ? mtxs : (host_matrices.size() == n_host_matrices ? host_matrices.data() : nullptr);
+        // every index a kernel uses is checked here first
+        {
+            std::string rerr;
+            if (!validate_ranges(O, n_o, n_m, nullptr, rerr)) return fail(ATN_ERR_UNSUPPORTED, rerr);
+            for (uint32_t i = 0; i < n_o; i++)
+                if (O[i].light_id >= scene.n_lights) return fail(ATN_ERR_UNSUPPORTED, "object light id out of range");
+        }
+        const size_t n_leaves = tlas_refs.size();
+        if (n_leaves == 0) return fail(ATN_ERR_UNSUPPORTED, "the top layer has no instance leaf to rebuild it over");
+        if (n_leaves > kLbvhMaxTris) return fail(ATN_ERR_UNSUPPORTED, "too many instances: node indices are stored as floats");
+        const uint32_t n = (uint32_t)n_leaves;
+        for (const HostSceneImage::TlasRef& t : tlas_refs) {
+            if (t.objid < 0 || (uint32_t)t.objid >= n_o) return fail(ATN_ERR_UNSUPPORTED, "TLAS leaf object id out of range");
+            if (t.list == 0 || t.list >= list_root_link.size() || list_root_link[t.list] == kLinkEnd) return fail(ATN_ERR_UNSUPPORTED, "TLAS leaf references a missing BLAS list");
+        }
+        const size_t top_bytes = (size_t)(2 * (uint64_t)n - 1) * kInnerBytes;
+        if ((uint64_t)top_base + top_bytes >= (1ull << 31)) return fail(ATN_ERR_UNSUPPORTED, "too many BVH nodes for 31-bit byte-offset links");
+        if (n == 1) {
+            // fill_root_direct needs the record itself: one instance is written from the host, as updateBVH does it
+            const HostSceneImage::TlasRef t = tlas_refs[0];
+            atn_bvh_node top{};
+            top.hit = -1.0F; top.miss = -1.0F; top.f0 = (float)t.objid; top.f1 = -1.0F; top.f3 = (float)t.meshid;
+            { const uint32_t exid = t.list; std::memcpy(&top.f2, &exid, 4); }      // (the exid bit-field: mainExid = the list)
+            const std::vector<atn_object_param> keep(O, O + n_o);
+            return updateBVH(keep.data(), n_o, mtxs, n_mtxs, &top, 1);
+        }
+        std::vector<float4> mv;
+        if (n_mtxs) {
+            mv.resize((size_t)n_mtxs * 4);
+            for (uint32_t i = 0; i < n_mtxs; i++)
+                for (int r = 0; r < 4; r++)
+                    mv[4 * (size_t)i + r] = make_float4(mtxs[i].m[r][0], mtxs[i].m[r][1], mtxs[i].m[r][2], mtxs[i].m[r][3]);
+        }
+        const size_t need = ((size_t)top_base + top_bytes + 15) / 16;
+        const size_t obj_bytes = (size_t)n_objs * sizeof(atn_object_param), mtx_bytes = mv.size() * sizeof(float4);
+        { int r = grow_for_top_layer(need, n_objs, mv.size()); if (r) return r; }
+        const TlasLaunch l = tlas_launch(n, kTlasBlockMax, (flags & 1u) != 0);
+        // Scratch.  The sort's and the hierarchy's buffers are the list rebuilds' (lb): a list rebuild of this tick is enqueued on
+        // the same update stream in front of this call, and stream order is all that keeps the two apart -- nothing here may move
+        // to another stream without a dependency on it.
+        if (tl.table.n < n) { ATN_HIP(tl.table.resize(n)); tl.table_current = false; }
+        if (!l.block_path) {
+            { int r = lbvh_reserve(n); if (r) return r; }
+            if (tl.wbox.n < n) ATN_HIP(tl.wbox.resize(n));
+            if (tl.partial.n < l.leaf_grid) ATN_HIP(tl.partial.resize(l.leaf_grid));
+            if (tl.ubox.n < 1) ATN_HIP(tl.ubox.resize(1));
+            if (tl.nbox.n < 2 * (size_t)n - 1) ATN_HIP(tl.nbox.resize(2 * (size_t)n - 1));
+        }
+        const size_t table_bytes = tl.table_current ? 0 : (size_t)n * sizeof(TlasLeaf);
+        { int r = begin_scene_update(table_bytes + obj_bytes + mtx_bytes + 512); if (r) return r; }
+        if (!tl.table_current) {
+            std::vector<TlasLeaf> tab(n);
+            for (uint32_t k = 0; k < n; k++) {
+                const HostSceneImage::TlasRef& t = tlas_refs[k];
+                tab[k] = TlasLeaf{ t.objid, list_root_link[t.list], t.list < list_twin_delta.size() ? list_twin_delta[t.list] : 0, t.meshid };
+            }
+            { int r = stage_copy(tl.table.p, tab.data(), table_bytes); if (r) return r; }
+            tl.table_current = true;
+        }
+        if (objs) { int r = stage_copy(objects.p, objs, obj_bytes); if (r) return r; log_range(SB_OBJECTS, 0, obj_bytes); }
+        if (n_mtxs) { int r = stage_copy(matrices.p, mv.data(), mtx_bytes); if (r) return r; log_range(SB_MATRICES, 0, mtx_bytes); }
+        TlasArgs a{};
+        a.table = tl.table.p; a.n = n; a.top_base = top_base; a.image = nodes.p;
+        a.objects = objects.p; a.matrices = matrices.p; a.tris = tris.p; a.vtx_pos = vtx_pos.p;
+        a.recognise_identity = M ? 1 : 0;
+        if (l.block_path) tlas_launch_block(l, upd, a);
+        else {
+            a.wbox = tl.wbox.p; a.partial = tl.partial.p; a.ubox = tl.ubox.p; a.nbox = tl.nbox.p; a.n_partial = l.leaf_grid;
+            a.codes = lb.codes[0].p; a.indices = lb.indices[0].p; a.arrived = lb.arrived.p;
+            a.topo = LbvhTopo{ lb.left.p, lb.right.p, lb.parent.p, lb.first.p, lb.last.p };
+            tlas_launch_codes(l, upd, a);
+            const uint32_t rounds = radix_rounds(n), tile = kSortThreads * rounds, nb = (n + tile - 1) / tile;
+            for (uint32_t pass = 0; pass < 4; pass++) {     // (four passes: the sorted keys end in codes[0] / indices[0])
+                const int in = pass & 1, out = in ^ 1;
+                hipLaunchKernelGGL(k_radix_count, dim3(nb), dim3(kSortThreads), 0, upd, (const uint32_t*)lb.codes[in].p, n, pass * 8u, lb.counts.p, nb, rounds);
+                hipLaunchKernelGGL(k_radix_scan, dim3(256), dim3(64), 0, upd, lb.counts.p, nb, lb.totals.p);
+                hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(kSortThreads), 0, upd, (const uint32_t*)lb.codes[in].p, (const uint32_t*)lb.indices[in].p,
+                                   lb.codes[out].p, lb.indices[out].p, n, pass * 8u, (const uint32_t*)lb.counts.p, nb, (const uint32_t*)lb.totals.p, rounds);
+            }
+            hipLaunchKernelGGL(k_lbvh_hierarchy, dim3(l.leaf_grid), dim3(256), 0, upd, (const uint32_t*)lb.codes[0].p, n, a.topo, lb.arrived.p);
+            tlas_launch_emit(l, upd, a);
+        }
+        ATN_HIP(hipGetLastError());
+        log_range(SB_NODES, top_base, top_bytes);
+        { int r = end_scene_update(); if (r) return r; }
+        // the host state updateBVH leaves behind
+        if (n_mtxs) { n_host_matrices = n_mtxs; host_matrices.assign(mtxs, mtxs + n_mtxs); }
+        if (objs) host_objects.assign(objs, objs + n_objs);
+        const int32_t root = (int32_t)top_base;     // inner node 0 lies first
+        list_root_link[0] = root;
+        if (scene.planar_lights && !planar_certs_survive_objects(host_objects.data(), (uint32_t)host_objects.size(), mtxs, n_mtxs)) scene.planar_lights = 0;
+        int32_t ident_row = -1;
+        for (uint32_t k = 0; k < n; k++) {
+            tlas_refs[k].offset = top_base + kInnerBytes * (n - 1 + k);
+            const int32_t mtx_id = host_objects[tlas_refs[k].objid].mtx_id;
+            if (ident_row < 0 && mtx_id >= 0 && M && is_exact_identity(host_matrices[(size_t)mtx_id + 1])) ident_row = 4 * (mtx_id + 1);
+        }
+        scene.root_link = root;
+        fill_root_direct(scene, nullptr, 0);        // (an inner root: no direct entry)
+        scene.node_bytes = (uint32_t)(top_base + top_bytes);
+        scene.ident_row = ident_row;
+        if (n_mtxs) scene.mtx_quads = (uint32_t)mv.size();
+        point_scene_at_current_set();
+        tree_is_deep = n_bottom_nodes + (2 * (uint64_t)n - 1) >= kRefillMinNodes;
+        return ATN_OK;
+    }
+
+    // Probe: the top layer's records as they are in device memory (waits for everything)
+    int tlas_download(void* out, uint32_t cap_bytes, uint32_t* out_records, int32_t* out_root_link, uint32_t* out_top_base)
+    {
+        if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        const uint32_t bytes = scene.node_bytes - top_base;
+        if (out_records) *out_records = bytes / kInnerBytes;
+        if (out_root_link) *out_root_link = scene.root_link;
+        if (out_top_base) *out_top_base = top_base;
+        if (!out) return ATN_OK;
+        if (cap_bytes < bytes) return fail(ATN_ERR_INVALID_ARG, "atn_tlas_download: the buffer is smaller than the top layer");
+        ATN_HIP(hipMemcpyAsync(out, reinterpret_cast<const char*>(nodes.p) + top_base, bytes, hipMemcpyDeviceToHost, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
         return ATN_OK;
     }
 
@@ -3862,6 +4017,16 @@ int atn_lbvh_rebuild_list_skinned(atn_ctx* ctx, uint32_t list_index, atn_skin sk
     CTX_OR_FAIL(ctx);
     return guarded(ctx, [&] { return ctx->r.lbvh_rebuild_list_skinned(list_index, skin); });
 }
+int atn_tlas_rebuild(atn_ctx* ctx, const atn_object_param* objects, uint32_t n_objects, const atn_mat4* matrices, uint32_t n_matrices, uint32_t flags)
+{
+    CTX_OR_FAIL(ctx);      // enqueued behind the frames in flight, like atn_update_tlas
+    return guarded(ctx, [&] { return ctx->r.tlas_rebuild(objects, n_objects, matrices, n_matrices, flags); });
+}
+int atn_tlas_download(atn_ctx* ctx, void* out, uint32_t cap_bytes, uint32_t* out_records, int32_t* out_root_link, uint32_t* out_top_base)
+{
+    CTX_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.tlas_download(out, cap_bytes, out_records, out_root_link, out_top_base); });
+}
 int atn_skin_download(atn_ctx* ctx, atn_skin skin, int32_t which, void* out_host)
 {
     CTX_OR_FAIL(ctx);
@@ -4356,6 +4521,14 @@ int atn_mgpu_lbvh_rebuild_list(atn_mgpu* mg, uint32_t list_index, uint32_t tri_o
         PathTracing& r = *mg->m.shard[i];
         if (hipSetDevice(r.device) != hipSuccess) return r.fail(ATN_ERR_HIP, "hipSetDevice");
         return r.lbvh_rebuild_list(list_index, tri_offset, n_triangles, bbox_min, bbox_max, false); }); });
+}
+int atn_mgpu_tlas_rebuild(atn_mgpu* mg, const atn_object_param* objects, uint32_t n_objects, const atn_mat4* matrices, uint32_t n_matrices, uint32_t flags)
+{
+    MG_OR_FAIL(mg);
+    return mg_guarded(mg, [&] { return mg->m.on_all([&](int i) {
+        PathTracing& r = *mg->m.shard[i];
+        if (hipSetDevice(r.device) != hipSuccess) return r.fail(ATN_ERR_HIP, "hipSetDevice");
+        return r.tlas_rebuild(objects, n_objects, matrices, n_matrices, flags); }); });
 }
 int atn_mgpu_update_materials(atn_mgpu* mg, const atn_material_param* materials, uint32_t n, uint32_t first)
 {

@@ -221,6 +221,31 @@ void skin_launch_triangles(const SkinLaunch& l, hipStream_t st, const SkinTriArg
 void skin_launch_morton(hipStream_t st, const atn_triangle_param* tris, const float4* vtx, int32_t vtx_offset, uint32_t n, const float* box,
                         uint32_t* codes, uint32_t* indices);
 
+// ---- tlas.hip (device/tlas.hpp) ----
+struct TlasArgs;
+// a top-layer rebuild over n >= 2 instances: the block path (one launch of one workgroup, a power of two >= n threads) up to
+// `block_max` instances unless the general path is forced; the general path's grids are blocks of 256 over the leaves / the nodes
+struct TlasLaunch {
+    bool block_path;
+    uint32_t block;             // threads of the block path's workgroup
+    uint32_t leaf_grid, node_grid;
+};
+inline TlasLaunch tlas_launch(uint32_t n, uint32_t block_max, bool force_general)
+{
+    TlasLaunch l{};
+    l.block_path = n <= block_max && !force_general;
+    l.block = 64u;
+    while (l.block < n && l.block < block_max) l.block <<= 1;
+    l.leaf_grid = (n + 255u) / 256u;
+    l.node_grid = (2u * n - 1u + 255u) / 256u;
+    return l;
+}
+void tlas_launch_block(const TlasLaunch& l, hipStream_t st, const TlasArgs& a);
+// the general path in front of the sort (leaf boxes, union box, codes) ...
+void tlas_launch_codes(const TlasLaunch& l, hipStream_t st, const TlasArgs& a);
+// ... and behind k_lbvh_hierarchy (boxes, links and records)
+void tlas_launch_emit(const TlasLaunch& l, hipStream_t st, const TlasArgs& a);
+
 // ---- motion.hip (device/motion.hpp) ----
 struct MotionArgs;
 // the primary hit records of slots [fp.slot_begin, fp.slot_end) -> the ids plane; `grid` blocks of 256 over those slots

@@ -67,7 +67,18 @@ __device__ __forceinline__ void lbvh_triangle_box(const atn_triangle_param* tris
     mx = mk3(fmaxf(fmaxf(v0.x, v1.x), v2.x), fmaxf(fmaxf(v0.y, v1.y), v2.y), fmaxf(fmaxf(v0.z, v1.z), v2.z));
 }
 
-#ifndef ATN_LBVH_HELPERS_ONLY     // (skinning.hip takes the helpers above for its Morton pass; the kernels belong to aten_amd.hip)
+__device__ __forceinline__ int32_t lbvh_clz(uint32_t x) { return x ? __builtin_clz(x) : 32; }
+
+// computeLongestCommonPrefix, LBVHBuilder.cu:194-216: equal codes fall back to the positions
+__device__ __forceinline__ int32_t lbvh_lcp(const uint32_t* __restrict__ keys, int32_t n, int32_t i1, int32_t i2)
+{
+    const int32_t l = min(i1, i2), r = max(i1, i2);
+    if (l < 0 || r >= n) return -1;
+    const uint32_t a = keys[l], b = keys[r];
+    return a != b ? lbvh_clz(a ^ b) : 32 + lbvh_clz((uint32_t)(l ^ r));
+}
+
+#ifndef ATN_LBVH_HELPERS_ONLY     // (skinning.hip and tlas.hip take the helpers above; the kernels belong to aten_amd.hip)
 __global__ __launch_bounds__(256) void k_lbvh_morton(const atn_triangle_param* __restrict__ tris, const float4* __restrict__ vtx,
                                                      int32_t vtx_offset, uint32_t n, f3 bmin, f3 bmax,
                                                      uint32_t* __restrict__ codes, uint32_t* __restrict__ indices)
@@ -175,17 +186,6 @@ __global__ __launch_bounds__(kSortThreads) void k_radix_scatter(const uint32_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int32_t lbvh_clz(uint32_t x) { return x ? __builtin_clz(x) : 32; }
-
-// computeLongestCommonPrefix, LBVHBuilder.cu:194-216: equal codes fall back to the positions
-__device__ __forceinline__ int32_t lbvh_lcp(const uint32_t* __restrict__ keys, int32_t n, int32_t i1, int32_t i2)
-{
-    const int32_t l = min(i1, i2), r = max(i1, i2);
-    if (l < 0 || r >= n) return -1;
-    const uint32_t a = keys[l], b = keys[r];
-    return a != b ? lbvh_clz(a ^ b) : 32 + lbvh_clz((uint32_t)(l ^ r));
-}
-
 __global__ __launch_bounds__(256) void k_lbvh_hierarchy(const uint32_t* __restrict__ keys, uint32_t n, LbvhTopo t, uint32_t* __restrict__ arrived)
 {
     const int32_t idx = blockIdx.x * blockDim.x + threadIdx.x, num = (int32_t)n;

@@ -37,7 +37,7 @@ struct HostSceneImage {
     std::vector<int32_t> list_root_link; // typed link of each list's root
     std::vector<uint32_t> list_bytes;   // bytes of each list's contiguous region starting at list_root
     std::vector<int32_t> list_twin_delta; // byte distance from a bottom-level list's root record to the root of its any-hit twin (anyhit_twin.hpp), 0 = none
-    struct TlasRef { uint32_t offset, list; };
+    struct TlasRef { uint32_t offset, list; int32_t objid, meshid; };     // (objid, meshid: what atn_tlas_rebuild needs to write the leaf again)
     std::vector<TlasRef> tlas_refs;     // every TLAS-leaf record (byte offset) and the list it enters: where a twin is switched off later (LBVH rebuild)
     std::vector<uint32_t> list_tri_leaves, list_inner;  // record counts of each list
     std::vector<atn_triangle_param> tris;
@@ -245,7 +245,7 @@ inline bool emit_list(char* img, const ListLayout& L, const atn_bvh_node* src, c
             if (w2l_row >= 0 && c.matrices && is_exact_identity(c.matrices[obj.mtx_id + 1])) { flags |= kTlasIdentity; if (c.ident_row < 0) c.ident_row = w2l_row; }
             q[0] = make_float4(i2f(objid), i2f(w2l_row), i2f(c.list_root_link[exid]), i2f(flags));
             q[1] = make_float4(i2f((int32_t)nd.f3), i2f(h), i2f(m), i2f(c.list_twin_delta ? c.list_twin_delta[exid] : 0));
-            if (c.tlas_refs) c.tlas_refs->push_back({ L.offset[j], (uint32_t)exid });
+            if (c.tlas_refs) c.tlas_refs->push_back({ L.offset[j], (uint32_t)exid, objid, (int32_t)nd.f3 });
             counts[2]++;
             break;
         }

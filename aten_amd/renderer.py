@@ -153,6 +153,26 @@ class PathTracing:
         """lbvh_rebuild_list over the skin's triangles, normalised by the skin's box as it lies in device memory."""
         self._check(self._l.atn_lbvh_rebuild_list_skinned(self._ctx, list_index, skin))
 
+    # ---- the top layer rebuilt on the device (docs/TLAS.md)
+    def tlas_rebuild(self, objects=None, matrices=None, force_general=False):
+        """atn_tlas_rebuild: the top layer as an LBVH over the instances' world boxes, built on the device behind the frames in
+        flight.  objects (layout.OBJECT_PARAM) / matrices (float32 [n, 4, 4]): as updateBVH's; None keeps the uploaded ones."""
+        objs = None if objects is None else np.ascontiguousarray(objects, L.OBJECT_PARAM)
+        mtx = None if matrices is None else np.ascontiguousarray(matrices, np.float32).reshape(-1, 4, 4)
+        self._check(self._l.atn_tlas_rebuild(self._ctx, objs.ctypes.data if objs is not None else None, len(objs) if objs is not None else 0,
+                                             mtx.ctypes.data if mtx is not None and len(mtx) else None, len(mtx) if mtx is not None else 0,
+                                             1 if force_general else 0))
+
+    def tlas_records(self):
+        """For tests (waits for everything): the top layer's device records, the root first, as (records, root_link, top_base) --
+        records is uint32 [n, 8]: an inner record is {boxmin, hit}{boxmax, miss}, a TLAS leaf {objid, w2l_row, BLAS root link, flags}
+        {meshid, hit, miss, twin}; links are typed byte offsets into the node image (device/scene_dev.hpp)."""
+        n, root, base = C.c_uint32(0), C.c_int32(0), C.c_uint32(0)
+        self._check(self._l.atn_tlas_download(self._ctx, None, 0, C.byref(n), C.byref(root), C.byref(base)))
+        out = np.zeros((max(n.value, 1), 8), np.uint32)
+        self._check(self._l.atn_tlas_download(self._ctx, out.ctypes.data, out.nbytes, C.byref(n), C.byref(root), C.byref(base)))
+        return out[:n.value], int(root.value), int(base.value)
+
     def skin_buffer(self, skin, name):
         """For tests: "pos", "nml", "prev" (float32 [n, 4]), "bbox" (float32 [6]) or "area" (float32 [n_triangles])."""
         which = {"pos": 0, "nml": 1, "prev": 2, "bbox": 3, "area": 4}[name]
@@ -962,6 +982,14 @@ class MultiGpuPathTracing:
         """idaten::LBVHBuilder::build into the renderer's node list (LBVHBuilder.cu:700-810), on the device."""
         f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
         self._check(self._l.atn_mgpu_lbvh_rebuild_list(self._mg, list_index, tri_offset, n_triangles, f3(bbox_min), f3(bbox_max)))
+
+    def tlas_rebuild(self, objects=None, matrices=None, force_general=False):
+        """PathTracing.tlas_rebuild on every shard."""
+        objs = None if objects is None else np.ascontiguousarray(objects, L.OBJECT_PARAM)
+        mtx = None if matrices is None else np.ascontiguousarray(matrices, np.float32).reshape(-1, 4, 4)
+        self._check(self._l.atn_mgpu_tlas_rebuild(self._mg, objs.ctypes.data if objs is not None else None, len(objs) if objs is not None else 0,
+                                                  mtx.ctypes.data if mtx is not None and len(mtx) else None, len(mtx) if mtx is not None else 0,
+                                                  1 if force_general else 0))
 
     def updateCamera(self, cam):
         self._check(self._l.atn_mgpu_update_camera(self._mg, cam.ctypes.data))

@@ -162,6 +162,23 @@ int atn_skin_compute(atn_ctx* ctx, atn_skin skin, int32_t is_restart, float bbox
 /* atn_lbvh_rebuild_list over the skin's triangles with the Morton codes normalised by the skin's box AS IT IS IN DEVICE MEMORY (after
  * atn_skin_compute): no read-back.  Same tree, same refusals. */
 int atn_lbvh_rebuild_list_skinned(atn_ctx* ctx, uint32_t list_index, atn_skin skin);
+/* Rebuild the TOP layer on the device as an LBVH over the instances' world boxes (docs/TLAS.md), enqueued behind the frames in flight
+ * like atn_update_tlas: no host tree, no host wait, nothing read back.  An instance's local box is the root record of its list as it
+ * is in device memory at that point of the update stream -- after atn_lbvh_rebuild_list[_skinned] the new LBVH's root, so a skinned
+ * tick needs neither a box read-back nor a conservative box.
+ * objects / matrices: as atn_update_tlas; NULL objects (n_objects == 0) keeps the uploaded ones, n_matrices == 0 keeps the old matrices.
+ * flags bit 0: force the general (multi-launch) path; both paths write the same bytes.
+ * The set of leaves is the last host-given top layer's (atn_upload_scene, atn_update_tlas): objid, the list it enters, meshid.  Leaves
+ * with neither triangles nor a nested tree (sphere instances, never tested by the walk) are dropped from a rebuilt layer.  Binding an
+ * instance to another list, or another number of instances, still needs atn_update_tlas.
+ * ATN_ERR_NO_SCENE before an upload; ATN_ERR_INVALID_ARG for a null array with a count (or a count without an array);
+ * ATN_ERR_UNSUPPORTED for ids out of range, more than 2^23 instances, and a top layer without an instance leaf.  A refused call
+ * changes nothing.  Additive entry points: atn_abi_version stays 3. */
+int atn_tlas_rebuild(atn_ctx* ctx, const atn_object_param* objects, uint32_t n_objects,
+                     const atn_mat4* matrices, uint32_t n_matrices, uint32_t flags);
+/* Probe: the top-layer records of the current scene set as they are in device memory (32-byte records, the root first; DESIGN.md
+ * "data layout in HBM").  Waits for everything.  out may be NULL (the counts only); cap_bytes is the size of `out`. */
+int atn_tlas_download(atn_ctx* ctx, void* out, uint32_t cap_bytes, uint32_t* out_records, int32_t* out_root_link, uint32_t* out_top_base);
 /* For tests; waits for everything.  which = 0 positions, 1 normals, 2 previous positions (atn_vec4[n_vertices]), 3 the box
  * (float[6]: min, max), 4 the triangles' areas (float[n_triangles]); and of the WHOLE scene as new frames read it: 5 the shading
  * records (8 atn_vec4 per triangle), 6 positions, 7 normals (atn_vec4 per vertex), 8 triangles (atn_triangle_param). */
@@ -370,6 +387,9 @@ int atn_mgpu_upload_scene(atn_mgpu* mg, const atn_scene_desc* scene);
 int atn_mgpu_update_tlas(atn_mgpu* mg, const atn_object_param* objects, uint32_t n_objects,
                          const atn_mat4* matrices, uint32_t n_matrices,
                          const atn_bvh_node* top_nodes, uint32_t n_top_nodes);
+/* atn_tlas_rebuild on every shard */
+int atn_mgpu_tlas_rebuild(atn_mgpu* mg, const atn_object_param* objects, uint32_t n_objects,
+                          const atn_mat4* matrices, uint32_t n_matrices, uint32_t flags);
 int atn_mgpu_update_geometry(atn_mgpu* mg, const atn_vec4* vtx_pos, const atn_vec4* vtx_nml, uint32_t n_vertices, uint32_t vtx_offset,
                              const atn_triangle_param* triangles, uint32_t n_triangles, uint32_t tri_offset);
 int atn_mgpu_lbvh_rebuild_list(atn_mgpu* mg, uint32_t list_index, uint32_t tri_offset, uint32_t n_triangles,

@@ -23,6 +23,7 @@
 #include "device/svgf_gather.hpp"
 #include "device/restir.hpp"
 #include "device/npr.hpp"
+#include "device/npr_advance.hpp"
 #include "device/ao.hpp"
 #include "device/npr_shadow.hpp"
 #include "device/npr_hatching.hpp"
@@ -3145,6 +3146,33 @@ public:
     int32_t np_w = 0, np_h = 0, np_capture = 0, np_depth = 0;
     bool np_captured = false;
     FrameFence np_fence;        // the last NPR frame's kernels are done with the sample-ray state (the next frame waits for it)
+    // the look-through (atn_npr_set_skip_through(1), device/npr_advance.hpp; docs/NPR_ADVANCE.md): the alpha-blend plane, the check's
+    // working ray and record per slot, the queue without the paths whose look-through missed; shared by the banks like the state above
+    int32_t np_skip = 0;
+    DevBuf<float4> np_ab, np_adv_o, np_adv_d, np_st_adv;
+    DevBuf<uint32_t> np_ab_acc, np_adv_info, np_adv_queue, np_adv_counters;
+    uint32_t np_adv_slots = 0;
+    int32_t np_adv_depth = 0;
+    bool np_adv_captured = false;
+    // does an NPR frame of the uploaded scene look through surfaces?  (a STENCIL material, or alpha blending with an alpha that may be < 1)
+    bool npr_advances() const { return np_skip == 1 && (np_stencil || np_alpha); }
+    int npr_set_skip_through(int32_t mode)
+    {
+        if (mode != 0 && mode != 1) return fail(ATN_ERR_INVALID_ARG, "NPR skip-through: mode is 0 (such scenes are refused) or 1 (AdvanceNPRPath)");
+        np_skip = mode;
+        return ATN_OK;
+    }
+    int npr_adv_ensure(int32_t w, int32_t h, int32_t max_depth)
+    {
+        if (n_slots != np_adv_slots) {
+            ATN_HIP(np_ab.resize(n_slots)); ATN_HIP(np_adv_o.resize(n_slots)); ATN_HIP(np_adv_d.resize(n_slots));
+            ATN_HIP(np_ab_acc.resize(n_slots)); ATN_HIP(np_adv_info.resize(n_slots)); ATN_HIP(np_adv_queue.resize(n_slots));
+            np_adv_slots = n_slots;
+        }
+        if (max_depth > np_adv_depth) { ATN_HIP(np_adv_counters.resize((size_t)kAdvCounters * max_depth)); np_adv_depth = max_depth; }
+        if (np_capture) ATN_HIP(np_st_adv.resize(2 * (size_t)w * h));
+        return ATN_OK;
+    }
 
     // (of src, the editable scene data as last uploaded or edited; `mats` = the device form of src.materials)
     int npr_decode(const std::vector<DevMaterial>& mats)
@@ -3211,13 +3239,19 @@ public:
         int rc = check_ready(d);
         if (rc) return rc;
         if (!np_cfg.enabled) return fail(ATN_ERR_UNSUPPORTED, "feature lines are off in the scene's config (FeatureLineConfig.enabled == 0): render with atn_render");
-        if (np_stencil) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not skip through StencilType::STENCIL materials (AdvanceNPRPath)");
-        if (np_alpha) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not skip through translucent-by-alpha surfaces: alpha blending is on and a material's alpha may be < 1 (AdvanceNPRPath)");
+        if (np_stencil && np_skip != 1) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not skip through StencilType::STENCIL materials (AdvanceNPRPath)");
+        if (np_alpha && np_skip != 1) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not skip through translucent-by-alpha surfaces: alpha blending is on and a material's alpha may be < 1 (AdvanceNPRPath)");
         if (np_carpaint) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not draw AdvanceNPRPath's extra CarPaint dimension: CarPaint materials are refused");
         if (world != 1) return fail(ATN_ERR_UNSUPPORTED, "NPR frames need the whole frame on one GPU (atn_set_screen_shard world 1)");
         if (regen_mode != 0) return fail(ATN_ERR_UNSUPPORTED, "NPR frames run the serial sample loop: switch path regeneration off (atn_set_regeneration(0))");
         if (shade_math_relaxed) return fail(ATN_ERR_UNSUPPORTED, "NPR frames have no relaxed-math kernels: atn_set_shade_math(0)");
         if (d->count_stats) return fail(ATN_ERR_UNSUPPORTED, "NPR frames do not count rays (count_stats must be 0)");
+        // the pre-pass has a primary pass of its own, which would need the same look-through
+        const bool adv = npr_advances();
+        if (adv && ns_mode == 1 && (nh_base != 1 || nh_dir != kHatchHorizontal))
+            return fail(ATN_ERR_UNSUPPORTED, "NPR skip-through: the hatching pre-pass does not look through STENCIL or alpha surfaces: atn_npr_hatching_set(1, 1, ...) and atn_npr_shadow_set_mode(0), or atn_npr_set_skip_through(0)");
+        if (adv && ns_mode == 1)
+            return fail(ATN_ERR_UNSUPPORTED, "NPR skip-through: the shadow pre-pass does not look through STENCIL or alpha surfaces: atn_npr_shadow_set_mode(0), or atn_npr_set_skip_through(0)");
         rc = nh_check(d);
         if (rc) return rc;
         ATN_HIP(hipSetDevice(device));
@@ -3225,6 +3259,7 @@ public:
         if (rc) return rc;
         rc = npr_ensure(d->width, d->height, d->maxDepth);
         if (rc) return rc;
+        if (adv) { rc = npr_adv_ensure(d->width, d->height, d->maxDepth); if (rc) return rc; }
         // atn_npr_shadow_set_mode(1): the same pre-pass as with lines off (docs/NPR_SHADOW.md)
         if (ns_frame()) { rc = ns_prepass(d); if (rc) return rc; }
         const bool prof = d->profile != 0;
@@ -3240,6 +3275,16 @@ public:
         if (np_capture) { na.st_line = np_st_line.p; na.st_desc = np_st_desc.p; na.st_disc = np_st_disc.p; na.st_dims = np_st_dims.p; }
         // the walk of the sample rays: the frame's walk, LDS copy and block, 8 rays per path
         const RayLaunch nl = ray_launch(plan, n_slots, kNprRays * n_slots, trace_grid(kNprRays * n_slots, true));
+        // the look-through's walk: one job per path
+        NprAdvArgs aa{};
+        RayLaunch al{};
+        if (adv) {
+            aa.queue_in = np_queue.p; aa.counters_in = np_counters.p; aa.queue_out = np_adv_queue.p; aa.counters = np_adv_counters.p;
+            aa.ab = np_ab.p; aa.ab_acc = np_ab_acc.p; aa.ray_o = np_adv_o.p; aa.ray_d = np_adv_d.p; aa.info = np_adv_info.p;
+            aa.st_adv = np_capture ? np_st_adv.p : nullptr;
+            aa.max_depth = d->maxDepth;
+            al = ray_launch(plan, n_slots, n_slots, trace_grid(n_slots, true));
+        }
 
         const uint32_t g_slots = grid_for(n_slots), g_all = (n_slots + 255u) / 256u;
         // the previous NPR frame (another bank's stream) still reads and writes the sample-ray state
@@ -3253,6 +3298,10 @@ public:
             prof_begin(prof, ATN_K_GEN);
             hipLaunchKernelGGL(k_gen_path, dim3(g_slots), dim3(256), 0, stream, pb, fp, camera, (const uint32_t*)seeds.p);
             npr_launch_gen(g_slots, stream, pb, fp, na);
+            if (adv) {
+                ATN_HIP(hipMemsetAsync(np_adv_counters.p, 0, (size_t)kAdvCounters * d->maxDepth * sizeof(uint32_t), stream));
+                npr_adv_launch_init(g_all, stream, fp, aa);
+            }
             prof_end(prof);
             for (int32_t b = 0; b <= d->maxDepth; b++) {
                 const TraceLaunch tl = trace_launch(plan, b);
@@ -3264,9 +3313,24 @@ public:
                 npr_launch_bounce(nl, stream, pb, scene, fp, camera, na, b);
                 PathBuffers pbs = pb;
                 pbs.queue[b & 1] = np_queue.p;
-                prof_begin(prof, ATN_K_SHADE);
-                launch_shade<false>(plan, stream, pbs, fp, b, SvgfShade{});
-                prof_end(prof);
+                if (adv) {
+                    // AdvanceNPRPath: the paths that look through a surface get their new hit and ray; those that end in a miss leave
+                    // this bounce's shade queue for the next bounce's trace queue
+                    prof_begin(prof, ATN_K_TRACE_FUSED);
+                    npr_adv_launch_bounce(al, stream, pb, scene, aa, b);
+                    prof_end(prof);
+                    if (b == 0 && np_capture) npr_adv_launch_capture0(g_all, stream, pb, fp, aa);
+                    pbs.queue[b & 1] = np_adv_queue.p;
+                    prof_begin(prof, ATN_K_SHADE);
+                    if (npr_adv_launch_shade(scene.material_set, plan.shade_waves, plan.shade_grid, stream, pbs, scene, fp, camera, b, np_ab.p))
+                        return fail(ATN_ERR_UNSUPPORTED, "NPR skip-through: no alpha-blend shade kernel for the scene's material set");
+                    prof_end(prof);
+                }
+                else {
+                    prof_begin(prof, ATN_K_SHADE);
+                    launch_shade<false>(plan, stream, pbs, fp, b, SvgfShade{});
+                    prof_end(prof);
+                }
                 if (b == 0 && np_capture) npr_launch_capture0(g_all, stream, pb, fp, na);
             }
             if (d->sample > 1) {
@@ -3277,6 +3341,7 @@ public:
         }
         ATN_HIP(np_fence.record(stream));
         np_captured = np_capture != 0;
+        np_adv_captured = np_captured && adv;
         rc = ns_end_frame();
         if (rc) return rc;
         rc = gather_film(*d, pb, fp);
@@ -3292,8 +3357,16 @@ public:
             ATN_HIP(hipMemsetAsync(np_desc_p.p, 0, np_desc_p.n * sizeof(float4), stream));
             ATN_HIP(hipMemsetAsync(np_desc_n.p, 0, np_desc_n.n * sizeof(float4), stream));
         }
-        np_captured = false;
+        np_captured = false; np_adv_captured = false;
         return reset();
+    }
+
+    int npr_advance_download(void* out)
+    {
+        if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
+        if (!np_adv_captured) return fail(ATN_ERR_INVALID_ARG, "the last NPR frame kept no look-through stage: atn_npr_capture(ctx, 1) and atn_npr_set_skip_through(ctx, 1) before a frame of a scene that needs it");
+        const StageBuf bufs[] = { { np_st_adv.p, 2 * (size_t)np_w * np_h * sizeof(float4) } };
+        return download_stage(bufs, 0, out, "no such NPR buffer");
     }
 
     int npr_download(int32_t which, void* out)
@@ -4274,6 +4347,8 @@ int atn_npr_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host)
 int atn_npr_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.npr_reset(); }); }
 int atn_npr_capture(atn_ctx* ctx, int32_t on) { CTX_QUIET_OR_FAIL(ctx); ctx->r.np_capture = on != 0; return ATN_OK; }
 int atn_npr_download(atn_ctx* ctx, int32_t which, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.npr_download(which, out_host); }); }
+int atn_npr_set_skip_through(atn_ctx* ctx, int32_t mode) { CTX_QUIET_OR_FAIL(ctx); return ctx->r.npr_set_skip_through(mode); }
+int atn_npr_advance_download(atn_ctx* ctx, void* out_host) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.npr_advance_download(out_host); }); }
 int atn_volume_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host)
 {
     CTX_OR_FAIL(ctx);

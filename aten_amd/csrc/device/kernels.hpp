@@ -592,6 +592,14 @@ ATN_DEV float4 vertex_albedo(const DevScene& sc, const DevMaterial& m, const Hit
     albedo4 = add4(mul4(1.0F, albedo4), make_float4(0, 0, 0, 0));
     return albedo4;
 }
+// ... with the path's alpha blend (the NPR look-through's plane, device/npr_advance.hpp): transmission * albedo + throughput
+// (pathtracing.cpp:158), blend = {alpha_blend.throughput.xyz, alpha_blend.transmission}
+ATN_DEV float4 vertex_albedo_blend(const DevScene& sc, const DevMaterial& m, const HitRec& rec, const float4& blend)
+{
+    float4 albedo4 = sample_texture(sc, m.albedoMap, rec.u, rec.v, m.baseColor);
+    albedo4 = add4(mul4(blend.w, albedo4), make_float4(blend.x, blend.y, blend.z, 0.0F));
+    return albedo4;
+}
 // the shading frame: the back-face rule, material::applyNormal (the normal map -- or, for CarPaint, the flake normal and the random
 // number it shares: the return value) and what the BSDF sample, the NEE evaluation and the light sample share (shading.hpp, HitPre).
 // `orienting_normal` comes in as the hit's normal.
@@ -642,10 +650,14 @@ ATN_DEV void store_shadow_ray(const PathBuffers& pb, uint32_t slot, const HitRec
 // it was.
 // DN: the deferred-NEE flavour (PathBuffers::nee_reached, above), every shade launch of a deferred frame: at the NEE block it casts the
 // shadow ray from the light sample's geometry and leaves the evaluation to k_nee_eval; hit records are read from the bounce's plane.
-template <bool SVGF, int MS, bool REGEN = false, bool LA = false, bool DN = false>
+// AB: the alpha-blend flavour, the shade launches of an NPR frame that looks through surfaces (device/npr_advance.hpp): the albedo of a
+// hit and the colour of a miss go through ApplyAlphaBlend with the slot's entry of `ab` {alpha_blend.throughput.xyz, transmission};
+// every other launch multiplies by 1 and adds 0.
+template <bool SVGF, int MS, bool REGEN = false, bool LA = false, bool DN = false, bool AB = false>
 ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const atn_camera_param& cam, int32_t bounce_arg, const SvgfShade& sv,
-                        const RegenOut& ro = RegenOut{})
+                        const RegenOut& ro = RegenOut{}, const float4* __restrict__ ab = nullptr)
 {
+    static_assert(!AB || (!SVGF && !REGEN && !LA && !DN), "the alpha blend is the NPR frame's");
     static_assert(!LA || (!SVGF && !REGEN && ATN_SHADE_PARTITION), "the look-ahead is the serial path tracer's");
     static_assert(!DN || (!SVGF && !REGEN && MS <= kMsAnalytic), "the deferred NEE is the serial path tracer's, without CarPaint and toon");
     const float4* __restrict__ isect_b = pb.isect;
@@ -866,7 +878,9 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                         if (sc.ibl_importance) pdfLight = ibl_direction_pdf(sc, dir);   // optional table sampler: its own density
                         misW = pdfb / (pdfLight + pdfb);
                     }
-                    f3 c = 1.0F * mk3(mul4(misW, emit)) + mk3(0.0F);   // ApplyAlphaBlend (transmission 1, throughput 0)
+                    f3 c;
+                    if constexpr (AB) { const float4 bl = ab[slot]; c = bl.w * mk3(mul4(misW, emit)) + mk3(bl); }      // ApplyAlphaBlend
+                    else c = 1.0F * mk3(mul4(misW, emit)) + mk3(0.0F);   // ApplyAlphaBlend (transmission 1, throughput 0)
                     c = c * throughput;
                     contrib_add = c; contrib_changed = true;
                     flags |= F_TERMINATED;
@@ -913,6 +927,9 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                         if (bounce == 0) sv.primary[s4.w] = make_float4(rec.p.x, rec.p.y, rec.p.z, 1.0F);
                     }
                     albedo4 = sample_texture(sc, albedo_map, rec.u, rec.v, make_float4(1.0F, 1.0F, 1.0F, 1.0F));
+                }
+                else if constexpr (AB) {
+                    albedo4 = vertex_albedo_blend(sc, m, rec, ab[slot]);
                 }
                 else {
                     albedo4 = vertex_albedo(sc, m, rec);

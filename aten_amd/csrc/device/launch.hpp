@@ -164,6 +164,17 @@ void npr_launch_bounce(const RayLaunch& l, hipStream_t st, const PathBuffers& pb
                        const atn_camera_param& cam, const NprArgs& na, int32_t bounce);
 void npr_launch_capture0(uint32_t grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const NprArgs& na);
 
+// ---- npr_advance.hip (device/npr_advance.hpp) ----
+struct NprAdvArgs;
+// the alpha-blend plane and the look-through's records of a sample, per slot
+void npr_adv_launch_init(uint32_t slot_grid, hipStream_t st, const FrameParams& fp, const NprAdvArgs& aa);
+// one bounce's look-through between npr_launch_bounce and the shade launch: the job over the queue NPR's eval left, through the frame's walk
+void npr_adv_launch_bounce(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const NprAdvArgs& aa, int32_t bounce);
+void npr_adv_launch_capture0(uint32_t slot_grid, hipStream_t st, const PathBuffers& pb, const FrameParams& fp, const NprAdvArgs& aa);
+// the shade launch's alpha-blend flavour; -1 = the material set has none (CarPaint)
+int npr_adv_launch_shade(int material_set, int waves, uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                         const atn_camera_param& cam, int32_t bounce, const float4* ab);
+
 // ---- ao.hip (device/ao.hpp) ----
 struct AoArgs;
 // one AO frame's launches after k_gen_path: the primary rays (the pass's first trace launch, with the AO job), shade over the queue,

@@ -514,6 +514,21 @@ class PathTracing:
             return out
         raise ValueError("no NPR buffer %r" % (name,))
 
+    def npr_set_skip_through(self, mode):
+        """0 (default): npr_render refuses STENCIL materials and alpha blending with an alpha that may be < 1; 1: it looks through them
+        (AdvanceNPRPath: CheckStencil, CheckMaterialTranslucentByAlpha; docs/NPR_ADVANCE.md)."""
+        self._check(self._l.atn_npr_set_skip_through(self._ctx, int(mode)))
+
+    def npr_advance_buffer(self):
+        """The look-through's stage of the last NPR frame after bounce 0 (needs npr_capture, npr_set_skip_through(1) and a scene that
+        looks through something): dict kind (0 none, 1 stencil, 2 alpha), walks, answer (triangle id, -1 = miss) int32 [h, w],
+        singular bool [h, w], throughput float32 [h, w, 3], transmission float32 [h, w]."""
+        w, h = self.width, self.height
+        out = np.empty((h, w, 2, 4), np.float32)
+        self._check(self._l.atn_npr_advance_download(self._ctx, out.ctypes.data))
+        return dict(kind=out[..., 0, 0].astype(np.int32), walks=out[..., 0, 1].astype(np.int32), answer=out[..., 0, 2].astype(np.int32),
+                    singular=out[..., 0, 3] != 0, throughput=out[..., 1, :3].copy(), transmission=out[..., 1, 3].copy())
+
     # ---- volume rendering: path tracing through homogeneous media (aten::VolumePathTracing; docs/VOLUME.md)
     def volume_render(self, width, height, max_depth=5, rr_depth=3, spp=1, frame=0, progressive=True, break_on_terminate=True,
                       download=True, profile=False):

@@ -527,19 +527,30 @@ int atn_restir_download(atn_ctx* ctx, int32_t which, void* out_host);
  * the path's query ray; a found line sets the path's contribution to the MIS-weighted line colour and ends the path.  Settings:
  * atn_scene_rendering_config.feature_line (atn_feature_line_config) and atn_material_param.feature_line (atn_feature_line_mtrl).
  *   atn_npr_render: one frame; the film follows atn_render's progressive / overwrite rules.  ATN_ERR_UNSUPPORTED for a config
- *                   with feature lines off, StencilType::STENCIL materials, alpha blending with a material whose alpha may be < 1,
- *                   CarPaint materials, a screen shard with world > 1, path regeneration, relaxed shade math and count_stats.
+ *                   with feature lines off, StencilType::STENCIL materials and alpha blending with a material whose alpha may be
+ *                   < 1 (both unless atn_npr_set_skip_through(1)), CarPaint materials, a screen shard with world > 1, path regeneration, relaxed shade math and count_stats.
  *   atn_npr_reset: the film and the sample-ray state start over (a fresh context's)
  *   atn_npr_capture: keep the stage buffers of the next frames (tests)
  *   atn_npr_download: which = 0 the line decision per pixel, atn_vec4[w*h] {found, bounce, closest distance, 0} of the frame's
  *                     last sample that found one; 1 the sample-ray descriptors after bounce 0, atn_vec4[w*h][8] {u, v, live, 0};
  *                     2 the disc after bounce 0, atn_vec4[w*h][2] {center, radius} {normal, accumulated distance}; 3 the CMJ
  *                     dimension after bounce 0, uint32[w*h].  All for a frame rendered with capture on.
+ *   atn_npr_set_skip_through: AdvanceNPRPath's look-through (docs/NPR_ADVANCE.md).  mode 0 (default): atn_npr_render refuses STENCIL
+ *                     materials and alpha blending with an alpha that may be < 1, as above.  mode 1: it renders them -- behind a
+ *                     STENCIL surface the path looks for a front-facing ALWAYS surface (CheckStencil), behind a surface with
+ *                     alpha < 1 it goes on with the surface's colour blended in (CheckMaterialTranslucentByAlpha); a scene that
+ *                     needs neither renders with the kernels of mode 0, byte for byte.  Mode 1 on a scene that needs the look-through
+ *                     refuses atn_npr_shadow_set_mode(1), hatching included (ATN_ERR_UNSUPPORTED).  Other values: ATN_ERR_INVALID_ARG.
+ *   atn_npr_advance_download: the look-through's stage buffer of the last frame (capture on, mode 1, a scene that needs it), after
+ *                     bounce 0: atn_vec4[w*h][2] {the check that said true: 0 none, 1 stencil, 2 alpha; walks done; the answer: the
+ *                     triangle id, or -1 for a miss; is_singular} {alpha_blend.throughput.rgb, alpha_blend.transmission}
  * Additive entry points: atn_abi_version stays 3. */
 int atn_npr_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host);
 int atn_npr_reset(atn_ctx* ctx);
 int atn_npr_capture(atn_ctx* ctx, int32_t on);
 int atn_npr_download(atn_ctx* ctx, int32_t which, void* out_host);
+int atn_npr_set_skip_through(atn_ctx* ctx, int32_t mode);
+int atn_npr_advance_download(atn_ctx* ctx, void* out_host);
 
 /* ---- Volume rendering: path tracing through homogeneous media (aten::VolumePathTracing / idaten::VolumeRendering; docs/VOLUME.md)
  * Materials with is_medium set carry a medium (atn_medium_param): type ATN_MTRL_VOLUME is a pure boundary the ray passes through,

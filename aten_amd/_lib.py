@@ -52,6 +52,7 @@ SYMBOLS = [
     "atn_mgpu_svgf_render", "atn_mgpu_svgf_set_motion_depth", "atn_mgpu_svgf_reset", "atn_mgpu_svgf_set_atrous_iterations",
     "atn_mgpu_svgf_set_dilate_temporal_weight", "atn_mgpu_svgf_download", "atn_mgpu_svgf_output_device",
     "atn_mgpu_get_kernel_times", "atn_mgpu_reset_kernel_times",
+    "atn_set_sphere_intersection", "atn_sphere_leaves", "atn_mgpu_set_sphere_intersection",
 ]
 
 
@@ -112,6 +113,8 @@ def lib():
         l.atn_reset.argtypes = [vp]
         l.atn_set_upload_options.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         l.atn_set_regeneration.argtypes = [vp, C.c_int32]
+        l.atn_set_sphere_intersection.argtypes = [vp, C.c_int32]
+        l.atn_sphere_leaves.argtypes = [vp, vp]
         l.atn_set_shade_math.argtypes = [vp, C.c_int32]
         l.atn_set_rr_lookahead.argtypes = [vp, C.c_int32]
         l.atn_rr_lookahead_active.argtypes = [vp]; l.atn_rr_lookahead_active.restype = C.c_int32
@@ -213,6 +216,7 @@ def lib():
         l.atn_mgpu_render.argtypes = [vp, C.POINTER(Destination), vp]
         l.atn_mgpu_reset.argtypes = [vp]
         l.atn_mgpu_set_regeneration.argtypes = [vp, C.c_int32]
+        l.atn_mgpu_set_sphere_intersection.argtypes = [vp, C.c_int32]
         l.atn_mgpu_render_burst.argtypes = [vp, C.POINTER(Destination), C.c_int32, vp]
         l.atn_mgpu_synchronize.argtypes = [vp]
         l.atn_mgpu_film_device.argtypes = [vp]; l.atn_mgpu_film_device.restype = vp

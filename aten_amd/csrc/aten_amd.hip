@@ -848,6 +848,16 @@ public:
 
     int fail(int code, const std::string& msg) { last_error = msg; return code; }
 
+    // ---- analytic spheres (atn_set_sphere_intersection, docs/SPHERES.md) ----
+    int sphere_mode = 0;                // context state like the upload options: read by the next atn_upload_scene / atn_update_tlas
+    uint32_t n_sphere_leaves = 0;       // top-layer leaves of the uploaded scene the sphere-aware kernels (spheres.hip) test; 0 in mode 0
+    // what a scene with sphere leaves cannot be used for (each is a later change): false = go on
+    int sph_refuse(const char* what)
+    {
+        if (!n_sphere_leaves) return ATN_OK;
+        return fail(ATN_ERR_UNSUPPORTED, std::string("sphere intersection: ") + what + " (atn_set_sphere_intersection(0) and upload the scene again)");
+    }
+
     int init(int device_ordinal)
     {
         int n = 0;
@@ -907,7 +917,7 @@ public:
         // changes them -- every shard of a node, every re-upload gets the same layout whatever happened to the process environment since)
         const int layout_top = opt_node_layout ? kLayoutTopLevels : 0;
         const bool planar_lights = opt_planar_lights;
-        if (!build_host_image(img, s, err, env_anyhit_twin, env_anyhit_twin_dirs, layout_top, planar_lights)) return fail(ATN_ERR_UNSUPPORTED, err);
+        if (!build_host_image(img, s, err, env_anyhit_twin, env_anyhit_twin_dirs, layout_top, planar_lights, kTwinBudgetBytes, sphere_mode)) return fail(ATN_ERR_UNSUPPORTED, err);
         n_planar_lights = 0;
         for (const atn_light_param& l : img.lights) n_planar_lights += l._pad != 0 ? 1u : 0u;
         collect_planar_certs(s, img.lights);
@@ -934,6 +944,7 @@ public:
         ATN_HIP(hipGetLastError());
         ATN_HIP(hipStreamSynchronize(stream));      // `img` is pageable host memory
         scene = img.params;
+        n_sphere_leaves = img.n_sphere_leaf;
         if (!env_shadow_plain) scene.shadow_plain = 0;
         scene.nodes = nodes.p; scene.tris = tris.p; scene.shade_tris = shade_tris.p; scene.vtx_pos = vtx_pos.p; scene.vtx_nml = vtx_nml.p;
         scene.objects = objects.p; scene.matrices = matrices.p; scene.materials = materials.p; scene.carpaint = carpaint.p;
@@ -1217,7 +1228,7 @@ public:
         // the new top layer: every top-layer record is kInnerBytes long, laid out in walk order at the image's tail
         ListLayout lay;
         std::string err;
-        if (!analyse_list(lay, top, n_top, true, err)) return fail(ATN_ERR_UNSUPPORTED, err);
+        if (!analyse_list(lay, top, n_top, true, err, SphereLeafRule{ sphere_mode, objs, n_objs })) return fail(ATN_ERR_UNSUPPORTED, err);
         for (uint32_t j = 0; j < lay.order.size(); j++) {
             if (lay.kind[j] == KIND_TRI) return fail(ATN_ERR_UNSUPPORTED, "triangle leaves in this list need a full scene upload");
             lay.offset[j] = top_base + j * kInnerBytes;
@@ -1234,6 +1245,7 @@ public:
         int32_t root = kLinkEnd;
         uint64_t counts[3] = { 0, 0, 0 };
         if (!emit_list(reinterpret_cast<char*>(rec.data()), lay, top, c, root, counts, err, top_base)) return fail(ATN_ERR_UNSUPPORTED, err);
+        if (c.n_sphere_leaf && !sphere_materials_ok(objs, n_objs, (uint32_t)scene.n_materials, err)) return fail(ATN_ERR_UNSUPPORTED, err);
         std::vector<float4> mv;
         if (n_mtxs) {
             mv.resize((size_t)n_mtxs * 4);
@@ -1252,6 +1264,7 @@ public:
         if (n_mtxs) { int r = stage_copy(matrices.p, mv.data(), mtx_bytes); if (r) return r; log_range(SB_MATRICES, 0, mtx_bytes); n_host_matrices = n_mtxs; host_matrices.assign(mtxs, mtxs + n_mtxs); }
         { int r = end_scene_update(); if (r) return r; }
         list_root_link[0] = root;
+        n_sphere_leaves = c.n_sphere_leaf;
         // a light's instance may have a new matrix, or point at another object / matrix (an objs-only update too): the flags hold only
         // if every planar light's records came back byte for byte
         if (scene.planar_lights && !planar_certs_survive_objects(objs, n_objs, mtxs, n_mtxs)) scene.planar_lights = 0;
@@ -1459,6 +1472,7 @@ public:
         if (!has_scene) return fail(ATN_ERR_NO_SCENE, "atn_upload_scene has not been called");
         if ((objs == nullptr) != (n_objs == 0)) return fail(ATN_ERR_INVALID_ARG, "object array and count do not match");
         if (n_mtxs && !mtxs) return fail(ATN_ERR_INVALID_ARG, "null matrix array");
+        { const int sr = sph_refuse("atn_tlas_rebuild builds the top layer over instance leaves and would drop the sphere leaves"); if (sr) return sr; }
         ATN_HIP(hipSetDevice(device));
         const atn_object_param* O = objs ? objs : host_objects.data();
         const uint32_t n_o = objs ? n_objs : (uint32_t)host_objects.size();
@@ -1963,6 +1977,7 @@ public:
         p.kind = kind;
         p.refill = refill_walk(true);
         p.lds_bytes = lds_scene_bytes();
+        p.sph = n_sphere_leaves > 0;
         // threads per block of the plain walk's fused launches: one wave per block retires on its own (1-2 % over 256); a node image
         // of a few KB is walked from an LDS copy (trace_simple<., ., true>), above 8 KB per copy the blocks get four waves to share it
         p.block = p.lds_bytes > 8192u ? 256u : 64u;
@@ -1990,6 +2005,7 @@ public:
     void launch_trace(const PassPlan& p, const PathBuffers& pb, bool count, int32_t b, hipStream_t st)
     {
         const dim3 g(p.trace_grid), t(p.refill ? (uint32_t)kTraceBlock : 256u);
+        if (p.sph) { sph_launch_trace(SHADOW, count, p.refill, g.x, t.x, st, pb, scene, b); return; }
         with_flags([&](auto c, auto refill) {
             if constexpr (SHADOW) hipLaunchKernelGGL((k_trace_shadow<decltype(c)::value, decltype(refill)::value>), g, t, 0, st, pb, scene, b);
             else hipLaunchKernelGGL((k_trace_closest<decltype(c)::value, decltype(refill)::value>), g, t, 0, st, pb, scene, b);
@@ -2031,6 +2047,7 @@ public:
         // kernel as it is without -- and so is every launch of a material set that has no such flavour (none of those qualifies:
         // rr_lookahead_frame; unmarked, no path is ever doomed)
         const bool la = !SVGF && pb.doomed_bit != 0u && b >= fp.rr_depth;
+        if (!SVGF && p.sph) { (void)sph_launch_shade(scene.material_set, p.shade_waves, la, p.shade_grid, st, pb, scene, fp, camera, b); return; }     // (sph_frame_check refused what has no such kernel)
         // the deferred-NEE flavour for every launch of a deferred frame (nee_deferral_frame: run_paths hands such a frame the flag plane)
         const bool dn = !SVGF && pb.nee_reached != nullptr;
         with_shade_flavour(scene.material_set, p.shade_waves, [&](auto k) {
@@ -2266,6 +2283,8 @@ public:
         if (rc) return rc;
         rc = ns_check(d);
         if (rc) return rc;
+        rc = sph_frame_check(*d);
+        if (rc) return rc;
         ATN_HIP(hipSetDevice(device));
         if (d->sample > 1 && regen_applies(*d, 1)) return render_regen(d, 1, out_host);
         const bool count = d->count_stats != 0, prof = d->profile != 0;
@@ -2336,6 +2355,21 @@ public:
     // device memory, and a stage whose queue is empty costs a kernel start.
     // ------------------------------------------------------------------------------------------------
     bool shade_math_relaxed = false;    // atn_set_shade_math
+    // atn_render on a scene with sphere leaves: the serial loop with the parity shade math, eager NEE, no pre-pass, no toon surfaces,
+    // no material a shadow ray looks through (the sphere-aware kernels of spheres.hip are those)
+    int sph_frame_check(const atn_destination& d)
+    {
+        if (!n_sphere_leaves) return ATN_OK;
+        const bool count = d.count_stats != 0;
+        if (d.sample > 1 && regen_applies(d, 1)) return sph_refuse("path regeneration does not trace sphere leaves: atn_set_regeneration(0)");
+        if (shade_math_relaxed) return sph_refuse("there is no relaxed-math shade kernel for sphere hits: atn_set_shade_math(0)");
+        if (nee_deferral_frame(count)) return sph_refuse("deferred NEE does not replay sphere hits: atn_set_nee_deferral(0)");
+        if (gm_on) return sph_refuse("geometry motion does not follow sphere leaves: atn_set_geometry_motion(0)");
+        if (ns_mode != 0) return sph_refuse("the NPR shadow / hatching pre-pass does not trace sphere leaves: atn_npr_shadow_set_mode(0)");
+        if (scene.material_set >= kMsToon) return sph_refuse("toon / stylised materials walk a visibility ray of their own that does not test sphere leaves");
+        if (scene.any_alpha) return sph_refuse("shadow rays do not look through alpha / stencil materials in a scene with sphere leaves");
+        return ATN_OK;
+    }
     int regen_mode = 0;         // atn_set_regeneration: 0 = serial sample loop, 1 = regenerated pool wherever it applies
     uint64_t rg_host_totals[4] = {};
     static constexpr int32_t kRegenMaxStages = 1 << 16;
@@ -2356,6 +2390,7 @@ public:
     {
         if (!d) return fail(ATN_ERR_INVALID_ARG, "null destination");
         if (n_frames <= 0) return fail(ATN_ERR_INVALID_ARG, "bad burst length");
+        { const int sr = sph_refuse("atn_render_burst does not trace sphere leaves: render the frames with atn_render"); if (sr) return sr; }
         if (ns_mode == 1) return fail(ATN_ERR_UNSUPPORTED, "NPR shadow pre-pass: bursts are not supported: render the frames with atn_render, or atn_npr_shadow_set_mode(0)");
         if (regen_applies(*d, n_frames)) {
             { const int rc = check_ready(d); if (rc) return rc; }
@@ -2620,6 +2655,7 @@ public:
     // ≙ aten::SVGFRenderer::OnRender (svgf.cpp:452-637): the two halves below, back to back
     int svgf_render(const atn_destination* d, int32_t compute_motion, atn_vec4* out_host, atn_vec4* stages_host, bool path_pass = true)
     {
+        { const int sr = sph_refuse("the SVGF renderer does not trace sphere leaves"); if (sr) return sr; }
         int rc = check_ready(d);
         if (rc) return rc;
         // (a shard of a node-wide frame goes through the halves: MultiGpu::svgf_render gathers the hand-over planes in between)
@@ -2646,6 +2682,8 @@ public:
     // slot_to_pixel), so on a screen shard (world > 1) it fills exactly the shard's pixels of them.
     int svgf_path_half(const atn_destination* d, int32_t compute_motion, bool want_stages, bool path_pass)
     {
+        // (here too: a shard of a node-wide frame enters at this half, not through svgf_render)
+        { const int sr = sph_refuse("the SVGF renderer does not trace sphere leaves"); if (sr) return sr; }
         int rc = check_ready(d);
         if (rc) return rc;
         const bool geo_motion = compute_motion == 2;
@@ -2857,6 +2895,7 @@ public:
     // + spatial + pixel colour, bounces >= 1 = the path tracer's own k_shade.
     int restir_render(const atn_destination* d, int32_t compute_motion, atn_vec4* out_host)
     {
+        { const int sr = sph_refuse("the ReSTIR renderer does not trace sphere leaves"); if (sr) return sr; }
         int rc = check_ready(d);
         if (rc) return rc;
         if (d->sample != 1) return fail(ATN_ERR_UNSUPPORTED, "ReSTIR renders one sample per pixel (destination.sample must be 1)");
@@ -3236,6 +3275,7 @@ public:
     // CPU renderer (npr.cpp:101-200): one pass of the sample loop per frame (docs/NPR.md)
     int npr_render(const atn_destination* d, atn_vec4* out_host)
     {
+        { const int sr = sph_refuse("the NPR renderer does not trace sphere leaves"); if (sr) return sr; }
         int rc = check_ready(d);
         if (rc) return rc;
         if (!np_cfg.enabled) return fail(ATN_ERR_UNSUPPORTED, "feature lines are off in the scene's config (FeatureLineConfig.enabled == 0): render with atn_render");
@@ -3447,6 +3487,7 @@ public:
     // iterations of closest hit, shade and connection walk -- a fixed number of launches, nothing is read back
     int volume_render(const atn_destination* d, atn_vec4* out_host)
     {
+        { const int sr = sph_refuse("the volume renderer does not trace sphere leaves"); if (sr) return sr; }
         int rc = check_ready(d);
         if (rc) return rc;
         if (!vl_refuse.empty()) return fail(ATN_ERR_UNSUPPORTED, ("volume frames: " + vl_refuse).c_str());
@@ -3602,6 +3643,7 @@ public:
     // number of launches, nothing is read back
     int ao_render(const atn_destination* dst, atn_vec4* out_host)
     {
+        { const int sr = sph_refuse("the AO renderer does not trace sphere leaves"); if (sr) return sr; }
         if (!dst) return fail(ATN_ERR_INVALID_ARG, "null destination");
         atn_destination d1 = *dst;      // the reference reads neither sample nor maxDepth
         d1.maxDepth = 1; d1.russianRouletteDepth = 1; d1.sample = 1;
@@ -4019,6 +4061,20 @@ int atn_set_upload_options(atn_ctx* ctx, int32_t anyhit_twin, int32_t anyhit_twi
     if (anyhit_twin_dirs >= 0) ctx->r.env_anyhit_twin_dirs = anyhit_twin_dirs;
     if (node_layout >= 0) ctx->r.opt_node_layout = node_layout != 0;
     if (planar_lights >= 0) ctx->r.opt_planar_lights = planar_lights != 0;
+    return ATN_OK;
+}
+int atn_set_sphere_intersection(atn_ctx* ctx, int32_t mode)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    if (mode < 0 || mode > 1) return ctx->r.fail(ATN_ERR_INVALID_ARG, "sphere intersection mode out of range");
+    ctx->r.sphere_mode = mode;
+    return ATN_OK;
+}
+int atn_sphere_leaves(atn_ctx* ctx, uint32_t* n)
+{
+    CTX_OR_FAIL(ctx);
+    if (!n) return ctx->r.fail(ATN_ERR_INVALID_ARG, "null output");
+    *n = ctx->r.has_scene ? ctx->r.n_sphere_leaves : 0u;
     return ATN_OK;
 }
 int atn_update_camera(atn_ctx* ctx, const atn_camera_param* camera) { CTX_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.updateCamera(camera); }); }
@@ -4668,6 +4724,15 @@ int atn_mgpu_set_regeneration(atn_mgpu* mg, int32_t mode)
         return (int)ATN_OK;
     });
 }
+int atn_mgpu_set_sphere_intersection(atn_mgpu* mg, int32_t mode)
+{
+    MG_OR_FAIL(mg);
+    if (mode < 0 || mode > 1) return mg->m.fail(ATN_ERR_INVALID_ARG, "sphere intersection mode out of range");
+    return mg_guarded(mg, [&] {
+        for (int i = 0; i < mg->m.n; i++) mg->m.shard[i]->sphere_mode = mode;
+        return (int)ATN_OK;
+    });
+}
 int atn_mgpu_reset(atn_mgpu* mg)
 {
     MG_OR_FAIL(mg);
@@ -4814,7 +4879,8 @@ int atn_trace_closest(atn_ctx* ctx, const atn_ray* rays_host, uint32_t n, float 
         const bool refill = r.refill_walk(false);
         const dim3 g(r.trace_grid(n, refill)), t(refill ? (uint32_t)atn::kTraceBlock : 256u);
         const atn_ray* rp = rays.p;
-        atn::with_flags([&](auto c, auto rf) {
+        if (r.n_sphere_leaves) atn::sph_launch_batch(stats_out != nullptr, refill, g.x, t.x, r.stream, r.scene, rp, n, t_min, t_max, out.p, st.p);
+        else atn::with_flags([&](auto c, auto rf) {
             hipLaunchKernelGGL((atn::k_trace_batch<decltype(c)::value, decltype(rf)::value>), g, t, 0, r.stream, r.scene, rp, n, t_min, t_max, out.p, st.p);
         }, stats_out != nullptr, refill);
     }
@@ -4836,6 +4902,8 @@ int atn_trace_shadow(atn_ctx* ctx, const atn_shadow_query* queries_host, uint32_
     if (n == 0) return ATN_OK;
     if (!queries_host || !out_visible) return r.fail(ATN_ERR_INVALID_ARG, "null queries / output");
     if (r.scene.n_lights <= 0) return r.fail(ATN_ERR_UNSUPPORTED, "atn_trace_shadow: the scene has no lights");
+    if (r.n_sphere_leaves && (flavour == atn::kShadowProbeDeferred || flavour == atn::kShadowProbeRegen)) return r.sph_refuse("atn_trace_shadow: only the fused and the counted flavour test sphere leaves");
+    if (r.n_sphere_leaves && r.scene.any_alpha) return r.sph_refuse("shadow rays do not look through alpha / stencil materials in a scene with sphere leaves");
     for (uint32_t i = 0; i < n; i++)
         if (queries_host[i].light < 0 || queries_host[i].light >= r.scene.n_lights) return r.fail(ATN_ERR_INVALID_ARG, "atn_trace_shadow: light index outside the scene's lights");
     const uint64_t slots64 = 2ull * n + atn::kShadowProbePad;
@@ -4910,6 +4978,7 @@ int atn_shade_stage(atn_ctx* ctx, const atn_shade_call* call, const atn_shade_ve
     if (call->bounce < 0 || call->bounce >= call->max_depth) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: bounce outside 0 .. max_depth - 1");
     if (!r.has_camera || r.n_seeds == 0) return r.fail(ATN_ERR_INVALID_ARG, "atn_shade_stage: camera / sampler missing");
     if (r.shade_math_relaxed) return r.fail(ATN_ERR_UNSUPPORTED, "atn_shade_stage: the relaxed-math kernel is not the parity path: atn_set_shade_math(0)");
+    { const int sr = r.sph_refuse("atn_shade_stage's records have no sphere hits"); if (sr) return sr; }
     if (n == 0) return ATN_OK;
     if (!records_host || !out_host) return r.fail(ATN_ERR_INVALID_ARG, "null records / output");
     C_HIP(r, hipSetDevice(r.device));

@@ -463,16 +463,16 @@ __global__ void __launch_bounds__(256) k_regen_end(PathBuffers pb, FrameParams f
 #define ATN_TRACE_ATTR
 #endif
 
-template <bool COUNT, bool REFILL, class Job, bool LDSN = false>
+template <bool COUNT, bool REFILL, class Job, bool LDSN = false, bool SPH = false>
 ATN_DEV void trace_dispatch(const DevScene& sc, uint32_t count, uint32_t* fetch_counter, const Job& job, TravCounters* tc)
 {
     if constexpr (REFILL) {
         __shared__ TraceShared sh;
         if (LDSN) lds_scene_copy(sc);       // the whole node image + the matrices (small scenes)
-        trace_refill<COUNT, Job, LDSN>(sc, sh, count, fetch_counter, job, tc);
+        trace_refill<COUNT, Job, LDSN, SPH>(sc, sh, count, fetch_counter, job, tc);
     }
     else {
-        trace_simple<COUNT, Job, LDSN>(sc, count, job, tc);
+        trace_simple<COUNT, Job, LDSN, SPH>(sc, count, job, tc);
     }
 }
 
@@ -578,9 +578,19 @@ ATN_DEV void path_sampler(uint4& s4, const PathBuffers& pb, const FrameParams& f
     s4.z = rnd * 0x1fe3434fu * ((fs + 133u * rnd) / 256u);
 }
 // the hit record -> the surface point, its material id and which side the ray arrived on
-ATN_DEV void vertex_surface(HitRec& rec, int32_t& mtrlid, bool& isBackfacing, const DevScene& sc, const float4& is4, const f3& ray_dir)
+// SPH (spheres.hip only): a record with tri < 0 is a sphere leaf's hit {objid, t, 0, -1} (traverse.hpp, sphere_test) and goes through
+// sphere::EvaluateHitResult; `ray_org` is read only there.
+template <bool SPH = false>
+ATN_DEV void vertex_surface(HitRec& rec, int32_t& mtrlid, bool& isBackfacing, const DevScene& sc, const float4& is4, const f3& ray_dir, const f3& ray_org = f3{})
 {
     const int32_t tri_id = __float_as_int(is4.w);
+    if constexpr (SPH) {
+        if (tri_id < 0) {
+            evaluate_sphere_hit(rec, mtrlid, sc, __float_as_int(is4.x), ray_org, ray_dir, is4.y);
+            isBackfacing = dot(rec.normal, -ray_dir) < 0.0F;
+            return;
+        }
+    }
     evaluate_hit(rec, sc, __float_as_int(is4.x), tri_id, is4.y, is4.z);
     mtrlid = triangle_mtrlid(sc, tri_id);
     isBackfacing = dot(rec.normal, -ray_dir) < 0.0F;
@@ -653,11 +663,13 @@ ATN_DEV void store_shadow_ray(const PathBuffers& pb, uint32_t slot, const HitRec
 // AB: the alpha-blend flavour, the shade launches of an NPR frame that looks through surfaces (device/npr_advance.hpp): the albedo of a
 // hit and the colour of a miss go through ApplyAlphaBlend with the slot's entry of `ab` {alpha_blend.throughput.xyz, transmission};
 // every other launch multiplies by 1 and adds 0.
-template <bool SVGF, int MS, bool REGEN = false, bool LA = false, bool DN = false, bool AB = false>
+// SPH: the sphere-aware flavour (spheres.hip, docs/SPHERES.md): a hit record of a sphere leaf is evaluated as a sphere's.
+template <bool SVGF, int MS, bool REGEN = false, bool LA = false, bool DN = false, bool AB = false, bool SPH = false>
 ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FrameParams& fp, const atn_camera_param& cam, int32_t bounce_arg, const SvgfShade& sv,
                         const RegenOut& ro = RegenOut{}, const float4* __restrict__ ab = nullptr)
 {
     static_assert(!AB || (!SVGF && !REGEN && !LA && !DN), "the alpha blend is the NPR frame's");
+    static_assert(!SPH || (!SVGF && !REGEN && !DN && !AB && MS < kMsToon), "sphere leaves are the serial path tracer's, without deferred NEE and toon");
     static_assert(!LA || (!SVGF && !REGEN && ATN_SHADE_PARTITION), "the look-ahead is the serial path tracer's");
     static_assert(!DN || (!SVGF && !REGEN && MS <= kMsAnalytic), "the deferred NEE is the serial path tracer's, without CarPaint and toon");
     const float4* __restrict__ isect_b = pb.isect;
@@ -895,7 +907,7 @@ ATN_DEV void shade_body(const PathBuffers& pb, const DevScene& sc, const FramePa
                 HitRec rec;
                 int32_t mtrlid;
                 bool isBackfacing;
-                vertex_surface(rec, mtrlid, isBackfacing, sc, is4, ray_dir);
+                vertex_surface<SPH>(rec, mtrlid, isBackfacing, sc, is4, ray_dir, ray_org);
                 f3 orienting_normal = rec.normal;
 
                 // FillMaterial (material_impl.h:232-262): a negative id selects the white-diffuse fallback, which
@@ -1353,7 +1365,7 @@ __global__ void __launch_bounds__(256) k_nee_eval(PathBuffers pb, DevScene sc, F
 // REGEN (path regeneration): the shadow ray of a path's last vertex (kShadowFinalFlag) adds its light to `pend` -- by then the slot's
 // `contrib` belongs to the pixel's next sample.
 template <bool ALPHA, bool REGEN = false>
-struct ShadowJob {
+struct ShadowJob {      // (a sphere leaf's hit has no triangle: the sphere-aware launches are ALPHA = false, frames with ignorable materials are refused)
     PathBuffers pb;
     DevScene sc;
     float t_min;

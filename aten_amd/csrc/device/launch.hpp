@@ -54,6 +54,7 @@ struct PassPlan {
     int shade_items;            // queue entries per thread and chunk of the shade launches (FrameParams::chunk_items)
     uint32_t shade_grid;
     int shade_waves;            // 4 / 5 (with_shade_flavour)
+    bool sph = false;           // the uploaded scene has sphere leaves: the pass launches the sphere-aware kernels (spheres.hip)
 };
 
 // One fused trace launch of a pass: shadow rays of stage - 1 + closest-hit rays of stage
@@ -62,7 +63,17 @@ struct TraceLaunch {
     bool refill, lds;
     uint32_t grid, block, lds_bytes;
     int prof_kind;              // ATN_K_*
+    bool sph = false;           // PassPlan::sph
 };
+
+// ---- spheres.hip (device/spheres.hpp): the sphere-aware siblings of the serial loop's launches, for scenes with sphere leaves ----
+void sph_launch_trace(bool shadow, bool count, bool refill, uint32_t grid, uint32_t block, hipStream_t st, const PathBuffers& pb, const DevScene& sc, int32_t b);
+void sph_launch_trace_fused(const TraceLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, int32_t bs, int32_t bc, int32_t launch);
+void sph_launch_batch(bool count, bool refill, uint32_t grid, uint32_t block, hipStream_t st, const DevScene& sc, const atn_ray* rays, uint32_t n,
+                      float t_min, float t_max, atn_intersection* out, unsigned long long* stats);
+// -1 = the material set has no sphere-aware shade (toon)
+int sph_launch_shade(int material_set, int waves, bool la, uint32_t grid, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                     const atn_camera_param& cam, int32_t bounce);
 
 inline TraceLaunch trace_launch(const PassPlan& p, int32_t stage)
 {
@@ -77,7 +88,7 @@ inline TraceLaunch trace_launch(const PassPlan& p, int32_t stage)
     // (timed under "trace_closest" when it is a different kernel from the other launches: the roofline of k_trace_fused<true, .> is
     // about those)
     return TraceLaunch{ closest, refill, p.lds_bytes != 0u, refill ? p.fused_grid : p.fused_grid * (256u / p.block),
-                        refill ? (uint32_t)kTraceBlock : p.block, p.lds_bytes, p.refill && stage == 0 ? ATN_K_TRACE_CLOSEST : ATN_K_TRACE_FUSED };
+                        refill ? (uint32_t)kTraceBlock : p.block, p.lds_bytes, p.refill && stage == 0 ? ATN_K_TRACE_CLOSEST : ATN_K_TRACE_FUSED, p.sph };
 }
 
 // aten_amd.hip instantiates REGEN = false (the serial loop), regen.hip REGEN = true (the regenerated pool)
@@ -85,6 +96,7 @@ template <bool REGEN>
 void launch_trace_fused(const TraceLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, int32_t bs, int32_t bc, int32_t launch)
 {
     const dim3 g(l.grid), t(l.block);
+    if constexpr (!REGEN) if (l.sph) { sph_launch_trace_fused(l, st, pb, sc, bs, bc, launch); return; }
     if constexpr (!REGEN) if (l.closest) { hipLaunchKernelGGL((k_trace_closest<false, false>), g, t, l.lds_bytes, st, pb, sc, bc); return; }
     with_flags([&](auto refill, auto alpha, auto lds) {
         hipLaunchKernelGGL((k_trace_fused<decltype(refill)::value, decltype(alpha)::value, decltype(lds)::value, REGEN>), g, t, l.lds_bytes, st, pb, sc, bs, bc, launch);

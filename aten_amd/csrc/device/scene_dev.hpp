@@ -31,6 +31,10 @@ namespace atn {
 //                     each as long as the list (traverse.hpp: anyhit_root).  Rays with stop_t = +inf enter there, no other ray does.
 //   dead leaf (32 B): a leaf with neither triangle nor nested tree (sphere instance: never tested on this
 //              path); an inner record whose hit link IS its miss link.
+//   sphere leaf (32 B; atn_set_sphere_intersection(1) only, docs/SPHERES.md): a top-layer leaf of an ATN_OBJ_SPHERE object, tested with
+//              sphere::hit by the sphere-aware walks (spheres.hip).  Its link carries BOTH type bits (kLinkToSphere; kLinkEnd is the
+//              only other such value and names no record).  Self-contained: q0 = {center.xyz, radius}
+//              q1 = {objid, sphere.mtrl_id, meshid (leaf f3), next link}
 constexpr int32_t kLinkEnd = -1;
 constexpr int32_t kLinkLeafBit = 1;
 constexpr int32_t kLinkTlasBit = 2;
@@ -38,6 +42,7 @@ constexpr int32_t kLinkTypeMask = 3;
 constexpr int32_t kLinkNotInner = (int32_t)0x80000000u;   // set on leaf / TLAS-leaf links and on kLinkEnd
 constexpr int32_t kLinkToLeaf = kLinkNotInner | kLinkLeafBit;
 constexpr int32_t kLinkToTlas = kLinkNotInner | kLinkTlasBit;
+constexpr int32_t kLinkToSphere = kLinkNotInner | kLinkLeafBit | kLinkTlasBit;
 constexpr uint32_t kLinkOffsetMask = 0x7ffffff0u;
 constexpr int32_t kTlasIdentity = 1;
 constexpr uint32_t kInnerBytes = 32;

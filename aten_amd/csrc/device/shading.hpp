@@ -73,6 +73,27 @@ ATN_DEV void evaluate_hit(HitRec& rec, const DevScene& sc, int32_t objid, int32_
     rec.normal = normalize(m4_applyXYZ(L2W, rec.normal));
 }
 
+// evaluate_hit_result for a sphere leaf's hit (docs/SPHERES.md): sphere::EvaluateHitResult (geometry/sphere.cpp:93-107) with getUV
+// (:5-12), then the L2W step with the identity matrix -- the object is an ATN_OBJ_SPHERE itself, never an instance.  The material is
+// the sphere's own.
+ATN_DEV void evaluate_sphere_hit(HitRec& rec, int32_t& mtrlid, const DevScene& sc, int32_t objid, const f3& ray_org, const f3& ray_dir, float t)
+{
+    const atn_object_param* obj = &sc.objects[objid];
+    const float rad = obj->sphere.radius;
+    const f3 center = mk3(obj->sphere.center[0], obj->sphere.center[1], obj->sphere.center[2]);
+    mtrlid = obj->sphere.mtrl_id;
+    f3 p = ray_org + t * ray_dir;
+    f3 n = (p - center) / rad;
+    rec.area = ((4 * kPi) * rad) * rad;
+    const float phi = asinf(n.y);
+    const float theta = atanf(n.x / n.z);
+    rec.u = (theta + kPi * 0.5F) / kPi;
+    rec.v = (phi + kPi * 0.5F) / kPi;
+    const m4 L2W = m4_identity();
+    rec.p = m4_apply(L2W, p);
+    rec.normal = normalize(m4_applyXYZ(L2W, n));
+}
+
 // texture::at (image/texture.cpp:64-75, image/texture.h:197-208): point sample, wrap-repeat
 ATN_DEV int32_t wrap_repeat(int32_t value, int32_t wrap_size)
 {

@@ -158,6 +158,40 @@ ATN_DEV bool leaf_test(const RaySlab& ray, const float4& q0, const float4& q1, c
     return is_hit;
 }
 
+// sphere::hit (geometry/sphere.cpp:30-91) against a sphere-leaf record's first quarter {center.xyz, radius} on the WORLD ray, and the
+// traverser's acceptance as leaf_test has it -- the leaf step of the reference's stackless walk (docs/SPHERES.md).  sphere::hit as
+// written: no look at t_min / t_max, both roots rejected when |b| and sqrt(D4) are within 2500 ulps, the far root when the near one is
+// not beyond AT_MATH_EPSILON.  An accepted hit carries tri = -1 and its t in `a` (the hit record has no other slot for it).
+ATN_DEV bool sphere_test(const RaySlab& ray, const float4& q0, float t_min, Hit& hit, float& t_max, int32_t objid, int32_t meshid,
+                         bool& accept, float& t_out)
+{
+    const f3 p_o = mk3(q0) - ray.org;
+    const float b = dot(p_o, ray.dir);
+    const float D4 = (b * b - dot(p_o, p_o)) + q0.w * q0.w;
+    bool is_hit = false;
+    float t = kInf;                                                 // isect_tmp.t = INF
+    if (!(D4 < 0.0F)) {
+        const float sqrt_D4 = sqrtf(D4);
+        const float t1 = b - sqrt_D4, t2 = b + sqrt_D4;
+        // isClose(|b|, sqrt_D4, 2500 ulps), math/math.h:340-372 (the difference wraps, as the reference's does)
+        int32_t ai = __float_as_int(fabsf(b)), bi = __float_as_int(sqrt_D4);
+        if (ai < 0) ai = (int32_t)(0x80000000u - (uint32_t)ai);
+        if (bi < 0) bi = (int32_t)(0x80000000u - (uint32_t)bi);
+        const int32_t d = (int32_t)((uint32_t)ai - (uint32_t)bi);
+        const bool close = (d < 0 ? (int32_t)(0u - (uint32_t)d) : d) <= 2500;
+        if (t1 > kEps && !close) { t = t1; is_hit = true; }
+        else if (t2 > kEps && !close) { t = t2; is_hit = true; }
+    }
+    accept = (t_min < t) && is_hit && (t < hit.t);
+    if (accept) {
+        hit.t = t; hit.a = t; hit.b = 0.0F;
+        hit.objid = objid; hit.tri = -1; hit.meshid = meshid;
+        t_max = t;
+    }
+    t_out = t;
+    return is_hit;
+}
+
 // Job interface (all jobs of a launch share t_min):
 //   float t_min
 //   void fetch(uint32_t j, float4& a, float4& b, float& stop_t)   a = {org.xyz, t_max}, b = {dir.xyz, payload bits}
@@ -312,7 +346,9 @@ ATN_DEV void inner_burst(Walk& w, const char* __restrict__ nb, float t_min, Trav
 #ifndef ATN_TLAS_PERIOD
 #define ATN_TLAS_PERIOD 3
 #endif
-template <bool COUNT, int BURST, class Job, bool LDSN = false, bool DEFER = false>
+// SPH (spheres.hip only): the leaf step also serves the lanes on a sphere leaf (scene_dev.hpp: a link with both type bits) -- once per
+// burst, with the triangle leaves, not inside inner_burst.  SPH = false is the code as it was.
+template <bool COUNT, int BURST, class Job, bool LDSN = false, bool DEFER = false, bool SPH = false>
 ATN_DEV void walk_iteration(Walk& w, bool& all_finite, const DevScene& sc, const char* __restrict__ nb, float t_min,
                             const Job& job, TravCounters* cnt, uint32_t iter = 0)
 {
@@ -334,7 +370,17 @@ ATN_DEV void walk_iteration(Walk& w, bool& all_finite, const DevScene& sc, const
         if constexpr (LDSN) { q0 = ldn<true>(nb, off); q1 = ldn<true>(nb, off + 16u); }
         else { const __amdgpu_buffer_rsrc_t rs = node_rsrc(sc); q0 = ld16_buf(rs, off); q1 = ld16_buf(rs, off + 16u); }
         if (COUNT) { cnt->nodes++; cnt->ray_nodes++; }
-        if (w.node & kLinkLeafBit) {
+        bool at_sphere = false;
+        if constexpr (SPH) at_sphere = (w.node & kLinkTypeMask) == kLinkTypeMask;
+        if (at_sphere) {
+            // a sphere leaf stands in the top layer: the ray is the world ray, the record's one link is the next node
+            bool accept; float t;
+            is_hit = sphere_test(w.wray, q0, t_min, w.hit, w.t_max, __float_as_int(q1.x), __float_as_int(q1.z), accept, t);
+            w.node = __float_as_int(q1.w);
+            if (accept && t <= w.stop_t) w.node = kLinkEnd;         // see Job::fetch (top_hit / top_miss are kLinkEnd in the top layer)
+            ended = w.node == kLinkEnd;
+        }
+        else if (w.node & kLinkLeafBit) {
             float4 q2;
             if constexpr (LDSN) q2 = ldn<true>(nb, off + 32u);
             else q2 = ld16_buf(node_rsrc(sc), off + 32u);
@@ -482,7 +528,7 @@ ATN_DEV bool walk_finish(Walk& w, const DevScene& sc, const Job& job, TravCounte
 // into its dynamic LDS and the walk reads ALL records from there -- one source, so none of the per-lane selection that
 // sank the LDS treelet of the deep trees; a walk step waits for the LDS (~100 clocks) instead of the
 // L1 behind a queue of other waves' gathers, and the plain walk is latency-bound by construction.
-template <bool COUNT, class Job, bool LDSN = false>
+template <bool COUNT, class Job, bool LDSN = false, bool SPH = false>
 ATN_DEV void trace_simple(const DevScene& sc, uint32_t count, const Job& job, TravCounters* cnt)
 {
     const char* __restrict__ nb = reinterpret_cast<const char*>(sc.nodes);
@@ -508,7 +554,7 @@ ATN_DEV void trace_simple(const DevScene& sc, uint32_t count, const Job& job, Tr
             bool all_finite = __all(w.ray.finite) != 0;
             for (;;) {
                 while (__any(w.node != kLinkEnd))
-                    walk_iteration<COUNT, kSimpleBurstLds, Job, LDSN, true>(w, all_finite, sc, nb, t_min, job, cnt);
+                    walk_iteration<COUNT, kSimpleBurstLds, Job, LDSN, true, SPH>(w, all_finite, sc, nb, t_min, job, cnt);
                 if (!walk_finish<COUNT, Job, LDSN>(w, sc, job, cnt)) break;
                 all_finite = __all(w.node == kLinkEnd || w.ray.finite) != 0;    // (a shadow ray restarted behind an ignored surface)
             }
@@ -530,6 +576,13 @@ ATN_DEV void trace_simple(const DevScene& sc, uint32_t count, const Job& job, Tr
                                               : slab_hit_exact(w.ray, mk3(q0), mk3(q1), t_min, w.t_max);
                 w.node = __float_as_int(box ? q0.w : q1.w);
                 is_hit = false;
+            }
+            else if (SPH && (w.node & kLinkTypeMask) == kLinkTypeMask) {
+                // sphere leaf (top layer: w.ray is the world ray); see walk_iteration
+                bool accept; float t;
+                is_hit = sphere_test(w.wray, q0, t_min, w.hit, w.t_max, __float_as_int(q1.x), __float_as_int(q1.z), accept, t);
+                w.node = __float_as_int(q1.w);
+                if (accept && t <= w.stop_t) w.node = kLinkEnd;
             }
             else if (w.node & kLinkLeafBit) {
                 const float4 q2 = ldn<LDSN>(nb, off + 32u);
@@ -601,7 +654,7 @@ struct TraceShared {
 // (XCD-affine job lists -- rays filed by the cell of their origin, a block draining its own XCD's list first -- were built and
 // measured in r04: L2 hit 0.79 -> 0.85 and fabric reads -41 % on the 250 K-triangle atrium, and the launch no faster.
 // profiles/r04_variants_ray_cells.txt; code in git history, commit "Ray cells".)
-template <bool COUNT, class Job, bool LDSN = false>
+template <bool COUNT, class Job, bool LDSN = false, bool SPH = false>
 ATN_DEV void trace_refill(const DevScene& sc, TraceShared& sh, uint32_t count, uint32_t* fetch_counter,
                           const Job& job, TravCounters* cnt)
 {
@@ -681,7 +734,7 @@ ATN_DEV void trace_refill(const DevScene& sc, TraceShared& sh, uint32_t count, u
                 break;          // drained, chunk empty, nothing in flight
             }
         }
-        walk_iteration<COUNT, kInnerBurst, Job, LDSN, ATN_DEFER_FINISH != 0>(w, all_finite, sc, nb, t_min, job, cnt, iter++);
+        walk_iteration<COUNT, kInnerBurst, Job, LDSN, ATN_DEFER_FINISH != 0, SPH>(w, all_finite, sc, nb, t_min, job, cnt, iter++);
     }
 }
 

@@ -255,6 +255,8 @@ public:
         // the refusals shard 0 would make, before any shard has moved
         int rc = r0.check_ready(d);
         if (rc) return fail(rc, "shard 0: " + r0.last_error);
+        for (int i = 0; i < n; i++)
+            if (shard[i]->n_sphere_leaves) { const int sr = shard[i]->sph_refuse("the SVGF renderer does not trace sphere leaves"); return fail(sr, "shard " + std::to_string(i) + ": " + shard[i]->last_error); }
         if (compute_motion == 2)
             return fail(ATN_ERR_UNSUPPORTED, "atn_mgpu_svgf_render: compute_motion = 2 is not supported: the geometry history (previous positions of the "
                                              "deforming meshes, per-pixel primary hit ids) has no node-wide form yet; use compute_motion = 1 or atn_svgf_render");

@@ -57,6 +57,7 @@ struct HostSceneImage {
     DevScene params{};                  // scalar fields filled; pointers left null
     SceneSource source;                 // the caller's editable data (the context keeps it for atn_update_*)
     uint64_t n_inner = 0, n_tri_leaf = 0, n_tlas_leaf = 0;
+    uint32_t n_sphere_leaf = 0;         // top-layer leaves the sphere-aware walks test (sphere_mode 1 only)
 };
 
 inline float i2f(int32_t i) { float f; std::memcpy(&f, &i, 4); return f; }
@@ -80,9 +81,23 @@ inline bool walk_order(const atn_bvh_node* nodes, uint32_t count, std::vector<in
     return true;
 }
 
-enum NodeKind : uint8_t { KIND_INNER = 0, KIND_TRI = 1, KIND_TLAS = 2, KIND_DEAD = 3 };
+enum NodeKind : uint8_t { KIND_INNER = 0, KIND_TRI = 1, KIND_TLAS = 2, KIND_DEAD = 3, KIND_SPHERE = 4 };
 inline uint32_t record_bytes(uint8_t kind) { return kind == KIND_TRI ? kTriLeafBytes : kInnerBytes; }
-inline int32_t kind_type_bits(uint8_t kind) { return kind == KIND_TRI ? kLinkToLeaf : (kind == KIND_TLAS ? kLinkToTlas : 0); }
+inline int32_t kind_type_bits(uint8_t kind) { return kind == KIND_TRI ? kLinkToLeaf : (kind == KIND_TLAS ? kLinkToTlas : (kind == KIND_SPHERE ? kLinkToSphere : 0)); }
+
+// Which leaves without triangle or nested tree become KIND_SPHERE (atn_set_sphere_intersection, docs/SPHERES.md).  mode 0: none, they are
+// dead leaves as ever.  mode 1: every such leaf has to be a top-layer leaf of an ATN_OBJ_SPHERE object (not an instance of one) with one
+// link; anything else refuses the upload.
+struct SphereLeafRule { int mode = 0; const atn_object_param* objects = nullptr; uint32_t n_objects = 0; };
+// The material ids of the sphere objects, which the sphere-aware kernels index the materials with: negative = the white-diffuse
+// fallback (as a triangle's), otherwise below n_materials.  Checked by the upload and by the top-layer update wherever sphere leaves
+// were written.
+inline bool sphere_materials_ok(const atn_object_param* objs, uint32_t n_objs, uint32_t n_materials, std::string& err)
+{
+    for (uint32_t i = 0; i < n_objs; i++)
+        if (objs[i].type == ATN_OBJ_SPHERE && objs[i].sphere.mtrl_id >= 0 && (uint32_t)objs[i].sphere.mtrl_id >= n_materials) { err = "sphere material id out of range"; return false; }
+    return true;
+}
 
 // One threaded list analysed: walk order, node kinds, depth of every node, and (filled by the layout pass) the byte
 // offset of every node's device record.
@@ -95,7 +110,7 @@ struct ListLayout {
 };
 
 // Validates a list (reachability, forward links, the structural rules the walk relies on) and fills order/kind/depth.
-inline bool analyse_list(ListLayout& L, const atn_bvh_node* src, uint32_t count, bool top, std::string& err)
+inline bool analyse_list(ListLayout& L, const atn_bvh_node* src, uint32_t count, bool top, std::string& err, const SphereLeafRule& sph = SphereLeafRule{})
 {
     if (!walk_order(src, count, L.new_index, L.order, err)) return false;
     const uint32_t n = (uint32_t)L.order.size();
@@ -125,6 +140,16 @@ inline bool analyse_list(ListLayout& L, const atn_bvh_node* src, uint32_t count,
         else if (nd.f1 >= 0) {
             if ((int32_t)nd.hit != (int32_t)nd.miss) { err = "triangle leaf with hit != miss link"; return false; }
             kind = KIND_TRI;
+        }
+        else if (sph.mode == 1) {
+            // f1 < 0 && f2 < 0: the leaf the reference's stackless walk tests with sphere::hit
+            const std::string where = "sphere intersection: leaf " + std::to_string(L.order[j]) + (top ? " of the top layer" : " of a bottom-level list");
+            const int32_t objid = (int32_t)nd.f0;
+            if (!top) { err = where + " is not in the top layer"; return false; }
+            if (objid < 0 || (uint32_t)objid >= sph.n_objects || !sph.objects) { err = where + " names an object id out of range"; return false; }
+            if (sph.objects[objid].type != ATN_OBJ_SPHERE) { err = where + " names object " + std::to_string(objid) + ", which is not of type ATN_OBJ_SPHERE (instances of spheres are not traced)"; return false; }
+            if ((int32_t)nd.hit != (int32_t)nd.miss) { err = where + " has hit != miss link"; return false; }
+            kind = KIND_SPHERE;
         }
         else kind = KIND_DEAD;      // leaf without triangle or nested tree (sphere instance): never tested on this path
         L.kind[j] = kind;
@@ -169,6 +194,7 @@ struct ListEmitCtx {
     std::vector<HostSceneImage::TlasRef>* tlas_refs = nullptr;     // out (optional)
     const atn_mat4* matrices = nullptr;     // the matrices the TLAS leaves' rows index (null: identity instances are not recognised)
     mutable int32_t ident_row = -1;         // out: w2l_row of an instance whose W2L is bit for bit the identity
+    mutable uint32_t n_sphere_leaf = 0;     // out: KIND_SPHERE records written
 };
 
 // mat4 == identity, bit for bit (+0.0 zeros): applying it is the same arithmetic for every instance that has it
@@ -228,6 +254,15 @@ inline bool emit_list(char* img, const ListLayout& L, const atn_bvh_node* src, c
             q[0] = make_float4(0, 0, 0, i2f(m));
             q[1] = make_float4(0, 0, 0, i2f(m));
             break;
+        case KIND_SPHERE: {     // (analyse_list checked the object id and type, and hit == miss)
+            const int32_t objid = (int32_t)nd.f0;
+            if (objid < 0 || (uint32_t)objid >= c.n_objects) { err = "sphere leaf object id out of range"; return false; }
+            const atn_object_param& obj = c.objects[objid];
+            q[0] = make_float4(obj.sphere.center[0], obj.sphere.center[1], obj.sphere.center[2], obj.sphere.radius);
+            q[1] = make_float4(i2f(objid), i2f(obj.sphere.mtrl_id), i2f((int32_t)nd.f3), i2f(h));
+            c.n_sphere_leaf++;
+            break;
+        }
         case KIND_TLAS: {
             // nested tree (exid bit-field, threaded_bvh.h:29-37)
             const int32_t objid = (int32_t)nd.f0;
@@ -633,7 +668,8 @@ inline int32_t encode_texels8(const atn_texture_desc& t, std::vector<uint32_t>& 
 }
 
 inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::string& err, int anyhit_twins = 0, int twin_dirs = 8,
-                             int node_layout_top_levels = kLayoutTopLevels, bool planar_lights = true, uint64_t twin_budget_bytes = kTwinBudgetBytes)
+                             int node_layout_top_levels = kLayoutTopLevels, bool planar_lights = true, uint64_t twin_budget_bytes = kTwinBudgetBytes,
+                             int sphere_mode = 0)
 {
     if (!s || s->n_bvh_lists == 0 || !s->bvh_lists) { err = "scene has no BVH lists"; return false; }
     const uint32_t nl = s->n_bvh_lists;
@@ -648,7 +684,7 @@ inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::
     std::vector<std::vector<std::vector<atn_bvh_node>>> twin(nl);    // the any-hit twin(s) of list k as threaded lists of their own (empty: none)
     uint64_t total_nodes = 0;
     for (uint32_t k = 0; k < nl; k++) {
-        if (!analyse_list(lay[k], s->bvh_lists[k].nodes, s->bvh_lists[k].count, k == 0, err)) return false;
+        if (!analyse_list(lay[k], s->bvh_lists[k].nodes, s->bvh_lists[k].count, k == 0, err, SphereLeafRule{ sphere_mode, s->objects, s->n_objects })) return false;
         total_nodes += lay[k].order.size();
         if (k == 0 || !anyhit_twins || lay[k].order.size() != s->bvh_lists[k].count) continue;
         AnyhitTwin tw;
@@ -728,6 +764,8 @@ inline bool build_host_image(HostSceneImage& img, const atn_scene_desc* s, std::
     img.n_inner = counts[0]; img.n_tri_leaf = counts[1]; img.n_tlas_leaf = counts[2];
     img.params.node_bytes = (uint32_t)off;
     img.params.ident_row = c.ident_row;
+    img.n_sphere_leaf = c.n_sphere_leaf;
+    if (img.n_sphere_leaf && !sphere_materials_ok(s->objects, s->n_objects, s->n_materials, err)) return false;
 
     // ---- plain copies
     img.tris.assign(s->triangles, s->triangles + s->n_triangles);

@@ -259,6 +259,17 @@ class PathTracing:
         v = lambda x: -1 if x is None else int(x)
         self._check(self._l.atn_set_upload_options(self._ctx, v(anyhit_twin), v(anyhit_twin_dirs), v(node_layout), v(planar_lights)))
 
+    def set_sphere_intersection(self, mode):
+        """Analytic spheres (docs/SPHERES.md): 0 (default) a sphere object's top-layer leaf is never tested, as in the CPU tracer; 1 the
+        next UpdateSceneData / update_tlas makes such leaves records every ray tests with sphere::hit."""
+        self._check(self._l.atn_set_sphere_intersection(self._ctx, int(mode)))
+
+    def sphere_leaves(self):
+        """How many top-layer leaves of the uploaded scene are tested as spheres (0 in mode 0)."""
+        n = C.c_uint32(0)
+        self._check(self._l.atn_sphere_leaves(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def set_shade_math(self, relaxed):
         """False (default): the parity path; True: the shade kernel under the reference GPU build's --use_fast_math rules (opt-in)."""
         self._check(self._l.atn_set_shade_math(self._ctx, int(relaxed)))
@@ -1022,6 +1033,10 @@ class MultiGpuPathTracing:
 
     def set_regeneration(self, on):
         self._check(self._l.atn_mgpu_set_regeneration(self._mg, int(on)))
+
+    def set_sphere_intersection(self, mode):
+        """PathTracing.set_sphere_intersection on every shard (read by the next upload)."""
+        self._check(self._l.atn_mgpu_set_sphere_intersection(self._mg, int(mode)))
 
     def render_burst(self, width, height, n_frames, max_depth=5, rr_depth=3, spp=1, frame=0, progressive=True,
                      break_on_terminate=True, download=True):

@@ -78,6 +78,17 @@ int atn_update_tlas(atn_ctx* ctx, const atn_object_param* objects, uint32_t n_ob
  * Films do not depend on any of them (tests/test_gpu_anyhit_twin.py). */
 int atn_set_upload_options(atn_ctx* ctx, int32_t anyhit_twin, int32_t anyhit_twin_dirs, int32_t node_layout, int32_t planar_lights);
 
+/* Analytic spheres in the walk (docs/SPHERES.md).  Context state with the lifetime of the upload options above: read by the next
+ * atn_upload_scene / atn_update_tlas.
+ *   mode 0 (default)  a top-layer leaf of an ATN_OBJ_SPHERE object is never tested, as in aten::ThreadedBvhTraverser: the sphere can
+ *                     be sampled as a light and is invisible to every ray
+ *   mode 1            such leaves are tested with sphere::hit by every ray of atn_render, atn_trace_closest and atn_trace_shadow; a leaf
+ *                     without triangle and nested tree that is anything else refuses the upload (ATN_ERR_UNSUPPORTED)
+ * atn_sphere_leaves: how many leaves of the uploaded scene are tested (0 in mode 0).  While it is above 0 the other renderers, path
+ * regeneration and bursts, relaxed shade math, deferred NEE, atn_tlas_rebuild, atn_shade_stage and geometry motion are refused. */
+int atn_set_sphere_intersection(atn_ctx* ctx, int32_t mode);
+int atn_sphere_leaves(atn_ctx* ctx, uint32_t* n);
+
 /* ≙ idaten::Renderer::updateCamera (renderer.cpp:202-205). */
 int atn_update_camera(atn_ctx* ctx, const atn_camera_param* camera);
 
@@ -415,6 +426,8 @@ int atn_mgpu_set_frames_in_flight(atn_mgpu* mg, int32_t n);
 /* atn_set_regeneration on every shard; atn_render_burst on every shard followed by ONE exchange of the tiles (a progressive film is
  * looked at after the burst: its tiles travel once per burst, not once per frame). */
 int atn_mgpu_set_regeneration(atn_mgpu* mg, int32_t mode);
+/* atn_set_sphere_intersection on every shard (read by the next atn_mgpu_upload_scene / atn_mgpu_update_tlas) */
+int atn_mgpu_set_sphere_intersection(atn_mgpu* mg, int32_t mode);
 int atn_mgpu_render_burst(atn_mgpu* mg, const atn_destination* dst, int32_t n_frames, atn_vec4* out_host);
 /* Node-wide SVGF (docs/MGPU_SVGF.md): atn_svgf_render (below) with the path pass -- most of the frame -- spread over the shards.  Every
  * shard runs the path pass on its tiles; shards 1 .. N-1 pack their pixels of the four planes the path pass hands to the filters

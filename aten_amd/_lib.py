@@ -23,7 +23,7 @@ SYMBOLS = [
     "atn_svgf_download", "atn_svgf_output_device", "atn_svgf_set_dilate_temporal_weight", "atn_svgf_denoise", "atn_svgf_upload",
     "atn_restir_set_options", "atn_restir_render", "atn_restir_set_motion_depth", "atn_restir_reset", "atn_restir_capture",
     "atn_restir_download", "atn_npr_render", "atn_npr_reset", "atn_npr_capture", "atn_npr_download", "atn_npr_set_skip_through", "atn_npr_advance_download",
-    "atn_volume_render", "atn_volume_reset", "atn_volume_capture", "atn_volume_download", "atn_volume_phase_table",
+    "atn_volume_set_grids", "atn_volume_render", "atn_volume_reset", "atn_volume_capture", "atn_volume_download", "atn_volume_phase_table",
     "atn_ao_set_params", "atn_ao_render", "atn_ao_reset", "atn_ao_capture", "atn_ao_download",
     "atn_npr_shadow_set_mode", "atn_npr_shadow_download", "atn_npr_shadow_filter",
     "atn_npr_hatching_set", "atn_npr_hatching_get", "atn_npr_hatching_filter", "atn_npr_hatching_download",
@@ -148,6 +148,7 @@ def lib():
         l.atn_npr_download.argtypes = [vp, C.c_int32, vp]
         l.atn_npr_set_skip_through.argtypes = [vp, C.c_int32]
         l.atn_npr_advance_download.argtypes = [vp, vp]
+        l.atn_volume_set_grids.argtypes = [vp, vp, C.c_uint32]
         l.atn_volume_render.argtypes = [vp, vp, vp]
         l.atn_volume_reset.argtypes = [vp]
         l.atn_volume_capture.argtypes = [vp, C.c_int32]

@@ -99,7 +99,7 @@ def build_host(force=False):
     return HOST_LIB
 
 
-# libaten_amd.so is sixteen translation units; all but two share ONE flag (device/svgf_atrous.hpp says why):
+# libaten_amd.so is seventeen translation units; all but two share ONE flag (device/svgf_atrous.hpp says why):
 #   aten_amd.hip      -fno-slp-vectorize  (no packed-fp32 pairing: the path-tracing kernels lose 15-25 % of their registers to it)
 #   svgf_atrous.hip   vectoriser on       (straight-line tap arithmetic, 22 % faster packed)
 #   regen.hip         -fno-slp-vectorize  (the path-regeneration kernels: same sources and flags as aten_amd.hip's, compiled beside them)
@@ -116,11 +116,13 @@ def build_host(force=False):
 #   taa.hip           -fno-slp-vectorize  (the display tail: temporal anti-aliasing, the history write and the gamma / RGBA8 epilogue, device/taa.hpp)
 #   npr_advance.hip   -fno-slp-vectorize  (the NPR look-through: its walk, and k_shade's alpha-blend flavour, device/npr_advance.hpp)
 #   spheres.hip       -fno-slp-vectorize  (analytic spheres: the sphere-aware walks and shade launches of a scene with sphere leaves, device/spheres.hpp)
+#   volume_grid.hip   -fno-slp-vectorize  (grid media: the GRID flavours of the volume shade kernel and connection walk, device/volume_grid.hpp)
 #   shade_relaxed.hip  k_shade with the reference GPU build's --use_fast_math rules (opt-in, atn_set_shade_math): contraction, approximate
 #                      division / sqrt, flushed denormals (the unit itself redirects sinf / cosf / expf / logf / powf to the hardware forms)
 RELAXED_FLAGS = ["-fno-slp-vectorize", "-ffp-contract=fast", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero"]
 HIP_UNITS = [("aten_amd.hip", ["-fno-slp-vectorize"]), ("regen.hip", ["-fno-slp-vectorize"]), ("restir.hip", ["-fno-slp-vectorize"]), ("npr.hip", ["-fno-slp-vectorize"]), ("volume.hip", ["-fno-slp-vectorize"]), ("ao.hip", ["-fno-slp-vectorize"]), ("npr_shadow.hip", ["-fno-slp-vectorize"]), ("npr_hatching.hip", ["-fno-slp-vectorize"]), ("skinning.hip", ["-fno-slp-vectorize"]), ("motion.hip", ["-fno-slp-vectorize"]), ("taa.hip", ["-fno-slp-vectorize"]), ("shade_relaxed.hip", RELAXED_FLAGS), ("svgf_atrous.hip", []),
-             ("tlas.hip", ["-fno-slp-vectorize"]), ("npr_advance.hip", ["-fno-slp-vectorize"]), ("spheres.hip", ["-fno-slp-vectorize"])]      # (new units go last: the units in front keep their places in the library)
+             ("tlas.hip", ["-fno-slp-vectorize"]), ("npr_advance.hip", ["-fno-slp-vectorize"]), ("spheres.hip", ["-fno-slp-vectorize"]),
+             ("volume_grid.hip", ["-fno-slp-vectorize"])]      # (new units go last: the units in front keep their places in the library)
 
 
 def hip_compile(out_lib, extra_flags=(), objdir=None, hipcc=None):

@@ -958,6 +958,7 @@ public:
         for (size_t i = 0; i < img.lights.size(); i++) light_planar[i] = img.lights[i]._pad != 0 ? 1 : 0;
         host_textures = img.textures; n_texels_used = img.texels.size();
         { const int nrc = npr_decode(img.materials); if (nrc) return nrc; }
+        vl_grids.clear();       // (an upload drops the grids of atn_volume_set_grids; the material edits keep them)
         { const int vrc = vol_decode(img.materials); if (vrc) return vrc; }
         {
             const int32_t ei = s->config.bg.envmap_tex_idx;
@@ -3435,6 +3436,95 @@ public:
     int32_t vl_w = 0, vl_h = 0, vl_capture = -1, vl_captured = -1;
     bool vl_rendered = false;
     FrameFence vl_fence;        // the last volume frame's kernels are done with the per-slot state (the next frame waits for it)
+    // Grid media (atn_volume_set_grids; device/volume_grid.hpp): dense float grids a medium material names by grid_idx.  They outlive
+    // atn_update_*; atn_upload_scene drops them.  What is wrong with a grid, or with a material that names one, is kept as a
+    // message and refused by atn_volume_render.
+    struct VolGridHost {
+        int32_t dim[3] = { 0, 0, 0 };
+        float max_density = 0.0F, diagonal = 0.0F;
+        std::string bad;            // why the grid cannot be traced ("" = it can)
+        DevBuf<float> density;
+    };
+    std::vector<VolGridHost> vl_grids;
+    std::vector<VolMedium> vl_med_host;     // what vol_decode made of the materials, before the grids are bound
+    DevBuf<atn_vg::Grid> vl_grid_desc;
+    DevBuf<uint4> vl_c_smp;
+    std::string vl_grid_refuse;     // why a material's grid medium cannot be rendered ("" = it can, or no material names a grid)
+    bool vl_use_grid = false;       // a material names a valid grid: the frame launches the GRID flavours
+
+    // Marks the media that name a grid (kVolGridFlag, the grid's index, the majorant in sigma_t) and uploads the medium records.
+    // Runs where nothing is in flight: behind vol_decode and in volume_set_grids.
+    int vol_bind_grids()
+    {
+        std::vector<VolMedium> med = vl_med_host;
+        vl_grid_refuse.clear();
+        vl_use_grid = false;
+        const size_t nm = med.empty() ? 0 : med.size() - 1;
+        for (size_t i = 0; i < nm && i < src.materials.size(); i++) {
+            const atn_material_param& m = src.materials[i];
+            if (!m.is_medium) continue;
+            atn_medium_param mp;
+            std::memcpy(&mp, m.medium, sizeof(mp));
+            if (mp.grid_idx < 0) continue;
+            const std::string who = "material " + std::to_string(i) + " is a heterogeneous medium (grid_idx " + std::to_string(mp.grid_idx) + "): ";
+            std::string why;
+            if ((size_t)mp.grid_idx >= vl_grids.size())
+                why = "atn_volume_set_grids has set " + std::to_string(vl_grids.size()) + " grids";
+            else {
+                const VolGridHost& g = vl_grids[(size_t)mp.grid_idx];
+                if (!g.bad.empty()) why = "its grid has " + g.bad;
+                else if (mp.sigma_a != 0.0F) why = "a grid medium needs sigma_a == 0 (only scattering is tracked)";
+                else if (!std::isfinite(mp.majorant) || !(mp.majorant > 0.0F)) why = "its majorant is not a finite value > 0";
+                else if (mp.majorant < mp.sigma_s * g.max_density) why = "its majorant is below sigma_s * max density (a scattering probability would exceed 1)";
+                else if (mp.majorant * g.diagonal > atn_vg::kVolGridStepsBound) why = "majorant * box diagonal > 1024 expected tracking steps across the grid";
+            }
+            if (!why.empty()) { if (vl_grid_refuse.empty()) vl_grid_refuse = who + why; continue; }
+            med[i].flags |= kVolGridFlag | ((uint32_t)mp.grid_idx << kVolGridShift);
+            med[i].sigma_t = mp.majorant;
+            vl_use_grid = true;
+        }
+        if (!vl_grid_refuse.empty()) vl_use_grid = false;
+        if (!med.empty()) { ATN_HIP(vl_med.upload(med, stream)); ATN_HIP(hipStreamSynchronize(stream)); }      // (`med` is pageable host memory)
+        return ATN_OK;
+    }
+
+    int volume_set_grids(const atn_volume_grid* grids, uint32_t n)
+    {
+        if (n && !grids) return fail(ATN_ERR_INVALID_ARG, "null grid array");
+        if (n > (1u << 16)) return fail(ATN_ERR_INVALID_ARG, "more than 65536 grids");
+        for (uint32_t i = 0; i < n; i++) if (!grids[i].density) return fail(ATN_ERR_INVALID_ARG, "a grid without densities");
+        ATN_HIP(hipSetDevice(device));
+        { int q = quiesce(); if (q) return q; }
+        std::vector<VolGridHost> next(n);
+        std::vector<atn_vg::Grid> desc(n, atn_vg::Grid{});
+        for (uint32_t i = 0; i < n; i++) {
+            const atn_volume_grid& g = grids[i];
+            VolGridHost& h = next[i];
+            for (int k = 0; k < 3; k++) h.dim[k] = g.dim[k];
+            if (g.dim[0] <= 0 || g.dim[1] <= 0 || g.dim[2] <= 0) { h.bad = "a dim component <= 0"; continue; }
+            if (!std::isfinite(g.voxel_size) || !(g.voxel_size > 0.0F)) { h.bad = "a voxel_size that is not a finite value > 0"; continue; }
+            const uint64_t cells = (uint64_t)g.dim[0] * (uint64_t)g.dim[1] * (uint64_t)g.dim[2];
+            if (cells > (1ull << 30)) { h.bad = "more than 2^30 voxels"; continue; }
+            float mx = 0.0F;
+            for (uint64_t c = 0; c < cells && h.bad.empty(); c++) {
+                const float d = g.density[c];
+                if (!std::isfinite(d)) h.bad = "a density that is not finite";
+                else if (d < 0.0F) h.bad = "a density < 0";
+                else if (d > mx) mx = d;
+            }
+            if (!h.bad.empty()) continue;
+            h.max_density = mx;
+            const double ex = (double)g.dim[0] * g.voxel_size, ey = (double)g.dim[1] * g.voxel_size, ez = (double)g.dim[2] * g.voxel_size;
+            h.diagonal = (float)std::sqrt(ex * ex + ey * ey + ez * ez);
+            ATN_HIP(h.density.resize((size_t)cells));
+            ATN_HIP(hipMemcpy(h.density.p, g.density, (size_t)cells * sizeof(float), hipMemcpyHostToDevice));
+            desc[i] = atn_vg::make_grid(h.density.p, g.dim, g.origin, g.voxel_size);
+        }
+        vl_grids = std::move(next);
+        ATN_HIP(vl_grid_desc.upload(desc, stream));
+        ATN_HIP(hipStreamSynchronize(stream));
+        return vol_bind_grids();
+    }
 
     int vol_decode(const std::vector<DevMaterial>& mats)
     {
@@ -3457,15 +3547,14 @@ public:
             v.le[0] = mp.le[0]; v.le[1] = mp.le[1]; v.le[2] = mp.le[2];
             v.sigma_t = mp.sigma_a + mp.sigma_s;
             if (!vl_refuse.empty()) continue;
-            if (mp.grid_idx >= 0) vl_refuse = "material " + std::to_string(i) + " is a heterogeneous medium (grid_idx >= 0): NanoVDB grids are not supported";
-            else if (!(mp.sigma_a + mp.sigma_s > 0.0F)) vl_refuse = "material " + std::to_string(i) + " is a medium with sigma_a + sigma_s <= 0";
+            if (!(mp.sigma_a + mp.sigma_s > 0.0F)) vl_refuse = "material " + std::to_string(i) + " is a medium with sigma_a + sigma_s <= 0";
             else if ((uint32_t)m.id != i) vl_refuse = "material " + std::to_string(i) + " is a medium whose id is not its index (the medium stack holds material ids)";
         }
         for (const DevMaterial& dm : mats) if (dm.attrib & kAttrMaybeAlpha) any_maybe_alpha = true;
         vl_alpha = src.config.enable_alpha_blending != 0 && any_maybe_alpha;
         vl_eps_bias = src.config.epsilon_bias_for_traversing_shadow_ray_in_medium;
-        ATN_HIP(vl_med.upload(med, stream));
-        return ATN_OK;
+        vl_med_host = std::move(med);
+        return vol_bind_grids();       // (a medium with grid_idx >= 0: its grid is looked up, or the frame is refused)
     }
 
     int vol_ensure(int32_t w, int32_t h)
@@ -3475,6 +3564,7 @@ public:
         ATN_HIP(vl_c_o.resize(ns)); ATN_HIP(vl_c_d.resize(ns)); ATN_HIP(vl_c_w.resize(ns)); ATN_HIP(vl_c_a.resize(ns)); ATN_HIP(vl_c_b.resize(ns));
         ATN_HIP(vl_c_c.resize(ns)); ATN_HIP(vl_c_stack.resize(ns)); ATN_HIP(vl_conn_q.resize(ns)); ATN_HIP(vl_segs.resize(ns));
         ATN_HIP(vl_counters.resize(kVolCounters));
+        if (!vl_grids.empty()) ATN_HIP(vl_c_smp.resize(ns));
         if (vl_capture >= 0) {
             const size_t n = (size_t)w * h;
             ATN_HIP(vl_st_state.resize(n)); ATN_HIP(vl_st_stack.resize(n)); ATN_HIP(vl_st_ray.resize(2 * n)); ATN_HIP(vl_st_conn.resize(3 * n));
@@ -3490,6 +3580,7 @@ public:
         { const int sr = sph_refuse("the volume renderer does not trace sphere leaves"); if (sr) return sr; }
         int rc = check_ready(d);
         if (rc) return rc;
+        if (!vl_grid_refuse.empty()) return fail(ATN_ERR_UNSUPPORTED, ("volume frames: " + vl_grid_refuse).c_str());
         if (!vl_refuse.empty()) return fail(ATN_ERR_UNSUPPORTED, ("volume frames: " + vl_refuse).c_str());
         if (vl_stencil) return fail(ATN_ERR_UNSUPPORTED, "volume frames do not skip through StencilType::STENCIL materials");
         if (vl_alpha) return fail(ATN_ERR_UNSUPPORTED, "volume frames do not skip through translucent-by-alpha surfaces: alpha blending is on and a material's alpha may be < 1");
@@ -3515,6 +3606,8 @@ public:
         va.c_o = vl_c_o.p; va.c_d = vl_c_d.p; va.c_w = vl_c_w.p; va.c_a = vl_c_a.p; va.c_b = vl_c_b.p; va.c_c = vl_c_c.p; va.c_stack = vl_c_stack.p;
         va.conn_q = vl_conn_q.p; va.segs = vl_segs.p; va.counters = vl_counters.p; va.eps_bias = vl_eps_bias;
         va.capture = vl_capture;
+        const bool grid = vl_use_grid;      // a material names a grid: the GRID flavours of the shade kernel and the connection walk
+        const VolGridArgs vg{ vl_grid_desc.p, vl_c_smp.p };
         if (vl_capture >= 0) { va.st_state = vl_st_state.p; va.st_stack = vl_st_stack.p; va.st_ray = vl_st_ray.p; va.st_conn = vl_st_conn.p; }
         // the iteration's queue counters are the volume renderer's own (9 entries: the frame's are sized by maxDepth)
         pb.q_count = vl_counters.p + kVolCntQueue;
@@ -3540,10 +3633,12 @@ public:
                 vol_launch_closest(vlc, stream, pb, scene, va, it);
                 prof_end(prof);
                 prof_begin(prof, ATN_K_SHADE);
-                vol_launch_shade(scene.material_set, vlc, stream, pb, scene, fp, camera, va, it);
+                if (grid) vol_launch_shade_grid(scene.material_set, vlc, stream, pb, scene, fp, camera, va, vg, it);
+                else vol_launch_shade(scene.material_set, vlc, stream, pb, scene, fp, camera, va, it);
                 prof_end(prof);
                 prof_begin(prof, ATN_K_TRACE_FUSED);
-                vol_launch_transmit(vlc, stream, pb, scene, va, it);
+                if (grid) vol_launch_transmit_grid(vlc, stream, pb, scene, va, vg, it);
+                else vol_launch_transmit(vlc, stream, pb, scene, va, it);
                 prof_end(prof);
             }
             if (d->sample > 1) {
@@ -3572,10 +3667,11 @@ public:
     {
         if (!out) return fail(ATN_ERR_INVALID_ARG, "null output");
         if (!vl_rendered) return fail(ATN_ERR_INVALID_ARG, "no volume frame has been rendered");
-        if (which != 4 && vl_captured < 0) return fail(ATN_ERR_INVALID_ARG, "the last volume frame kept no stage buffers: atn_volume_capture(ctx, iteration) before the frame");
+        if (which != 4 && which != 5 && vl_captured < 0) return fail(ATN_ERR_INVALID_ARG, "the last volume frame kept no stage buffers: atn_volume_capture(ctx, iteration) before the frame");
         const size_t n = (size_t)vl_w * vl_h;
         const StageBuf bufs[] = { { vl_st_state.p, n * sizeof(uint4) }, { vl_st_stack.p, n * sizeof(uint4) }, { vl_st_ray.p, 2 * n * sizeof(float4) },
-                                  { vl_st_conn.p, 3 * n * sizeof(float4) }, { vl_counters.p + kVolCntFrame, 4 * sizeof(uint32_t) } };
+                                  { vl_st_conn.p, 3 * n * sizeof(float4) }, { vl_counters.p + kVolCntFrame, 4 * sizeof(uint32_t) },
+                                  { vl_counters.p + kVolCntFrame + 4, 2 * sizeof(uint32_t) } };
         return download_stage(bufs, which, out, "no such volume buffer");
     }
 
@@ -4409,6 +4505,11 @@ int atn_volume_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_ho
 {
     CTX_OR_FAIL(ctx);
     return guarded(ctx, [&] { return ctx->r.volume_render(dst, out_host); });
+}
+int atn_volume_set_grids(atn_ctx* ctx, const atn_volume_grid* grids, uint32_t n)
+{
+    CTX_QUIET_OR_FAIL(ctx);
+    return guarded(ctx, [&] { return ctx->r.volume_set_grids(grids, n); });
 }
 int atn_volume_reset(atn_ctx* ctx) { CTX_QUIET_OR_FAIL(ctx); return guarded(ctx, [&] { return ctx->r.volume_reset(); }); }
 int atn_volume_capture(atn_ctx* ctx, int32_t iteration)

@@ -220,6 +220,11 @@ void vol_launch_shade(int material_set, const RayLaunch& l, hipStream_t st, cons
 void vol_launch_transmit(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, int32_t it);
 void vol_launch_reduce(const RayLaunch& l, hipStream_t st, const FrameParams& fp, const VolArgs& va);
 void vol_launch_phase_table(hipStream_t st, float g, uint32_t n, const float* w, const float* r1, const float* r2, const float* wo, float* out_dir, float* out_eval);
+// ---- volume_grid.hip (device/volume_grid.hpp): the shade and connection launches of a frame whose media name a grid ----
+struct VolGridArgs;
+void vol_launch_shade_grid(int material_set, const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const FrameParams& fp,
+                           const atn_camera_param& cam, const VolArgs& va, const VolGridArgs& vg, int32_t it);
+void vol_launch_transmit_grid(const RayLaunch& l, hipStream_t st, const PathBuffers& pb, const DevScene& sc, const VolArgs& va, const VolGridArgs& vg, int32_t it);
 
 // ---- skinning.hip (device/skinning.hpp) ----
 struct SkinVtxArgs;

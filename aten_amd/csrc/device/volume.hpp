@@ -16,14 +16,19 @@
 //   c_*     the connection record: see ConnRecord below                                              112 B per path
 #pragma once
 #include "kernels.hpp"
+#include "volume_grid_track.h"
 
 namespace atn {
 
 constexpr int kVolIterations = 8;           // MedisumStackSize, pt_params.h:22
 constexpr uint32_t kVolWalkMax = 64u;       // boundaries a connection may cross before it counts as blocked
 constexpr uint32_t kVolMediumFlag = 1u, kVolPureFlag = 2u;      // VolMedium::flags: is_medium, type == MaterialType::Volume
+// a medium that names a grid (atn_volume_set_grids): its index in flags >> kVolGridShift, and VolMedium::sigma_t holds its MAJORANT.
+// Only the GRID flavours of the kernels (volume_grid.hip) meet one: a frame launches them when a material names a valid grid.
+constexpr uint32_t kVolGridFlag = 4u, kVolGridShift = 8u;
 // counters (uint32): [0, 9) live paths entering iteration i; [16, 24) connections of iteration i; [32, 41) fetch cursors of the
-// closest-hit walks; [48, 56) of the connection walks; 64 stack overflows, 65 walk overflows, 66 connections, 67 segments (frame)
+// closest-hit walks; [48, 56) of the connection walks; 64 stack overflows, 65 walk overflows, 66 connections, 67 segments (frame);
+// 68 grid flights, 69 grid connections stopped at kVolGridStepsMax (frame; device/volume_grid.hpp)
 constexpr int kVolCntQueue = 0, kVolCntConn = 16, kVolCntFetchC = 32, kVolCntFetchT = 48, kVolCntFrame = 64, kVolCounters = 80;
 // stage flags (atn_volume_download, which = 0)
 constexpr uint32_t kVolProcessed = 1u, kVolHit = 2u, kVolSampled = 4u, kVolAbsorbed = 8u, kVolScattered = 16u, kVolPassed = 32u,
@@ -49,7 +54,13 @@ struct VolArgs {
     uint4* st_state; uint4* st_stack; float4* st_ray; float4* st_conn;      // per pixel
 };
 
-#ifdef ATN_VOLUME_TU      // (the kernels: volume.hip; aten_amd.hip reads the declarations above)
+// what the GRID flavours read besides VolArgs (a kernel argument of their own: the gridless kernels' arguments stay as they are)
+struct VolGridArgs {
+    const atn_vg::Grid* grids;  // atn_volume_set_grids, the densities on the device
+    uint4* c_smp;               // per slot, the connection's own sample stream {idx, dim, scramble, ratio-tracking steps so far}
+};
+
+#ifdef ATN_VOLUME_TU      // (the kernels: volume.hip, volume_grid.hip; aten_amd.hip reads the declarations above)
 // ---- the medium stack --------------------------------------------------------------------------------------------------------
 struct VolStack { uint4 q; uint32_t n, bottom; };
 ATN_DEV VolStack vol_stack_load(const uint4& q, uint32_t meta) { VolStack s; s.q = q; s.n = meta & 15u; s.bottom = meta >> 16; return s; }
@@ -150,11 +161,44 @@ __global__ void ATN_TRACE_ATTR __launch_bounds__(kTraceBlock > 256 ? kTraceBlock
 // ---- the connection's walk: TraverseRayInMedium, volume_pathtracing_impl.h:111-229 ----------------------------------------------
 // One connection per lane; a closest-hit walk per segment (Job::finish hands the lane the next segment's ray).  The running state
 // (origin, remaining distance, transmittance, the stack's copy, boundaries crossed) lives in the connection record between segments.
-struct VolWalkJob {
+// the connection's sample stream as the tracking loops draw from it (device/volume_grid_track.h)
+struct VolDraw {
+    Cmj& smp;
+    ATN_DEV float next() { return cmj_next(smp); }
+};
+// the extra state of the GRID flavour: nothing for the gridless walk, so that VolWalkJobT<false> is laid out as VolWalkJob always was
+template <bool GRID> struct VolWalkGrid {};
+template <> struct VolWalkGrid<true> { VolGridArgs vg; };
+
+// GRID: a segment inside a grid medium is ratio-tracked with the connection's own stream (docs/VOLUME.md, "Grid media")
+template <bool GRID>
+struct VolWalkJobT : VolWalkGrid<GRID> {
     PathBuffers pb;
     DevScene sc;
     VolArgs va;
     float t_min;
+    // the transmittance of the segment org .. org + distance * dir in medium `md`.  false: the tracking loop hit its cap
+    ATN_DEV bool segment(uint32_t slot, const VolMedium& md, const f3& org, const f3& dir, float distance, float& transmittance) const
+    {
+        if constexpr (GRID) {
+            if (md.flags & kVolGridFlag) {
+                const atn_vg::Grid g = this->vg.grids[md.flags >> kVolGridShift];
+                const uint4 cs = this->vg.c_smp[slot];
+                Cmj smp{ cs.x, cs.y, cs.z };
+                VolDraw draw{ smp };
+                atn_vg::NoTie tie;
+                uint32_t steps = cs.w;
+                bool capped = false;
+                const float tr = atn_vg::ratio_track(g, md.sigma_a, md.sigma_s, md.sigma_t, org.x, org.y, org.z, dir.x, dir.y, dir.z, distance, draw, tie, steps, capped);
+                this->vg.c_smp[slot] = make_uint4(cs.x, smp.dim, cs.z, steps);
+                transmittance = transmittance * tr;
+                if (capped) atomicAdd(&va.counters[kVolCntFrame + 5], 1u);
+                return !capped;
+            }
+        }
+        transmittance = transmittance * expf(-md.sigma_t * distance);
+        return true;
+    }
     ATN_DEV void fetch(uint32_t j, float4& a, float4& b, float& stop_t) const
     {
         const uint32_t slot = va.conn_q[j];
@@ -185,6 +229,10 @@ struct VolWalkJob {
             float4* o = va.st_conn + 3u * (size_t)(pixel & 0x7fffffffu);
             o[2] = make_float4((float)segments, visible ? 1.0F : 0.0F, 0.0F, 0.0F);
             o[1].w = transmittance;
+            if constexpr (GRID) {       // the ratio-tracking steps and the final dimension of the connection's stream
+                const uint4 cs = this->vg.c_smp[slot];
+                o[2].z = (float)cs.w; o[2].w = (float)cs.y;
+            }
         }
     }
     ATN_DEV bool finish(uint32_t slot, const Hit& h, bool is_hit, float4& ra, float4& rb, float& rstop) const
@@ -215,7 +263,7 @@ struct VolWalkJob {
             }
             if (st.n > 0u) {
                 const float distance = length(org - rec.p);
-                transmittance = transmittance * expf(-va.med[st.bottom].sigma_t * distance);
+                if (!segment(slot, va.med[st.bottom], org, dir, distance, transmittance)) { end(slot, false, transmittance, bits, pixel, segments); return false; }
             }
             if (!vol_update_medium(dir, dir, rec.normal, mflags, (uint32_t)sc.materials[mslot].id, st)) atomicAdd(&va.counters[kVolCntFrame + 0], 1u);
             const f3 nml = dot(dir, rec.normal) > 0 ? rec.normal : -rec.normal;
@@ -234,18 +282,20 @@ struct VolWalkJob {
         if (st.n > 0u) {
             const f3 end_p = org + t_max * dir;
             const float distance = length(org - end_p);
-            transmittance = transmittance * expf(-va.med[st.bottom].sigma_t * distance);
+            if (!segment(slot, va.med[st.bottom], org, dir, distance, transmittance)) { end(slot, false, transmittance, bits, pixel, segments); return false; }
         }
         end(slot, true, transmittance, bits, pixel, segments);
         return false;
     }
 };
+using VolWalkJob = VolWalkJobT<false>;
 
+#ifndef ATN_VOLUME_GRID_TU      // (volume_grid.hip instantiates the GRID flavours only: the gridless kernels live in volume.hip)
 template <bool REFILL, bool LDSN>
 __global__ void ATN_TRACE_ATTR __launch_bounds__(kTraceBlock > 256 ? kTraceBlock : 256) k_vol_transmit(PathBuffers pb, DevScene sc, VolArgs va, int32_t it)
 {
     const uint32_t count = va.counters[kVolCntConn + it];
-    const VolWalkJob job{ pb, sc, va, kEps };
+    const VolWalkJob job{ {}, pb, sc, va, kEps };
     TravCounters tc{};
     trace_dispatch<false, REFILL, VolWalkJob, LDSN>(sc, count, &va.counters[kVolCntFetchT + it], job, &tc);
 }
@@ -278,6 +328,8 @@ __global__ void __launch_bounds__(256) k_vol_reduce(FrameParams fp, VolArgs va)
         if (sb) atomicAdd(&va.counters[kVolCntFrame + 2], sb);
     }
 }
+
+#endif  // !ATN_VOLUME_GRID_TU
 
 // SampleLight (pathtracing_impl.h:178-208) + the connection record of a scatter event (TraverseShadowRay, volume_pathtracing_impl.h:
 // 231-283): the ray direction stands in for a normal.  Returns whether a record was written.
@@ -314,267 +366,19 @@ ATN_DEV bool vol_event_connection(const DevScene& sc, const VolArgs& va, uint32_
 }
 
 // VolumePathTracing::Nee (volume_pathtracing.cpp:228-407) + ShadeMiss with bounce = depth_count + the bookkeeping of TraverseShadowRay
-// (volume_pathtracing_impl.h:285-293), one path per lane over the iteration's queue
+// (volume_pathtracing_impl.h:285-293), one path per lane over the iteration's queue.  The body is device/volume_shade_body.hpp, shared as
+// text with k_vol_shade_grid (device/volume_grid.hpp)
+#ifndef ATN_VOLUME_GRID_TU
 template <int MS>
 __global__ void __launch_bounds__(256) k_vol_shade(PathBuffers pb, DevScene sc, FrameParams fp, atn_camera_param cam, VolArgs va, int32_t it)
 {
-    __shared__ BlockAppendShared sh;
-    const uint32_t count = va.counters[kVolCntQueue + it];
-    const uint32_t* __restrict__ q = pb.queue[it & 1];
-    uint32_t* qn = pb.queue[(it + 1) & 1];
-    for (uint32_t j0 = blockIdx.x * 256u; j0 < count; j0 += gridDim.x * 256u) {
-        const uint32_t j = j0 + threadIdx.x;
-        bool push_next = false, push_conn = false;
-        uint32_t slot = 0u;
-        if (j < count) {
-            slot = q[j];
-            const float4 ro4 = pb.ray_o[slot], rd4 = pb.ray_d[slot];
-            f3 ray_org = mk3(ro4);
-            const f3 ray_dir = mk3(rd4);
-            float pdfb = ro4.w;
-            uint32_t flags = __float_as_uint(rd4.w) & ~F_HIT;
-            const float4 is4 = pb.isect[slot];
-            const int32_t hit_objid = __float_as_int(is4.x);
-            const float4 thr4 = pb.thr[slot];
-            f3 throughput = mk3(thr4);
-            uint32_t meta = va.meta[slot];
-            VolStack st = vol_stack_load(va.stack[slot], meta);
-            int32_t depth = (int32_t)((meta >> 4) & 255u);
-            bool sh_active = ((meta >> 12) & 1u) != 0u;
-            int32_t px = 0, py = 0;
-            slot_to_pixel(fp, slot, px, py);
-            const uint32_t pixel = (uint32_t)(py * fp.width + px);
-            Cmj smp;
-            {
-                const uint32_t fs = fp.frame + (uint32_t)fp.sample;
-                const uint32_t rnd = pb.seeds[pixel < fp.n_seeds ? pixel : pixel % fp.n_seeds];
-                smp.idx = fs % 256u; smp.dim = __float_as_uint(thr4.w); smp.scramble = rnd * 0x1fe3434fu * ((fs + 133u * rnd) / 256u);
-            }
-            const bool cap = va.capture == it && fp.sample == 0;
-            const uint32_t pixel_bits = pixel | (cap ? 0x80000000u : 0u);
-            uint32_t sflags = kVolProcessed;
-            float s_dist = 0.0F;
-            f3 next_o = ray_org, next_d = ray_dir;
-            bool new_ray = false;
-            f3 contrib_add = mk3(0.0F);
-            bool contrib_changed = false;
-
-            if (hit_objid < 0) {
-                // ---------------- ShadeMiss (pathtracing_impl.h:112-175), bounce = depth_count
-                f3 dir = ray_dir;
-                if (depth == 0) {
-                    const float s = (float)px / (float)fp.width;
-                    const float t = (float)py / (float)fp.height;
-                    f3 o;
-                    pinhole_sample(cam, s, t, o, dir);
-                }
-                const float4 emit = background_sample(sc, dir);
-                float misW = 1.0f;
-                if (!(depth == 0 || (depth == 1 && (flags & F_SINGULAR)))) {
-                    float pdfLight = luminance(emit.x, emit.y, emit.z) / sc.avgIllum;
-                    pdfLight /= (2.0f * kPi);
-                    if (sc.ibl_importance) pdfLight = ibl_direction_pdf(sc, dir);
-                    misW = pdfb / (pdfLight + pdfb);
-                }
-                f3 c = 1.0F * mk3(mul4(misW, emit)) + mk3(0.0F);
-                c = c * throughput;
-                contrib_add = c; contrib_changed = true;
-                flags |= F_TERMINATED;
-            }
-            else {
-                flags |= F_HIT;
-                sflags |= kVolHit;
-                const float hit_t = va.hit_t[slot];
-                // ---- ComputeRussianProbability on depth_count
-                float russian_prob = 1.0f;
-                if (depth > fp.rr_depth) {
-                    if (dot(throughput, throughput) > 0) {
-                        russian_prob = max3(throughput);
-                        const float p = cmj_next(smp);
-                        if (p >= russian_prob) flags |= F_TERMINATED; else flags &= ~F_TERMINATED;
-                    }
-                }
-                bool will_update_depth = false;
-                if (flags & F_TERMINATED) {
-                    // Nee returns before it clears the shadow ray: TraverseShadowRay connects the LAST event's point again
-                    if (sh_active) {
-                        const float4 eo = va.ev_o[slot], ed = va.ev_d[slot];
-                        push_conn = vol_event_connection(sc, va, slot, pixel_bits, smp, mk3(eo), mk3(ed), throughput, st);
-                    }
-                }
-                else {
-                    throughput = throughput / russian_prob;
-                    const int32_t tri_id = __float_as_int(is4.w);
-                    HitRec rec;
-                    evaluate_hit(rec, sc, hit_objid, tri_id, is4.y, is4.z);
-                    const int32_t mtrlid = triangle_mtrlid(sc, tri_id);
-                    const int32_t mtrl_slot = mtrlid >= 0 ? mtrlid : sc.n_materials;
-                    const DevMaterial& m = sc.materials[mtrl_slot];
-                    const uint32_t mflags = va.med[mtrl_slot].flags;
-                    const bool isBackfacing = dot(rec.normal, -ray_dir) < 0.0F;
-                    f3 orienting_normal = rec.normal;
-                    sh_active = false;
-                    bool is_scattered = false;
-                    f3 ev_dir = ray_dir;
-                    if (st.n > 0u) {
-                        // ---- HomogeniousMedium::Sample, medium.h:26-83
-                        const VolMedium md = va.med[st.bottom];
-                        const float sigma_t = md.sigma_a + md.sigma_s;
-                        const float r1 = cmj_next(smp);
-                        // the logarithm in double, rounded once (as the host library's logf evaluates it): at most 1 ulp from the twin's,
-                        // so s stays within 2 ulp behind the division by ANY sigma_t.  With logf (<= 1 ulp, but on the other side of
-                        // the true value at times) the two logarithms lay up to 2 ulp apart, and a sigma_t that is no power of two
-                        // turned that into 3 ulp of s (docs/VOLUME.md, "Parity")
-                        const float s = -(float)log((double)smax(1.0F - r1, 0.0F)) / sigma_t;
-                        s_dist = s;
-                        sflags |= kVolSampled;
-                        if (s >= hit_t) ray_org = ray_org + ray_dir * hit_t;
-                        else {
-                            const float r2 = cmj_next(smp);
-                            const float Pa = md.sigma_a / sigma_t;
-                            ray_org = ray_org + ray_dir * s;
-                            if (r2 < Pa) { throughput = throughput * mk3(md.le[0], md.le[1], md.le[2]); sflags |= kVolAbsorbed; }
-                            else {
-                                const float r3 = cmj_next(smp);
-                                const float r4 = cmj_next(smp);
-                                ev_dir = normalize(hg_sample(r3, r4, md.g, -ray_dir));
-                                sflags |= kVolScattered;
-                            }
-                            is_scattered = true;
-                            sh_active = true;
-                            va.ev_o[slot] = make_float4(ray_org.x, ray_org.y, ray_org.z, 0.0F);
-                            va.ev_d[slot] = make_float4(ev_dir.x, ev_dir.y, ev_dir.z, 0.0F);
-                        }
-                    }
-                    bool is_reflected_or_refracted = false;
-                    if (is_scattered) { next_o = ray_org; next_d = ev_dir; new_ray = true; }
-                    else if ((m.attrib & ATN_MTRL_ATTR_EMISSIVE) && !isBackfacing) {
-                        // ---- HitImplicitLight, pathtracing_impl.h:395-451 (ray.org is the hit point after a free flight without event)
-                        const int32_t lid = sc.objects[hit_objid].light_id;
-                        const f3 light_color = (lid >= 0 && lid < sc.n_lights) ? area_light_color(sc.lights[lid], rec.area) : mk3(0.0F);
-                        float weight = 1.0f;
-                        if (depth > 0) {
-                            const float cosLight = dot(rec.normal, -ray_dir);
-                            const f3 dv = rec.p - ray_org;
-                            const float dist2 = dot(dv, dv);
-                            if (cosLight >= 0) {
-                                float pdfLight = 1 / rec.area;
-                                pdfLight = (pdfLight * dist2) / cosLight;
-                                weight = pdfb / (pdfb + pdfLight);
-                            }
-                        }
-                        contrib_add = (throughput * weight) * light_color; contrib_changed = true;
-                        flags |= F_TERMINATED;
-                    }
-                    else {
-                        const VolStack st_before = st;
-                        if ((mflags & (kVolMediumFlag | kVolPureFlag)) == (kVolMediumFlag | kVolPureFlag)) {
-                            // a pure medium boundary: straight through
-                            const f3 base = dot(ray_dir, orienting_normal) > 0 ? orienting_normal : -orienting_normal;
-                            next_o = ray_offset(rec.p, base);
-                            next_d = normalize(ray_dir);
-                            new_ray = true;
-                            sflags |= kVolPassed;
-                        }
-                        else {
-                            const float4 albedo4 = sample_texture(sc, m.albedoMap, rec.u, rec.v, m.baseColor);
-                            const f3 albedo = mk3(albedo4);
-                            if (!(m.attrib & ATN_MTRL_ATTR_TRANSLUCENT) && isBackfacing) orienting_normal = -orienting_normal;
-                            const float pre_r = apply_normal<MS>(sc, m, mtrl_slot, orienting_normal, rec.u, rec.v, ray_dir, smp);
-                            // what the BSDF sample, the NEE evaluation and the light sample share at this vertex (shading.hpp, HitPre)
-                            HitPre hp;
-                            tangent_coordinate(orienting_normal, hp.t, hp.b);
-                            hp.rough = ggx_roughness(sc, m, rec.u, rec.v);
-                            hp.lambda_v = m.type == ATN_MTRL_GGX ? ggx_lambda(hp.rough, -ray_dir, orienting_normal) : 0.0F;
-                            // ---- SampleLight + the connection record (the walk runs in k_vol_transmit: it draws nothing)
-                            const bool invalid_mtrl = (m.attrib & (ATN_MTRL_ATTR_SINGULAR | ATN_MTRL_ATTR_TRANSLUCENT)) != 0;
-                            if (sc.n_lights > 0 && !invalid_mtrl) {
-                                int32_t li = (int32_t)(cmj_next(smp) * (float)sc.n_lights);
-                                li = li < sc.n_lights - 1 ? li : sc.n_lights - 1;
-                                LightSample ls;
-                                ls.attrib = sc.lights[li].attrib;
-                                sample_light(ls, sc.lights[li], sc, rec.p, orienting_normal, smp, &hp);
-                                f3 radiance = mk3(0.0F);
-                                const bool ok = radiance_nee_then<MS>(sc, ray_dir, orienting_normal, m, rec.u, rec.v, sc.inv_n_lights, ls, mtrl_slot, pre_r, nullptr,
-                                                                      [&](const f3& r) { radiance = r; }, &hp);
-                                const f3 nml = dot(ls.dir, orienting_normal) > 0 ? orienting_normal : -orienting_normal;
-                                const f3 o = ray_offset(rec.p, nml);
-                                const f3 d = normalize(ls.dir);
-                                float dist = ls.dist;
-                                if (ls.attrib & ATN_LIGHT_ATTR_INFINITE) dist = length(ls.pos - rec.p);
-                                const float t_max = dist - va.eps_bias;
-                                va.c_o[slot] = make_float4(o.x, o.y, o.z, t_max);
-                                va.c_d[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(kVolConnSurface | (ok ? 0u : kVolConnNoAdd)));
-                                va.c_w[slot] = make_float4(1.0F, __uint_as_float(pixel_bits), __uint_as_float(vol_stack_meta(st)), __uint_as_float(0u));
-                                va.c_a[slot] = make_float4(throughput.x, throughput.y, throughput.z, 0.0F);
-                                va.c_b[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0F);
-                                va.c_c[slot] = make_float4(albedo.x, albedo.y, albedo.z, 0.0F);
-                                va.c_stack[slot] = st.q;
-                                if (cap && va.st_conn) {
-                                    float4* so = va.st_conn + 3u * (size_t)pixel;
-                                    so[0] = make_float4(o.x, o.y, o.z, t_max);
-                                    so[1] = make_float4(d.x, d.y, d.z, 1.0F);
-                                }
-                                push_conn = true;
-                            }
-                            // ---- sampleMaterial + PrepareForNextBounce (the roulette probability divides a second time, as written)
-                            MtrlSample ms;
-                            sample_material<MS>(ms, sc, m, orienting_normal, ray_dir, smp, rec.u, rec.v, mtrl_slot, pre_r, &hp);
-                            const f3 ndir = normalize(ms.dir);
-                            const f3 ray_along_normal = dot(orienting_normal, ndir) >= 0.0f ? orienting_normal : -orienting_normal;
-                            const float c = dot(ray_along_normal, ndir);
-                            if (ms.pdf > 0 && c > 0) {
-                                throughput = throughput * ((((albedo * ms.bsdf) * c) / ms.pdf));
-                                throughput = throughput / russian_prob;
-                            }
-                            else flags |= F_TERMINATED;
-                            if (!(flags & F_TERMINATED)) {
-                                pdfb = ms.pdf;
-                                flags = (m.attrib & ATN_MTRL_ATTR_SINGULAR) ? (flags | F_SINGULAR) : (flags & ~F_SINGULAR);
-                                next_o = ray_offset(rec.p, ray_along_normal);
-                                next_d = normalize(ndir);
-                                new_ray = true;
-                            }
-                            is_reflected_or_refracted = true;
-                        }
-                        (void)st_before;
-                        // ---- UpdateMedium with the ray that goes on (rays[idx].dir)
-                        if (!vol_update_medium(ray_dir, next_d, orienting_normal, mflags, (uint32_t)m.id, st)) atomicAdd(&va.counters[kVolCntFrame + 0], 1u);
-                    }
-                    will_update_depth = is_scattered || is_reflected_or_refracted;
-                    // ---- TraverseShadowRay's connection of this iteration's event (the stack is the path's: an event leaves it alone)
-                    if (is_scattered) push_conn = vol_event_connection(sc, va, slot, pixel_bits, smp, ray_org, ev_dir, throughput, st);
-                }
-                if (will_update_depth) depth += 1;
-                if (depth > fp.max_depth) flags |= F_TERMINATED;
-            }
-            if (push_conn) sflags |= kVolConn;
-            // radiance's loop ends a path after MedisumStackSize iterations
-            if (!(flags & F_TERMINATED) && it + 1 >= kVolIterations) flags |= F_TERMINATED;
-            push_next = !(flags & F_TERMINATED);
-            if (new_ray) pb.ray_o[slot] = make_float4(next_o.x, next_o.y, next_o.z, pdfb);
-            pb.ray_d[slot] = make_float4(next_d.x, next_d.y, next_d.z, __uint_as_float(flags));
-            pb.thr[slot] = make_float4(throughput.x, throughput.y, throughput.z, __uint_as_float(smp.dim));
-            meta = vol_stack_meta(st) | ((uint32_t)depth << 4) | (sh_active ? 1u << 12 : 0u);
-            va.meta[slot] = meta;
-            va.stack[slot] = st.q;
-            if (contrib_changed) {
-                const f3 contrib = mk3(pb.contrib[slot]) + contrib_add;
-                pb.contrib[slot] = make_float4(contrib.x, contrib.y, contrib.z, 0.0F);
-            }
-            if (cap && va.st_state) {
-                if (flags & F_TERMINATED) sflags |= kVolTerminated;
-                va.st_state[pixel] = make_uint4(sflags, (uint32_t)depth, st.n, smp.dim);
-                va.st_stack[pixel] = st.q;
-                va.st_ray[2u * (size_t)pixel] = make_float4(next_o.x, next_o.y, next_o.z, s_dist);
-                va.st_ray[2u * (size_t)pixel + 1u] = make_float4(next_d.x, next_d.y, next_d.z, hit_objid >= 0 ? va.hit_t[slot] : 0.0F);
-            }
-        }
-        block_append2(sh, qn, &va.counters[kVolCntQueue + it + 1], push_next ? 1u : 0u, va.conn_q, &va.counters[kVolCntConn + it], push_conn ? 1u : 0u,
-                      [&](int) { return slot; });
-    }
+#define ATN_VOL_SHADE_GRID 0
+#include "volume_shade_body.hpp"
+#undef ATN_VOL_SHADE_GRID
 }
+#endif
 
+#ifndef ATN_VOLUME_GRID_TU
 // HenyeyGreensteinPhaseFunction::SampleDirection(r1, r2, g, w) and Evaluate(g, w, wo) for n cases (atn_volume_phase_table)
 __global__ void __launch_bounds__(256) k_vol_phase_table(float g, uint32_t n, const float* __restrict__ w, const float* __restrict__ r1,
                                                          const float* __restrict__ r2, const float* __restrict__ wo, float* __restrict__ out_dir,
@@ -587,6 +391,7 @@ __global__ void __launch_bounds__(256) k_vol_phase_table(float g, uint32_t n, co
     out_dir[3u * i] = d.x; out_dir[3u * i + 1u] = d.y; out_dir[3u * i + 2u] = d.z;
     out_eval[i] = hg_evaluate(g, ww, mk3(wo[3u * i], wo[3u * i + 1u], wo[3u * i + 2u]));
 }
+#endif  // !ATN_VOLUME_GRID_TU
 #endif  // ATN_VOLUME_TU
 
 } // namespace atn

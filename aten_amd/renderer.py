@@ -540,7 +540,25 @@ class PathTracing:
         return dict(kind=out[..., 0, 0].astype(np.int32), walks=out[..., 0, 1].astype(np.int32), answer=out[..., 0, 2].astype(np.int32),
                     singular=out[..., 0, 3] != 0, throughput=out[..., 1, :3].copy(), transmission=out[..., 1, 3].copy())
 
-    # ---- volume rendering: path tracing through homogeneous media (aten::VolumePathTracing; docs/VOLUME.md)
+    # ---- volume rendering: path tracing through homogeneous and grid media (aten::VolumePathTracing; docs/VOLUME.md)
+    def volume_set_grids(self, grids):
+        """The dense grids a medium names by grid_idx (SceneBuilder.add_medium_material(grid=...)): a list of
+        (density float32 [z, y, x], origin (x, y, z), voxel_size), copied; [] drops them.  A built scene carries its own as
+        FlatScene.grids.  They outlive the update_* edits; upload_scene drops them."""
+        grids = list(grids)
+        arr = (VolumeGrid * max(1, len(grids)))()
+        keep = []
+        for i, (density, origin, voxel_size) in enumerate(grids):
+            d = np.ascontiguousarray(density, np.float32)
+            if d.ndim != 3:
+                raise ValueError("a grid's density is an array [z, y, x]")
+            keep.append(d)
+            arr[i].dim[:] = [d.shape[2], d.shape[1], d.shape[0]]
+            arr[i].origin[:] = [float(c) for c in origin]
+            arr[i].voxel_size = float(voxel_size)
+            arr[i].density = d.ctypes.data
+        self._check(self._l.atn_volume_set_grids(self._ctx, C.byref(arr) if grids else None, len(grids)))
+
     def volume_render(self, width, height, max_depth=5, rr_depth=3, spp=1, frame=0, progressive=True, break_on_terminate=True,
                       download=True, profile=False):
         """One frame through the scene's media (materials with is_medium set) into the film; returns the film [h, w, 4]."""
@@ -563,12 +581,19 @@ class PathTracing:
         hit, sampled, absorbed, scattered, passed, connection, terminated and int32 depth_count, stack_size, uint32 dim;
         'stack': int32 [h, w, 8], the medium stack in the order entered (entries beyond stack_size are 0);
         'ray': dict org [h, w, 3], dir [h, w, 3], s, hit_t; 'conn': dict org, dir, t_max, transmittance, segments (int32), visible;
-        'counters': dict stack_overflow, walk_overflow, connections, segments of the last frame."""
+        'counters': dict stack_overflow, walk_overflow, connections, segments of the last frame;
+        'grid_counters': dict flight_capped, connection_capped: grid flights / connections stopped after 16384 tracking steps.
+        With grid media 'state' has flight_steps (the delta-tracking steps of the flight), and 'conn' track_steps and stream_dim (the
+        ratio-tracking steps and the final dimension of the connection's own sample stream)."""
         w, h = self.width, self.height
         if name == "counters":
             out = np.zeros(4, np.uint32)
             self._check(self._l.atn_volume_download(self._ctx, 4, out.ctypes.data))
             return dict(stack_overflow=int(out[0]), walk_overflow=int(out[1]), connections=int(out[2]), segments=int(out[3]))
+        if name == "grid_counters":
+            out = np.zeros(2, np.uint32)
+            self._check(self._l.atn_volume_download(self._ctx, 5, out.ctypes.data))
+            return dict(flight_capped=int(out[0]), connection_capped=int(out[1]))
         if name == "state":
             out = np.empty((h, w, 4), np.uint32)
             self._check(self._l.atn_volume_download(self._ctx, 0, out.ctypes.data))
@@ -587,7 +612,8 @@ class PathTracing:
             out = np.empty((h, w, 3, 4), np.float32)
             self._check(self._l.atn_volume_download(self._ctx, 3, out.ctypes.data))
             return dict(org=out[..., 0, :3].copy(), t_max=out[..., 0, 3].copy(), dir=out[..., 1, :3].copy(), transmittance=out[..., 1, 3].copy(),
-                        segments=out[..., 2, 0].astype(np.int32), visible=out[..., 2, 1] != 0)
+                        segments=out[..., 2, 0].astype(np.int32), visible=out[..., 2, 1] != 0,
+                        track_steps=out[..., 2, 2].astype(np.int32), stream_dim=out[..., 2, 3].astype(np.int32))
         raise ValueError("no volume buffer %r" % (name,))
 
     def volume_phase_table(self, g, w, r1, r2, wo):
@@ -1112,6 +1138,11 @@ class MultiGpuPathTracing:
         self._check(self._l.atn_mgpu_reset_kernel_times(self._mg))
 
 
+class VolumeGrid(C.Structure):
+    """atn_volume_grid (include/aten_amd.h)."""
+    _fields_ = [("dim", C.c_int32 * 3), ("origin", C.c_float * 3), ("voxel_size", C.c_float), ("density", C.c_void_p)]
+
+
 VOLUME_STATE_FLAGS = dict(processed=1, hit=2, sampled=4, absorbed=8, scattered=16, passed=32, connection=64, terminated=256)
 
 
@@ -1124,7 +1155,8 @@ def unpack_primary_hit(plane):
 def unpack_volume_state(raw):
     """uint32 [h, w, 4] {flags, depth_count, stack size, CMJ dimension} of atn_volume_download(0) -> dict."""
     out = {k: (raw[..., 0] & v) != 0 for k, v in VOLUME_STATE_FLAGS.items()}
-    out.update(depth_count=raw[..., 1].astype(np.int32), stack_size=raw[..., 2].astype(np.int32), dim=raw[..., 3].copy())
+    out.update(depth_count=raw[..., 1].astype(np.int32), stack_size=raw[..., 2].astype(np.int32), dim=raw[..., 3].copy(),
+               flight_steps=((raw[..., 0] >> 16) & 0x7fff).astype(np.int32))
     return out
 
 

@@ -48,10 +48,11 @@ def write_feature_line_config(config, enabled, color=(0.0, 0.0, 0.0), width=1.0,
     C.memmove(C.addressof(config) + L.SceneRenderingConfig.feature_line.offset, b, len(b))
 
 
-def write_medium(m, g, sigma_a, sigma_s, le=(0.0, 0.0, 0.0)):
+def write_medium(m, g, sigma_a, sigma_s, le=(0.0, 0.0, 0.0), grid_idx=-1, majorant=-1.0):
     """atn_medium_param (32 B: phase_function_g, sigma_a, sigma_s, int32 grid_idx = -1, majorant = -1, le[3]) into a MATERIAL_PARAM
     record's `medium` bytes, and is_medium = 1."""
-    m["medium"] = np.frombuffer(struct.pack("<fffif3f", float(g), float(sigma_a), float(sigma_s), -1, -1.0, *[float(c) for c in le]), F32)
+    m["medium"] = np.frombuffer(struct.pack("<fffif3f", float(g), float(sigma_a), float(sigma_s), int(grid_idx), float(majorant),
+                                            *[float(c) for c in le]), F32)
     m["is_medium"] = 1
 
 
@@ -67,6 +68,7 @@ class FlatScene:
         self.desc = L.SceneDesc()
         self.keep = []
         self.names = {}
+        self.grids = []
 
     def ref(self):
         return C.byref(self.desc)
@@ -135,6 +137,7 @@ class SceneBuilder:
         self.blas = {}          # polygon object id -> node array (or None = build)
         self.bvh_options = None # dict of atns_bvh_options fields for atns_build_blas_opt (None = DEFAULT_BVH_OPTIONS / the library's)
         self.mesh_counter = 0
+        self.grids = []         # (density float32 [z, y, x], origin, voxel_size): PathTracing.volume_set_grids
         self.config = L.SceneRenderingConfig()
         self.config.bvh_hit_min = -1.0
         self.config.epsilon_bias = 1e-3
@@ -171,14 +174,31 @@ class SceneBuilder:
         m["medium"][4] = -1.0                       # majorant
         write_feature_line_mtrl(m, *feature_line)
         if medium is not None:
-            write_medium(m, medium["g"], medium["sigma_a"], medium["sigma_s"], medium.get("le", (0.0, 0.0, 0.0)))
+            write_medium(m, medium["g"], medium["sigma_a"], medium["sigma_s"], medium.get("le", (0.0, 0.0, 0.0)),
+                         medium.get("grid_idx", -1), medium.get("majorant", -1.0))
         self.materials.append((name, m))
         return len(self.materials) - 1
 
-    def add_medium_material(self, name, g, sigma_a, sigma_s, le=(0.0, 0.0, 0.0)):
+    def add_grid(self, density, origin, voxel_size):
+        """A dense density grid (float32 [z, y, x], x fastest; world box origin .. origin + dim * voxel_size) for a heterogeneous
+        medium; returns its index.  The built scene carries the list as FlatScene.grids for PathTracing.volume_set_grids."""
+        d = np.ascontiguousarray(density, F32)
+        assert d.ndim == 3
+        self.grids.append((d, tuple(float(c) for c in origin), float(voxel_size)))
+        return len(self.grids) - 1
+
+    def add_medium_material(self, name, g, sigma_a, sigma_s, le=(0.0, 0.0, 0.0), grid=None, majorant=None):
         """material::CreateMaterialMediumParameter (material/material.cpp:212-232): type Volume, is_medium, no attribute bits -- a
-        pure medium boundary (a closed mesh around a homogeneous medium).  Everything else is MaterialParameter's default."""
-        mid = self.add_material(name, L.MTRL_VOLUME, (0.0, 0.0, 0.0), medium=dict(g=g, sigma_a=sigma_a, sigma_s=sigma_s, le=le))
+        pure medium boundary (a closed mesh around a homogeneous medium).  Everything else is MaterialParameter's default.
+        grid = an index of add_grid: a heterogeneous medium whose sigma_s scales with the grid's density; majorant = None writes
+        HeterogeneousMedium::EvalMajorant, (sigma_a + sigma_s) * the grid's largest density (volume/medium.cpp:10-25), in float.
+        grid = None writes the homogeneous bytes (grid_idx -1, majorant -1)."""
+        medium = dict(g=g, sigma_a=sigma_a, sigma_s=sigma_s, le=le)
+        if grid is not None:
+            if majorant is None:
+                majorant = F32(F32(F32(sigma_a) + F32(sigma_s)) * F32(self.grids[grid][0].max()))
+            medium.update(grid_idx=int(grid), majorant=float(majorant))
+        mid = self.add_material(name, L.MTRL_VOLUME, (0.0, 0.0, 0.0), medium=medium)
         self.materials[mid][1]["attrib"] = 0
         return mid
 
@@ -731,6 +751,7 @@ class SceneBuilder:
         fs.arrays = dict(objects=objs, matrices=mtx, materials=mats, lights=lights, triangles=tris,
                          vtx_pos=pos, vtx_nml=nml, bvh_lists=bvh_lists, textures=[t for _, t in self.textures])
         fs.names = dict(materials=[n for n, _ in self.materials], textures=[n for n, _ in self.textures])
+        fs.grids = list(self.grids)           # add_grid: what PathTracing.volume_set_grids takes
         return fs
 
 

@@ -823,3 +823,88 @@ def ao_room(asset_dir=None, pane_height=0.25):
     b.set_background((0.0, 0.0, 0.0))
     cam = dict(pos=(0.0, 1.0, 3.0), at=(0.0, 1.0, 0.0), vfov=45.0)
     return b.build(), cam
+
+
+# ---------------------------------------------------------------------------------------------------
+# Grid media (PathTracing.volume_set_grids(fs.grids); docs/VOLUME.md, "Grid media")
+# ---------------------------------------------------------------------------------------------------
+def cornell_box_smoke_grid(sigma_s=4.0):
+    """cornell_box_smoke with a heterogeneous smoke: a cubic smoke box (side 1.5, every coordinate a binary fraction) that is exactly
+    the world box of an 8 x 8 x 8 grid.  The density is a ramp in y (0.25 at the floor, 1 at the top) times a checkerboard of
+    2 x 2 x 2 blocks with empty blocks between: null collisions, events and empty cells all occur.  sigma_s 4 against a largest
+    density of 1 gives a majorant of 4, six expected tracking steps across the box."""
+    b, cam = _cornell_with(lambda b, name, mtype, clr, albedo, nml: b.add_material(name, mtype, clr))
+    z, y, x = np.meshgrid(np.arange(8), np.arange(8), np.arange(8), indexing="ij")
+    density = ((0.25 + 0.75 * y / 7.0) * (((x // 2 + y // 2 + z // 2) % 2) == 0)).astype(np.float32)
+    bmin, side = (-0.75, 0.0625, -0.75), 1.5
+    grid = b.add_grid(density, bmin, side / 8)
+    smoke = b.add_medium_material("medium", -0.4, 0.0, sigma_s, (1.0, 0.0, 0.0), grid=grid)
+    p, tri = _box_mesh(bmin, tuple(c + side for c in bmin))
+    b.create_instance(b.add_mesh("smoke", p, tri, smoke))
+    return b.build(), cam
+
+
+def smoke_grid_ragged(sigma_s=3.0):
+    """The Cornell box inside a medium boundary that also holds the area light, with a 5 x 3 x 7 grid whose origin lies off the voxel
+    lattice and whose box is smaller than the boundary mesh: rays miss the grid's box, cross it, or end in it at one of the two
+    diffuse boxes, which stand half inside the grid; connections end at the light inside the medium but outside the grid.  A second,
+    homogeneous medium straddles the front face of the boundary, so a path can enter it first and carry it at the bottom of its
+    stack into the grid medium, or the other way round."""
+    b, cam = _cornell_with(lambda b, name, mtype, clr, albedo, nml: b.add_material(name, mtype, clr))
+    r = np.random.default_rng(7).random((7, 3, 5))
+    density = np.where(r < 0.3, 0.0, r).astype(np.float32)
+    grid = b.add_grid(density, (-0.53, 0.31, -0.61), 0.21)
+    smoke = b.add_medium_material("smoke", 0.3, 0.0, sigma_s, (0.0, 0.0, 0.0), grid=grid)
+    p, tri = _box_mesh((-0.9, 0.05, -0.9), (0.9, 1.7, 0.9))
+    b.create_instance(b.add_mesh("smoke", p, tri, smoke))
+    haze = b.add_medium_material("haze", -0.2, 0.1, 0.7, (0.2, 0.2, 0.6))
+    p, tri = _box_mesh((-0.3, 0.9, 0.6), (0.3, 1.3, 1.2))
+    b.create_instance(b.add_mesh("haze", p, tri, haze))
+    return b.build(), cam
+
+
+def constant_grid_slab(sigma_s=2.0, density=0.5, grid=True, box=False, majorant_scale=1.0, light=False, thickness=1.0, bg=(1.0, 1.0, 1.0), half=50.0):
+    """absorbing_slab's geometry with a scattering medium (sigma_a 0): grid = True a 4 x 4 x 4 grid of constant `density` whose box
+    (side 100) holds the whole slab, grid = False the homogeneous medium of sigma_s * density -- in expectation the same picture
+    (docs/VOLUME.md, the acceptance rule of grid media).  box: a diffuse box stands inside the slab.  majorant_scale: the majorant
+    is that many times EvalMajorant's (1: every collision is real and the two scenes draw the same paths; above 1: null collisions).
+    light: a small area light stands inside the slab, facing the camera (the light inside the fog: every scatter event connects to
+    it through the medium, and the connection ends inside it)."""
+    b = SceneBuilder()
+    if grid:
+        g = b.add_grid(np.full((4, 4, 4), density, np.float32), (-half, -half, -0.75 * 2 * half), 2 * half / 4)
+        m = b.add_medium_material("slab", 0.0, 0.0, sigma_s, (0.0, 0.0, 0.0), grid=g, majorant=majorant_scale * sigma_s * density)
+    else:
+        m = b.add_medium_material("slab", 0.0, 0.0, sigma_s * density, (0.0, 0.0, 0.0))
+    p, tri = _box_mesh((-half, -half, -thickness), (half, half, 0.0))
+    b.create_instance(b.add_mesh("slab", p, tri, m))
+    if light:
+        e = b.add_material("light", L.MTRL_EMISSIVE, (1.0, 1.0, 1.0))
+        q = np.array([(-0.15, 0.35, -0.5 * thickness), (0.15, 0.35, -0.5 * thickness), (0.15, 0.65, -0.5 * thickness), (-0.15, 0.65, -0.5 * thickness)], np.float32)
+        b.add_area_light(b.create_instance(b.add_mesh("light", q, [[0, 1, 2], [0, 2, 3]], e)), (1.0, 1.0, 1.0), 20.0)
+    if box:
+        d = b.add_material("box", L.MTRL_DIFFUSE, (0.6, 0.4, 0.2))
+        p, tri = _box_mesh((-0.3, -0.3, -0.8 * thickness), (0.3, 0.3, -0.2 * thickness))
+        b.create_instance(b.add_mesh("box", p, tri, d))
+    b.set_background(bg)
+    return b.build(), dict(pos=(0.0, 0.0, 2.0), at=(0.0, 0.0, 0.0), vfov=45.0)
+
+
+def smoke_grid_sponza(sigma_s=0.6, g=0.2, n=64):
+    """fog_sponza with the fog replaced by an n^3 procedural grid (a sum of three sine waves, clipped at 0, largest value 1) over the
+    cube that holds the fog slab: the grid-media benchmark scene."""
+    def add_smoke(b, bmin, bmax, cam):
+        lo = np.asarray(bmin, np.float64) + 0.02 * (np.asarray(bmax, np.float64) - np.asarray(bmin, np.float64))
+        hi = np.asarray(bmax, np.float64) - 0.02 * (np.asarray(bmax, np.float64) - np.asarray(bmin, np.float64))
+        hi[2] = min(hi[2], cam["pos"][2] - 1.0)
+        lo[2] = min(lo[2], hi[2] - 1.0)
+        side = float((hi - lo).max())
+        t = (np.arange(n) + 0.5) / n
+        z, y, x = np.meshgrid(t, t, t, indexing="ij")
+        d = np.sin(9.0 * x + 2.0 * y) + np.sin(7.0 * y + 3.0 * z) + np.sin(11.0 * z + 5.0 * x)
+        d = np.clip(d / 3.0, 0.0, None)
+        grid = b.add_grid((d / d.max()).astype(np.float32), tuple(lo), side / n)
+        smoke = b.add_medium_material("smoke", g, 0.0, sigma_s, (0.0, 0.0, 0.0), grid=grid)
+        p, tri = _box_mesh(tuple(lo), tuple(hi))
+        b.create_instance(b.add_mesh("smoke", p, tri, smoke))
+    return sponza_lod(add_lights=add_smoke)

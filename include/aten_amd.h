@@ -565,12 +565,20 @@ int atn_npr_download(atn_ctx* ctx, int32_t which, void* out_host);
 int atn_npr_set_skip_through(atn_ctx* ctx, int32_t mode);
 int atn_npr_advance_download(atn_ctx* ctx, void* out_host);
 
-/* ---- Volume rendering: path tracing through homogeneous media (aten::VolumePathTracing / idaten::VolumeRendering; docs/VOLUME.md)
+/* ---- Volume rendering: path tracing through homogeneous and grid media (aten::VolumePathTracing / idaten::VolumeRendering; docs/VOLUME.md)
  * Materials with is_medium set carry a medium (atn_medium_param): type ATN_MTRL_VOLUME is a pure boundary the ray passes through,
  * any other type a surface with a scattering interior.  A path runs at most 8 iterations (the reference's cap); light connections
  * walk through medium boundaries and collect transmittance.
+ *   atn_volume_set_grids: n dense float grids (host arrays, copied) that a medium names by atn_medium_param.grid_idx; n = 0 drops them.
+ *                      A medium with 0 <= grid_idx < n is heterogeneous: delta tracking against atn_medium_param.majorant samples its
+ *                      free flight, ratio tracking its connections (HeterogeneousMedium, volume/medium.cpp:58-202).  The world box is
+ *                      origin .. origin + dim * voxel_size; a point maps to the voxel floor((p - origin) * (1 / voxel_size)); outside
+ *                      the box the density is 0.  Waits for frames in flight; the grids outlive atn_update_*, atn_upload_scene drops
+ *                      them.  A grid or medium that cannot be traced is refused by atn_volume_render, not here.
  *   atn_volume_render: one frame; the film follows atn_render's progressive / overwrite rules.  ATN_ERR_UNSUPPORTED for a medium
- *                      with grid_idx >= 0 (NanoVDB grids) or sigma_a + sigma_s <= 0, a screen shard with world > 1, path
+ *                      with grid_idx >= the number of grids set; a grid medium with sigma_a != 0, with a majorant that is not finite,
+ *                      <= 0, below sigma_s * max density, or above 1024 / box diagonal; a grid with a dim <= 0, a voxel_size that is
+ *                      not finite or <= 0, or a density that is not finite or < 0; sigma_a + sigma_s <= 0, a screen shard with world > 1, path
  *                      regeneration, relaxed shade math, count_stats, alpha blending with a material whose alpha may be < 1,
  *                      StencilType::STENCIL materials, CarPaint and Toon / Stylized materials.  A scene without media renders.
  *   atn_volume_reset: the film starts over (a fresh context's)
@@ -581,10 +589,20 @@ int atn_npr_advance_download(atn_ctx* ctx, void* out_host);
  *                        2 atn_vec4[w*h][2] {next ray org, sampled distance s} {next ray dir, hit distance};
  *                        3 atn_vec4[w*h][3] the connection {org, t_max} {dir, transmittance} {segments, visible, 0, 0};
  *                        4 uint32[4] the last frame's counters {pushes dropped on a full stack, connections that crossed 64
- *                        boundaries, connections, segments} (needs no capture).
+ *                        boundaries, connections, segments} (needs no capture);
+ *                        5 uint32[2] {grid flights, grid connections stopped after 16384 tracking steps} (needs no capture).
+ *                        With grid media, the flight's step count is in bits 16-30 of the flags, and the connection's third vector
+ *                        is {segments, visible, ratio-tracking steps, final dimension of the connection's sample stream}.
  *   atn_volume_phase_table: HenyeyGreensteinPhaseFunction::SampleDirection(r1, r2, g, w) -> out_dir[3 n] and Evaluate(g, w, wo) ->
  *                        out_eval[n] for n cases (host arrays; w, wo: float[3 n])
  * Additive entry points: atn_abi_version stays 3. */
+typedef struct atn_volume_grid {
+    int32_t dim[3];             /* voxels along x, y, z */
+    float origin[3];            /* the world position of voxel (0, 0, 0)'s low corner */
+    float voxel_size;
+    const float* density;       /* host floats, x fastest: dim[0] * dim[1] * dim[2] values */
+} atn_volume_grid;
+int atn_volume_set_grids(atn_ctx* ctx, const atn_volume_grid* grids, uint32_t n);
 int atn_volume_render(atn_ctx* ctx, const atn_destination* dst, atn_vec4* out_host);
 int atn_volume_reset(atn_ctx* ctx);
 int atn_volume_capture(atn_ctx* ctx, int32_t iteration);

@@ -229,7 +229,8 @@ typedef struct atn_feature_line_mtrl {
 /* Typed view of the medium bytes (atn_volume_render; the float member above stays as it is): aten::MediumParameter, 32 B
  * (material/material.h) = atn_material_param.medium, read when atn_material_param.is_medium != 0.  A pure medium boundary has
  * type ATN_MTRL_VOLUME (material::CreateMaterialMediumParameter, material.cpp:212-232); a surface type with is_medium set is a
- * surface with a scattering interior.  grid_idx >= 0 names a NanoVDB grid: refused (docs/VOLUME.md). */
+ * surface with a scattering interior.  grid_idx >= 0 names a grid of atn_volume_set_grids and makes the medium heterogeneous, tracked
+ * against `majorant` (docs/VOLUME.md, "Grid media"). */
 typedef struct atn_medium_param {
     float phase_function_g;               /*  0: Henyey-Greenstein g, clamped to [-1, 1] */
     float sigma_a;                        /*  4 */

@@ -6,7 +6,8 @@ JSON line.
 ms per frame: device events (torch.cuda.Event on the context's own stream) around `--steps` frames after `--warmup`, repeated
 `--repeats` times (median and spread).  Per kernel kind: the library's own event spans over `--steps` profiled frames (gen, closest =
 k_vol_closest, shade = k_vol_shade, trace_fused = k_vol_transmit, gather).  Segments per connection: the frame counters of
-atn_volume_download(4).
+atn_volume_download(4).  `--scenes smoke_grid_sponza` (fog_sponza with the fog replaced by a 64^3 procedural grid) measures grid
+media: its grids are set with volume_set_grids, and the cap counters of atn_volume_download(5) are reported.
 
     python tools/volume_bench.py [--steps 20] [--warmup 5] [--repeats 5] [--width 1920 --height 1080]
 """
@@ -37,7 +38,7 @@ def main():
     from aten_amd.scene import scenedefs
     from aten_amd.scene.camera import create_camera
     W, H = args.width, args.height
-    plain = {"fog_sponza": "sponza_lod", "cornell_box_smoke": "cornell_box"}
+    plain = {"fog_sponza": "sponza_lod", "cornell_box_smoke": "cornell_box", "smoke_grid_sponza": "sponza_lod", "cornell_box_smoke_grid": "cornell_box"}
     res = {"metric": "ms per frame (%dx%d, 1 spp, maxDepth %d, 1 frame in flight)" % (W, H, args.depth),
            "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats, "cases": {}}
 
@@ -47,6 +48,8 @@ def main():
         r.UpdateSceneData(fs)
         r.updateCamera(create_camera(cam["pos"], cam["at"], cam["vfov"], W, H))
         r.initSampler(W, H, 0)
+        if volume and fs.grids:
+            r.volume_set_grids(fs.grids)
         r._l.atn_stream.restype = C.c_void_p
         stream = torch.cuda.ExternalStream(r._l.atn_stream(r._ctx))
         frame = [0]
@@ -77,6 +80,8 @@ def main():
             cnt = r.volume_buffer("counters")
             out["counters_last_frame"] = cnt
             out["segments_per_connection"] = round(cnt["segments"] / max(cnt["connections"], 1), 4)
+            if fs.grids:
+                out["grid_counters_last_frame"] = r.volume_buffer("grid_counters")
         r.close()
         return out
     for name in args.scenes.split(","):
